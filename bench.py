@@ -34,7 +34,13 @@ wire (the xGMI / IPC granules carry 16 B per double) and stop-rule monitor traff
 of the same loop ([measured-here] row).
 
     python bench.py                      # 1 GPU
+    python bench.py --dump-outputs bench_outputs
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+
+A plain run sets up, warms up, times the steps and prints the JSON line. ``--dump-outputs DIR`` also
+writes what the last timed solve computed (theta, objective trace, iteration count) as ``DIR/*.npy``;
+``--full`` adds the measurements the headline figure does not need (the one-GPU calibration solves of
+the multi-GPU tournament's cost model).
 
 The other BASELINE.json configs (same JSON contract, own metric): ``--config cpu_gloo`` (configs[0]: the
 same GADMM over gloo CPU ranks, no GPU), ``--config logistic`` (configs[2]), ``--config dgadmm``
@@ -93,6 +99,12 @@ def main():
     ap.add_argument("--dim", type=int, default=10_000, help="real10m: features")
     ap.add_argument("--timeout", type=float, default=20.0,
                     help="multi-GPU hand-off deadline in seconds (a stalled peer ends a solve with done=4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline: after the timed steps write what the last timed solve left (theta, the "
+                         "objective trace, the iteration count) as DIR/<name>.npy in float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the one-GPU calibration solves of the "
+                         "multi-GPU tournament's cost model (one_gpu_us_per_iter_measured, model_error)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -310,7 +322,8 @@ def run_headline(args, rank, world, device, share):
         # candidates of a 4-rank shared-GPU rehearsal by up to 11 %: profiles/r06_b/calib), the other
         # families scaled by the ONE_GPU_US ratios; model_error = measured / predicted - 1 (ranks
         # time-sharing one GPU inflate it: the model has no term for that)
-        if os.environ.get("GADMM_TOURNAMENT_CALIBRATE", "1") != "0":
+        # Only under --full: the calibration is 5 more solves on another engine.
+        if args.full and os.environ.get("GADMM_TOURNAMENT_CALIBRATE", "1") != "0":
             calib_us = _one_gpu_calibration(args, rank, world, device, obj0)
         hop_us = max([h for h in (hop or {}).get("hop_us", []) if h is not None], default=None)
         scale = (calib_us / ONE_GPU_US["blocked"]) if calib_us else 1.0
@@ -337,6 +350,8 @@ def run_headline(args, rank, world, device, share):
     dl_mode = sol.blk is None or sol.blk.data_local  # theta-only exchange (payload formula below)
     data_local = dl_mode and repl == 0  # the halo mode also holds one neighbour head's shard per boundary
     per = np.diff(np.asarray([t0] + stamps)) * 1e3  # this rank's per-step wall times
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, sol, tr, iters, rank, world)
     if rank == 0:
         value = ms / 1e3
         out = {
@@ -395,6 +410,23 @@ def run_headline(args, rank, world, device, share):
         out["handoff_deadline_s"] = timeout_s  # the deadline of the warm-up and timed solves
         print(json.dumps(out), flush=True)
     sol.close()
+
+
+def _dump_outputs(out_dir, sol, trace, iters, rank, world):
+    """--dump-outputs: what the last timed solve left for its caller, as float64 ``.npy`` files (a few
+    KB): this rank's theta (one row per worker, chain order), the objective trace of iterations 1..iters
+    and the iteration count. Several ranks: every rank writes its own theta, rank 0 the rest."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    if sol.blk is not None:
+        theta = sol.blk.theta
+    else:
+        theta = sol.eng.local_theta() if hasattr(sol.eng, "local_theta") else None
+    if theta is not None:
+        np.save(os.path.join(out_dir, "theta%s.npy" % sfx), theta.detach().cpu().numpy().astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "objective_trace.npy"), np.asarray(trace[:iters], dtype=np.float64))
+        np.save(os.path.join(out_dir, "iterations.npy"), np.asarray([iters], dtype=np.float64))
 
 
 def run_cpu_gloo(args, rank, world):

@@ -486,6 +486,33 @@ def test_bench_json_contract():
     assert j["iterations_match_reference"] is True and j["value"] < 1.13
 
 
+def test_bench_dump_outputs(tmp_path, lin24):
+    """--dump-outputs: the last timed solve's theta, objective trace and iteration count as float64
+    .npy files; --steps sets the number of timed steps; --full is accepted on one GPU. theta is the
+    consensus solution: every worker's row within the 1e-8-gap neighbourhood of the stacked
+    least-squares solution, and the trace ends at the stop rule's gap."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--full", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["iterations_to_tol"] == 1373
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["iterations.npy", "objective_trace.npy", "theta.npy"]
+    arr = {f[:-4]: np.load(tmp_path / "dump" / f) for f in files}
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in arr.values())
+    assert arr["iterations"].tolist() == [1373.0]
+    assert arr["theta"].shape == (24, 50) and arr["objective_trace"].shape == (1373,)
+    from gadmm_amd.benchmarks import headline_rank_problem
+    obj0 = headline_rank_problem(24, 0, 1)[4]  # the bench's own stop target
+    assert abs(arr["objective_trace"][-1] - obj0) < 1e-8 <= abs(arr["objective_trace"][-2] - obj0)
+    # every worker's Hessian X_n^T X_n is >= I (X_n = 1.3^(n-1) q q^T + I), so a 1e-8 objective gap
+    # bounds a worker's distance to the optimum by sqrt(2e-8) ~ 1.42e-4
+    Xf, yf = lin24.stacked()
+    x_star = np.linalg.lstsq(Xf.numpy(), yf.numpy(), rcond=None)[0]
+    assert float(np.max(np.abs(arr["theta"] - x_star[None]))) < 1.5e-4
+
+
 def test_graft_smoke():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
