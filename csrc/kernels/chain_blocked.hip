@@ -77,7 +77,8 @@ __device__ __forceinline__ void quad_load_image(double (&m)[4][QT], const double
 
 // Stages a launch's epoch tables for chain position q into this wave's LDS rows (DYN); the wave's
 // own later LDS reads are ordered after these stores (in-order LDS within a wave).
-__device__ __forceinline__ void stage_epochs(const PersistArgs& a, int q, const EpochLds& el, bool flush) {
+template <class PA>
+__device__ __forceinline__ void stage_epochs(const PA& a, int q, const EpochLds& el, bool flush) {
   const int lane = threadIdx.x & 63;
   for (int e = lane; e < a.n_epochs; e += 64) {
     el.sl[e] = reinterpret_cast<const int4*>(a.ep_slots)[(long)e * a.n + q];
@@ -91,8 +92,8 @@ __device__ __forceinline__ void stage_epochs(const PersistArgs& a, int q, const 
 
 // ---- monitor workgroup (same protocol as chain_persistent): sums f_n in worker order, records the
 // trace and posts the stop decision of every iteration to every rank's decision ring
-template <bool SYS, bool TL>
-__device__ __forceinline__ void blocked_monitor(const PersistArgs& a, double* lds, int v, int lane,
+template <bool SYS, bool TL, class PA>
+__device__ __forceinline__ void blocked_monitor(const PA& a, double* lds, int v, int lane,
                                                 unsigned long long deadline, __amdgpu_buffer_rsrc_t rob, int bid) {
   const int n = a.n;
   if (v != 0) return;
@@ -146,8 +147,8 @@ __device__ __forceinline__ void blocked_monitor(const PersistArgs& a, double* ld
 
 // ---- objective workgroup: wave v evaluates f_q(theta_q^it) of owned chain position q (A_q in VGPRs,
 // quad layout) off the critical path and posts it to the monitor ring
-template <int QT, bool SYS, bool DYN = false>
-__device__ __forceinline__ void blocked_objective(const PersistArgs& a, double* lds, int v, int lane, int q,
+template <int QT, bool SYS, bool DYN = false, class PA = PersistArgs>
+__device__ __forceinline__ void blocked_objective(const PA& a, double* lds, int v, int lane, int q,
                                                   unsigned long long deadline, __amdgpu_buffer_rsrc_t rob,
                                                   __amdgpu_buffer_rsrc_t rtab, bool local = false) {
   const int d = a.d, n = a.n;
@@ -222,8 +223,13 @@ __device__ __forceinline__ void blocked_objective(const PersistArgs& a, double* 
 // dynamic_group_ADMM_closedForm.m:153-168). The regular halo schedule restarts after the switch.
 // HALO (SYS only): the data-local halo mode (PersistArgs::dl_halo, one workgroup per segment: no
 // intra-rank exchange is compiled in).
-template <int DB, bool SYS, bool TL, bool DYN = false, bool HALO = false>
-__global__ void __launch_bounds__(64 * MAXW) chain_blocked_kernel(PersistArgs a) {
+// SWEEP: the body runs as one slot of chain_blocked_sweep_kernel (below): always 8-strided, this
+// slot's blocks are blockIdx.x >> 3, and a block past the slot's own W + Wo + 1 leaves before the
+// placement check (slots of one launch may have different block counts).
+// PA: PersistArgs (the kernel's own argument) or SweepArgs (a slot's entry, read through the constant
+// address space: wave-uniform scalar loads, like the kernarg segment).
+template <int DB, bool SYS, bool TL, bool DYN, bool HALO, bool SWEEP, class PA>
+__device__ __forceinline__ void chain_blocked_body(const PA& a) {
   constexpr int QT = DB / 4;  // quad layout: columns per lane
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int abort_lds, stop_lds, stop_iter_lds;
@@ -242,9 +248,10 @@ __global__ void __launch_bounds__(64 * MAXW) chain_blocked_kernel(PersistArgs a)
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const __amdgpu_buffer_rsrc_t rtab = rsrc_of(a.blk_tab);
-  const bool packed = !SYS && a.xcd > 0;  // XCD packing (PersistArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
+  const bool packed = SWEEP || (!SYS && a.xcd > 0);  // XCD packing (PersistArgs::xcd)
+  if (!SWEEP && packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
   const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  if (SWEEP && bid > W + Wo) return;  // a wider slot's block: not one of this slot's W + Wo + 1 posters
   if (threadIdx.x == 0) {
     abort_lds = 0;
     stop_lds = 0;
@@ -765,6 +772,28 @@ __global__ void __launch_bounds__(64 * MAXW) chain_blocked_kernel(PersistArgs a)
   }
 }
 
+// A sweep slot's PersistArgs: written by the host before the launch and never by a kernel, so it is
+// read like kernel arguments, through the constant address space.
+typedef __attribute__((address_space(4))) PersistArgs SweepArgs;
+
+template <int DB, bool SYS, bool TL, bool DYN = false, bool HALO = false>
+__global__ void __launch_bounds__(64 * MAXW) chain_blocked_kernel(PersistArgs a) {
+  chain_blocked_body<DB, SYS, TL, DYN, HALO, false>(a);
+}
+
+// Up to 8 independent static-chain solves in one launch, one per XCD: slot j = blockIdx.x & 7 runs
+// solve j on the blocks b % 8 == j, i.e. on the blocks that the single-solve launch leaves as exiting
+// spacers. batch[j] is solve j's own PersistArgs (its own ctl, trace, tstamp, granule tables, xchk,
+// tag salt and deadline; only the read-only inputs may be shared), read through a uniform index.
+// Nothing assumes WHICH XCD a slot gets: with xcd = 2 a slot verifies that its own blocks share one
+// (xcd_verdict on its own xchk) before it publishes with plain stores, else it uses sc1 stores.
+template <int DB>
+__global__ void __launch_bounds__(64 * MAXW) chain_blocked_sweep_kernel(const PersistArgs* __restrict__ batch, int nb) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  chain_blocked_body<DB, false, false, false, false, true>(*(const SweepArgs*)(batch + j));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Paired-wave variant (PW = 2, opt-in: GADMM_BLOCK_PW=2): a workgroup of PWW = 8 waves computes up to 16 chain positions, wave
 // v the adjacent pair (2v, 2v + 1) = one head + one tail, with BOTH rows of (A + deg rho I)^{-1} in
@@ -1273,6 +1302,112 @@ int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
   ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   void* kargs[] = {&ka};
   GADMM_CHECK(hipLaunchKernel(fn, dim3(grid), dim3(64 * MAXW), kargs, (size_t)lds, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Solves one launch of chain_blocked_sweep_kernel can run side by side (one per XCD).
+int gadmm_chain_blocked_sweep_capacity() { return 8; }
+
+// nb <= 8 independent static-chain solves (one GPU each, 12-wave layout, one DB class) in ONE launch,
+// solve j on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its
+// own ctl, trace, theta, mu, granule tables and xchk (per-XCD L2s are not coherent: two slots never
+// write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each, owned by the caller and
+// left alone until the stream has drained; the entries go up in one async copy ahead of the kernel.
+// -1: refused before any HIP call; -2: the workgroups cannot all be resident (as the single launch).
+int gadmm_chain_blocked_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, PersistArgs* dev_stage,
+                                     hipStream_t st) {
+  if (nb < 1 || nb > gadmm_chain_blocked_sweep_capacity()) {
+    gadmm_set_error("blocked sweep: %d solves, one launch takes 1..%d", nb, gadmm_chain_blocked_sweep_capacity());
+    return -1;
+  }
+  if (!batch || !host_stage || !dev_stage) {
+    gadmm_set_error("blocked sweep: null batch or staging buffer");
+    return -1;
+  }
+  int blocks[8], max_blocks = 0, sum_blocks = 0;
+  long lds = gadmm_chain_blocked_lds(0, 0);
+  for (int j = 1; j < nb; ++j)
+    if ((batch[j].d <= 32) != (batch[0].d <= 32)) {
+      gadmm_set_error("blocked sweep: solves of different register classes (d = %d and %d; d <= 32 or 33..52)",
+                      batch[0].d, batch[j].d);
+      return -1;
+    }
+  for (int j = 0; j < nb; ++j) {
+    const PersistArgs& a = batch[j];
+    if (a.nranks > 1 || a.sys_scope || a.n_epochs > 0 || a.blk_pw == 2 || a.timeline || a.blk_dl || a.dl_halo ||
+        a.blk_npeer != 0 || a.hard_stop != 0 || a.cont) {
+      gadmm_set_error("blocked sweep: solve %d is multi-rank, system-scope, dynamic, paired-wave, instrumented or "
+                      "data-local (one-GPU static 12-wave solves only)", j);
+      return -1;
+    }
+    if (!a.xchk) {
+      gadmm_set_error("blocked sweep: solve %d has no placement-check buffer (xchk)", j);
+      return -1;
+    }
+    if (a.blk_k < 1 || a.blk_len < 1 || a.blk_len + 4 * a.blk_k > MAXW || a.d < 1 || a.d > 52 || a.n < 2 ||
+        !a.blk_tab || !a.dec_push || !a.objg || !a.decg || !a.ctl || !a.trace || !a.theta || !a.mu || !a.slots ||
+        !a.Minv || !a.A || !a.b || !a.yy || !a.has_monitor || a.n != a.n_local) {
+      gadmm_set_error("blocked sweep: solve %d: unsupported configuration", j);
+      return -1;
+    }
+    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+      gadmm_set_error("blocked sweep: solve %d: ring/lag/tag range", j);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i) {
+      const PersistArgs& o = batch[i];
+      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.blk_tab == a.blk_tab ||
+          o.objg == a.objg || o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp)) {
+        gadmm_set_error("blocked sweep: solves %d and %d share a buffer that both write", i, j);
+        return -1;
+      }
+    }
+    const int W = (a.n + a.blk_len - 1) / a.blk_len, Wo = (a.n + MAXW - 1) / MAXW;
+    blocks[j] = W + Wo + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("blocked sweep: solve %d has %d workgroups, the placement check holds %d", j, blocks[j], XCHK);
+      return -1;
+    }
+    sum_blocks += blocks[j];
+    if (blocks[j] > max_blocks) max_blocks = blocks[j];
+    if (lds < (long)a.n * 8) lds = (long)a.n * 8;
+  }
+  if (lds > 160 * 1024) {
+    gadmm_set_error("blocked sweep: %ld B of LDS", lds);
+    return -1;
+  }
+  const void* fn = batch[0].d <= 32 ? (const void*)chain_blocked_sweep_kernel<32> : (const void*)chain_blocked_sweep_kernel<52>;
+  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
+  // its 8-strided blocks are dealt to
+  const long cap = gadmm_resident_capacity(fn, 64 * MAXW, (size_t)lds);
+  const long cus_xcd = gadmm_cu_count() / 8;
+  if (sum_blocks > cap) {
+    gadmm_set_error("blocked sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
+    return -2;
+  }
+  for (int j = 0; j < nb; ++j)
+    if (blocks[j] > cus_xcd) {
+      gadmm_set_error("blocked sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
+      return -2;
+    }
+  if (lds > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int dbg = 0, xenv = -1;
+  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
+  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
+  for (int j = 0; j < nb; ++j) {
+    PersistArgs& ka = host_stage[j];
+    ka = batch[j];
+    ka.dbg = dbg;
+    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
+    const int x = xenv >= 0 ? xenv : ka.xcd;
+    ka.xcd = x >= 2 ? 2 : 1;
+    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
+  const PersistArgs* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb};
+  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64 * MAXW), kargs, (size_t)lds, st));
   GADMM_CHECK(hipGetLastError());
   return 0;
 }

@@ -105,6 +105,134 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
                              check_exchange, failures)
 
 
+def sweep_groups(n: int, width: int) -> List[List[int]]:
+    """Indices 0..n-1 in consecutive groups of at most ``width`` (one group per sweep launch)."""
+    if width < 1:
+        raise ValueError("sweep width must be >= 1")
+    return [list(range(i, min(i + width, n))) for i in range(0, n, width)]
+
+
+def run_in_groups(items: Sequence, width: int, run_group) -> list:
+    """``run_group(group_items, group_indices)`` per ``sweep_groups`` group; the results in input order."""
+    out = [None] * len(items)
+    for g in sweep_groups(len(items), width):
+        res = run_group([items[i] for i in g], g)
+        if len(res) != len(g):
+            raise RuntimeError("a sweep group of %d returned %d results" % (len(g), len(res)))
+        for i, r in zip(g, res):
+            out[i] = r
+    return out
+
+
+def chain_admm_sweep(model, local_ids: Sequence[int], n_total: int, rhos: Sequence[float], obj0: float, tol: float,
+                     max_iter: int, *, tols: Optional[Sequence[float]] = None, placement: Optional[Placement] = None,
+                     backend: str = "auto", name: str = "GADMM", engine_opts: Optional[dict] = None,
+                     comm: Optional[Comm] = None) -> List[RunResult]:
+    """The static-chain closed-form GADMM solve at every rho of ``rhos``: one ``RunResult`` per rho, in
+    the order given, equal to ``[chain_admm(model, ..., rho, ...) for rho in rhos]``. On one HIP device
+    the solves run side by side, up to eight per kernel launch, one per XCD
+    (engine/chain_sweep.py; more values run in groups), each to its own stop: ``tols`` gives one
+    tolerance per rho (default ``tol`` for all). Each result then carries ``extra['sweep'] = {width,
+    slot, kernel, placed, wall_ms_launch}`` and its ``wall_s`` is that solve's OWN time: the wall
+    clock of its launch (set-up, launch, read-back) less the device time between its stop decision and
+    the last member's, so the slowest member's equals the launch's; ``time_trace`` is each curve's own
+    device clock. ``extra['state']`` is not produced (a caller that checkpoints runs ``chain_admm``).
+    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, a shape the sweep kernel does not
+    take, or a device that cannot hold the group's workgroups -- it IS that loop, and every result
+    records ``extra['sweep_fallback'] = reason``. ``engine_opts``: ``refresh`` (recompute Gram +
+    inverses from the raw shards first), ``residual``, ``cache``, as in ``chain_admm``."""
+    rhos = [float(r) for r in rhos]
+    opts = dict(engine_opts or {})
+    tols = [float(tol)] * len(rhos) if tols is None else [float(t) for t in tols]
+    if len(tols) != len(rhos):
+        raise ValueError("tols: one per rho")
+    nranks = comm.nranks if comm is not None else 1
+
+    def sequential(reason: str) -> List[RunResult]:
+        out = []
+        for rho, t in zip(rhos, tols):
+            r = chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
+                           backend=backend, name=name, engine_opts=engine_opts)
+            r.extra["sweep_fallback"] = reason
+            out.append(r)
+        return out
+
+    if not rhos:
+        return []
+    if model.device.type != "cuda":
+        return sequential("cpu tensors")
+    if backend == "torch":
+        return sequential("torch backend")
+    if nranks > 1:
+        return sequential("several ranks")
+    if model.kind != "linear" or sorted(int(w) for w in local_ids) != list(range(n_total)):
+        return sequential("not a one-GPU linear closed-form chain")
+    if getenv("GADMM_CHECK_EXCHANGE", "0") == "1":
+        return sequential("exchange checker")
+    from ..ops import native
+    if not native.available():
+        return sequential("native library unavailable")
+    from ..engine.chain_engine import ResidencyError
+    from ..engine.chain_sweep import ChainSweepEngine, sweep_capacity
+
+    refresh = bool(opts.get("refresh", False))
+    residual = bool(opts.get("residual", True))
+
+    def run_group(g_rhos, idx):
+        t_begin = time.perf_counter()
+        g_tols = [tols[i] for i in idx]
+        key = ("sweep", n_total, tuple(map(int, local_ids)), tuple(g_rhos), int(max_iter), residual)
+        cache = getattr(model, "_chain_engines", None)
+        sw = cache.get(key) if cache is not None else None
+        if sw is None:
+            if refresh:
+                from ..ops.linalg import gram
+                gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
+            sw = ChainSweepEngine.rho_sweep(model.X, model.y, local_ids, n_total, g_rhos, obj0=obj0, tols=g_tols,
+                                            max_iters=max_iter, precomputed=(model.A, model.b, model.yy),
+                                            placement=placement, residual=residual)
+            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
+            if opts.get("cache", True):
+                if cache is None:
+                    cache = {}
+                    model._chain_engines = cache
+                cache[key] = sw
+        else:
+            sw.set_targets(obj0, g_tols)
+            if refresh:
+                sw.refresh(model.X, model.y)
+        runs = sw.run()
+        wall = time.perf_counter() - t_begin
+        ticks = sw.stop_ticks(runs)
+        last = max(ticks)
+        out = []
+        for j, (m, r, rho) in enumerate(zip(sw.members, runs, g_rhos)):
+            iters, done = int(r.iters), int(r.done)
+            tr, tt = m.traces(iters)
+            own = wall - (last - ticks[j]) * 1e-8 if ticks[j] > 0 else wall
+            res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(done == 1),
+                            wall_s=own, time_trace=tt,
+                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
+                            com_cost=np.arange(1, iters + 1) * 0.0, bytes_sent=0, bytes_total=0,
+                            primal_res=m.primal_residual(iters),
+                            extra={"backend": "native", "engine": "persistent", "rank": 0, "nranks": 1,
+                                   "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0, "transport": "local",
+                                   "obj_mode": m.obj_mode_name, "engine_obj": m,
+                                   "sweep": {"width": len(g_rhos), "slot": j, "kernel": sw.last_kernel,
+                                             "placed": int(sw.last_placed[j]), "wall_ms_launch": sw.last_wall_ms},
+                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j})
+            out.append(res)
+        return out
+
+    try:
+        with roctx_range("%s sweep native N=%d K=%d" % (name, n_total, len(rhos))):
+            return run_in_groups(rhos, sweep_capacity(), run_group)
+    except ResidencyError as e:
+        return sequential("ResidencyError: %s" % e)
+    except ValueError as e:  # a shape the sweep kernel does not take (d > 52, no blocked plan, ...)
+        return sequential("not eligible: %s" % e)
+
+
 def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
                       local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
                       check_exchange=False, failures=None):

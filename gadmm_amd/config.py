@@ -42,8 +42,14 @@ class ExperimentConfig:
     path_seed: int = 1234
     data_dir: Optional[str] = None  # directory with data.txt / y.txt (reference UCI layout)
     reference: str = ""             # reference script this preset mirrors
+    # the rho sweep of the linear closed-form entries: 'sequential' = one solve after the other,
+    # 'concurrent' = up to eight rho values side by side in one kernel launch, one per XCD (one GPU;
+    # algorithms.chain_admm_sweep)
+    sweep: str = "sequential"
 
     def override(self, **kw) -> "ExperimentConfig":
+        if kw.get("sweep", "sequential") not in ("sequential", "concurrent"):
+            raise ValueError("sweep must be 'sequential' or 'concurrent', not %r" % kw["sweep"])
         return dataclasses.replace(self, **kw)
 
     def quick(self) -> "ExperimentConfig":

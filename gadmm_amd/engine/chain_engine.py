@@ -137,7 +137,7 @@ class NativeChainEngine:
                  max_iter: int = 1000, lam: float = 0.0, step: float = 0.0, max_inner: int = 100,
                  inner_tol: float = 1e-4, comm=None, block: int = 16, stream: Optional[torch.cuda.Stream] = None,
                  precomputed=None, force_monitor: bool = False, obj_mode: str = "auto", local_solver: str = "gd",
-                 chord: Optional[float] = None, residual: bool = False, xcd: int = 2):
+                 chord: Optional[float] = None, residual: bool = False, xcd: int = 2, inverses=None):
         """``local_solver`` (logistic): "gd" = the reference's inexact inner GD (logReg_GD.m, step /
         max_inner / inner_tol), "newton" = exact local solves (group_ADMM_logistic.m semantics,
         csrc/kernels/chain_newton.hip; d, m <= 64). ``chord`` (newton): a worker reuses its last
@@ -153,7 +153,10 @@ class NativeChainEngine:
         ||theta_n - theta_right||^2) per iteration, read back by ``primal_residual``. ``xcd`` (one GPU,
         persistent kernels): 0 default grid, 1 deal every working workgroup onto one XCD, 2 also
         publish with L2-resident plain stores once the kernel has verified that placement
-        (PersistArgs::xcd; speed only, results are bit-identical)."""
+        (PersistArgs::xcd; speed only, results are bit-identical). ``inverses`` (linear, with
+        ``precomputed``): ``(Minv (N, nvar, d, d), nvar, deg_to_var)`` -- the engine reads its cached
+        inverses out of a table it shares with other engines (engine/chain_sweep.py builds one table for
+        a whole rho sweep in one launch) and leaves ``refresh`` / ``set_rho`` to the table's owner."""
         if not X_loc.is_cuda:
             raise ValueError("NativeChainEngine runs on a HIP device; use the torch algorithms on CPU")
         # the kernels read raw f64 pointers: anything else (e.g. float32 labels from torch.where) would be
@@ -237,7 +240,12 @@ class NativeChainEngine:
                     self.A, self.b, self.yy = precomputed
                 else:
                     self.A, self.b, self.yy = gram(X_loc, y_loc)
-                self._build_inverses()
+                self._shared_inverses = inverses is not None
+                if inverses is not None:
+                    self.Minv, self.nvar, self.deg_to_var = inverses[0], int(inverses[1]), tuple(inverses[2])
+                    self._minv_version = 1
+                else:
+                    self._build_inverses()
             elif model == "logistic":
                 self.X = X_loc.contiguous()
                 self.Y = y_loc.contiguous()
@@ -340,6 +348,8 @@ class NativeChainEngine:
         arguments built once (the general path's torch stream context, workspace allocation and
         argument checks were ~20 us of host time per solve, on the critical path of a 1 ms D-GADMM
         solve). Same kernels, same arguments: bit-identical."""
+        if getattr(self, "_shared_inverses", False):
+            raise RuntimeError("this engine's inverses belong to a shared table: refresh its owner")
         fast = getattr(self, "_refresh_fast", None)
         if fast is not None and fast[0] is X_loc and fast[1] is y_loc:
             lib, g_args, i_args = fast[2], fast[3], fast[4]
@@ -380,6 +390,8 @@ class NativeChainEngine:
 
     def set_rho(self, rho: float):
         """Change rho (re-inverts; the Gram is kept)."""
+        if getattr(self, "_shared_inverses", False):
+            raise RuntimeError("this engine's inverses belong to a shared table: rho is fixed")
         self.rho = float(rho)
         if self.model == "linear":
             with torch.cuda.stream(self.stream):
@@ -628,6 +640,187 @@ class NativeChainEngine:
             memo[key] = (kk.value, ll.value, W, pp.value) if W > 0 else None
         return memo[key]
 
+    def _persist_args(self, lag, ring, timeout_s, start_iter, pending_in, fabric, dynamic, hard_stop, cont):
+        """``(PersistArgs, slots, positions, keep)`` of one persistent launch: the slot / granule buffers
+        (allocated and zeroed on the engine stream, memoised per layout), a fresh tag salt and the
+        launch-invariant fields. ``dynamic``: a D-GADMM launch (epoch tables follow in the caller)."""
+        dev = self.device
+        # this rank's slots in chain order, their positions and the buffer key: memoised per plan
+        pk = (id(self.plan), tuple(self.path))
+        memo = getattr(self, "_slot_memo", None)
+        if memo is None or memo[0] != pk:
+            pos_of = {g: i for i, g in enumerate(self.path)}
+            sl = sorted(self.plan.head + self.plan.tail, key=lambda s: pos_of[s.gid])
+            memo = (pk, sl, [pos_of[s.gid] for s in sl], tuple((s.li, s.gid, s.left, s.right) for s in sl), self.plan)
+            self._slot_memo = memo
+        _, slots, pos, slot_key, _ = memo
+        key = (ring, slot_key, id(fabric), dynamic)
+        if getattr(self, "_pbuf", None) is None or self._pbuf[0] != key:
+            with torch.cuda.stream(self.stream):
+                slot_t = torch.tensor([[s.li, s.gid, s.left, s.right] for s in slots], dtype=torch.int32,
+                                      device=dev).reshape(-1)
+                pos_t = torch.tensor(pos, dtype=torch.int32, device=dev)
+                if fabric is None:
+                    # D-GADMM (epochs): one theta slot per ring iteration (see chain_persistent.hip)
+                    thg = torch.zeros(((ring if dynamic else 1) * self.n_total * self.d * 4,),
+                                      dtype=torch.int32, device=dev)
+                    objg = torch.zeros((ring * self.n_total * 4,), dtype=torch.int32, device=dev)
+                    decg = torch.zeros((ring,), dtype=torch.int64, device=dev)
+                    ptrs = (thg.data_ptr(), objg.data_ptr(), decg.data_ptr())
+                    push = None
+                    dec_push = torch.tensor([decg.data_ptr()], dtype=torch.int64, device=dev)
+                    keep = (thg, objg, decg)
+                elif dynamic:
+                    # D-GADMM across GPUs: push targets change per epoch (ep_push masks below)
+                    if getattr(fabric, "table_slots", 1) < ring:
+                        raise RuntimeError("fabric theta tables hold %d slots, D-GADMM needs %d"
+                                           % (getattr(fabric, "table_slots", 1), ring))
+                    push = None
+                else:
+                    owner = self._placement_owner
+                    pl = []
+                    for s in slots:
+                        peers = sorted({int(owner[u]) for u in (s.left, s.right) if u >= 0} - {self.rank})
+                        ps = [fabric.thg_peer[r] for r in peers] + [0, 0]
+                        pl += ps[:2]
+                    push = torch.tensor(pl, dtype=torch.int64, device=dev)
+                if fabric is not None:
+                    ptrs = (fabric.thg.ptr.value, fabric.objg_mon, fabric.decg.ptr.value)
+                    dec_push = torch.tensor(fabric.dec_all if fabric.dec_all else [0], dtype=torch.int64,
+                                            device=dev)
+                    keep = (torch.tensor(fabric.table_ptrs(), dtype=torch.int64, device=dev),) \
+                        if dynamic else ()
+            self._pbuf = (key, slot_t, pos_t, ptrs, push, dec_push, keep, [0])
+        _, slot_t, pos_t, ptrs, push, dec_push, keep, epoch_box = self._pbuf
+        if cont:  # same salt: the tables still hold theta^{start_iter - 1} of the previous chunk
+            epoch = self._salt
+            native.check(self.lib.gadmm_chain_engine_reset(self.handle, int(start_iter), int(pending_in)), "reset")
+        elif fabric is not None:
+            epoch = fabric.next_epoch()
+        else:
+            epoch_box[0] = epoch_box[0] % 4095 + 1
+            epoch = epoch_box[0]
+        self._salt = epoch
+        if fabric is None and getattr(self, "_xchk", None) is None:  # XCD packing (one GPU): PersistArgs::xcd
+            # zeroed on the engine stream, ordered before the kernel: a fill on torch's current stream
+            # could land while the blocks post their placement granules (they then spin to the deadline)
+            with torch.cuda.stream(self.stream):
+                self._xchk = torch.zeros((256 * 4,), dtype=torch.int32, device=dev)
+        # the launch-invariant fields, set once per (buffers, targets, layout) and copied per launch (a
+        # D-GADMM solve launches every ~1 ms: ~40 ctypes field stores were ~3 us of its host path). The
+        # buffers are held by the key itself, compared by identity, so a freed one cannot alias a new one
+        objs = (self._pbuf, self.Minv, self.A, self.b, self.yy, self.theta, self.mu, self.trace, self.ctl,
+                self.tstamp, self.rres, fabric, getattr(self, "_xchk", None))
+        nums = (int(lag), ring, self.rho, self.obj0, self.tol, float(timeout_s), dynamic, self.rank,
+                self.nranks, int(self.xcd), self.nvar, tuple(self.deg_to_var), self.max_iter, len(slots))
+        tmpl = self.__dict__.get("_pa_tmpl")
+        if tmpl is None or tmpl[1] != nums or any(x is not y for x, y in zip(tmpl[0], objs)):
+            pt = native.PersistArgs()
+            pt.d, pt.n, pt.n_local, pt.max_iter = self.d, self.n_total, len(slots), self.max_iter
+            pt.lag, pt.ring, pt.nvar, pt.obj_mode = int(lag), ring, self.nvar, self._obj_mode(dynamic)
+            for i, v in enumerate(self.deg_to_var):
+                pt.deg_to_var[i] = v
+            pt.has_monitor = 1 if (fabric is None or self.rank == 0) else 0
+            pt.nranks = 1 if fabric is None else self.nranks
+            pt.sys_scope = 0 if fabric is None else 1
+            pt.rho, pt.obj0, pt.tol = self.rho, self.obj0, self.tol
+            pt.timeout_ticks = int(timeout_s * 1e8)
+            pt.slots, pt.pos = slot_t.data_ptr(), pos_t.data_ptr()
+            pt.Minv, pt.A, pt.b, pt.yy = native.ptr(self.Minv), native.ptr(self.A), native.ptr(self.b), native.ptr(self.yy)
+            pt.theta, pt.mu = self.theta.data_ptr(), self.mu.data_ptr()
+            pt.thg, pt.objg, pt.decg = ptrs
+            pt.push = push.data_ptr() if push is not None else None
+            pt.dec_push = dec_push.data_ptr()
+            pt.trace, pt.ctl = self.trace.data_ptr(), self.ctl.data_ptr()
+            pt.tstamp = self.tstamp.data_ptr()
+            pt.rres = native.ptr(self.rres)
+            if fabric is None:
+                pt.xchk, pt.xcd = self._xchk.data_ptr(), int(self.xcd)
+            tmpl = (objs, nums, pt)
+            self._pa_tmpl = tmpl
+        pa = native.PersistArgs.from_buffer_copy(tmpl[2])
+        pa.start_iter, pa.pending_in, pa.epoch = int(start_iter), int(pending_in), int(epoch)
+        pa.hard_stop, pa.cont = int(hard_stop), 1 if cont else 0
+        return pa, slots, pos, keep
+
+    def _attach_blocked(self, pa, plan, ring, dynamic):
+        """The blocked kernel's fields of ``pa``: its plan and the halo exchange table (zeroed once, on
+        the engine stream; tags make re-zeroing between solves unnecessary)."""
+        ng = int((self.lib.gadmm_chain_blocked_tab_granules_dyn if dynamic else
+                  self.lib.gadmm_chain_blocked_tab_granules)(self.n_total, self.d, ring))
+        if getattr(self, "_blk_tab", None) is None or self._blk_tab.numel() != ng * 4:
+            with torch.cuda.stream(self.stream):  # (ordered before the kernel, as _xchk)
+                self._blk_tab = torch.zeros((ng * 4,), dtype=torch.int32, device=self.device)
+        pa.blk_k, pa.blk_len, pa.blk_pw = plan[0], plan[1], plan[3]
+        pa.blk_tab = self._blk_tab.data_ptr()
+
+    def _queue_readback(self, fetch_trace: bool) -> bool:
+        """Queue the read-back of the control block (with ``fetch_trace`` and a short trace: of the
+        whole read-back block) behind the launch on the engine stream; True if the traces come along."""
+        # the control block comes back with the same stream sync (pinned buffer, async copy queued
+        # behind the kernel): no second blocking round trip per solve
+        # the objective trace and the clock come back behind the same sync as the control block, in
+        # one copy of the read-back block (short traces: traces() then reads the pinned copy instead of
+        # a second blocking device round trip); without them, only the control block's words
+        nt = self.trace.numel()
+        fetch = fetch_trace and nt <= 16384
+        if getattr(self, "_rb_host", None) is None:
+            self._rb_host = torch.empty(self._rb.shape, dtype=torch.float64, pin_memory=True)
+            self._rb_host_np = self._rb_host.numpy()
+            self._ctl_host = self._rb_host[0:4].view(torch.int32)
+        # queued on the engine stream (every launch above names that stream explicitly, so no torch stream
+        # context is needed around this block) as a small kernel writing the pinned buffer: an SDMA copy
+        # started ~10 us after the solve kernel ended (csrc/kernels/readback.hip)
+        nb = self._rb.numel() * 8 if fetch else 32  # all of it, or the control block (8 x i32)
+        native.check(self.lib.gadmm_readback_d2h(self._rb_host.data_ptr(), self._rb.data_ptr(), nb,
+                                                 self.stream.cuda_stream), "readback")
+        return fetch
+
+    def _decode_ctl(self, what: str = "persistent chain kernel"):
+        """(done, conv_iter, next iteration) of the control block read back behind the last launch;
+        records ``last_placed``. A hand-off timeout (done == 4) raises."""
+        c = self._ctl_host.tolist()
+        done, conv, nxt = c[1], c[2], c[0]
+        self.last_placed = c[6]  # ChainCtl::placed: the XCD packing this launch got (0 / 1 / 2)
+        if done == 4:
+            raise HandoffTimeout("%s timed out (hand-off never completed)" % what)
+        return done, conv, nxt
+
+    # ---- a static blocked solve in two halves, for launches that carry several solves (chain_sweep.py)
+    def prepare_blocked(self, lag: int = 4, timeout_s: float = 20.0, start_iter: int = 1):
+        """``(PersistArgs, plan)`` of a static solve on the 12-wave blocked kernel, as ``run_persistent``
+        builds them, without launching: state must be reset by the caller. Every buffer allocation and
+        zero-fill is queued on the engine stream, so the launch must use that stream (``adopt_stream``).
+        Raises ValueError when the engine has no such plan."""
+        if self.nranks != 1 or self.n_local != self.n_total or not self.persistent_eligible(None):
+            raise ValueError("persistent kernel not eligible for this engine/config")
+        plan = self.blocked_plan(None) if self.model == "linear" else None
+        if plan is None or plan[3] != 1:
+            raise ValueError("no 12-wave blocked plan for this engine (n=%d, d=%d)" % (self.n_total, self.d))
+        lag = max(lag, 8)
+        ring = lag + 4
+        pa, _, _, _ = self._persist_args(lag, ring, timeout_s, start_iter, 0, None, False, 0, False)
+        self._attach_blocked(pa, plan, ring, False)
+        return pa, plan
+
+    def finish_blocked(self, start_iter: int, wall_ms: float, fetch: bool, what: str) -> EngineRun:
+        """The ``EngineRun`` of a static blocked solve whose read-back (``_queue_readback``) has
+        completed: decodes the control block as ``run_persistent`` does."""
+        self._tr_valid = fetch
+        self.last_timeline = self.last_timeline_slots = None
+        done, conv, nxt = self._decode_ctl(what)
+        return EngineRun(conv, done, nxt - start_iter, 1, wall_ms, 0, 0, 0, 0)
+
+    def adopt_stream(self, stream: torch.cuda.Stream):
+        """Move the engine onto ``stream`` (ordered behind everything queued on its old one): its
+        resets, refreshes and launches then share that stream with the other users of it."""
+        stream.wait_stream(self.stream)
+        self.stream = stream
+        self._desc.stream = stream.cuda_stream
+        self._refresh_fast = None  # its bound arguments name the old stream
+        self._pad_fast = None
+        self._recreate()
+
     def run_persistent(self, lag: int = 4, timeout_s: float = 20.0, start_iter: int = 1,
                        pending_in: int = 0, fabric=None, timeline_iters: int = 0,
                        epochs: Optional[Sequence] = None, hard_stop: int = 0, cont: bool = False,
@@ -672,102 +865,8 @@ class NativeChainEngine:
             lag = max(lag, 8)  # the objective takes one more hop (worker -> objective wave -> monitor)
         ring = lag + 4
         dev = self.device
-        # this rank's slots in chain order, their positions and the buffer key: memoised per plan
-        pk = (id(self.plan), tuple(self.path))
-        memo = getattr(self, "_slot_memo", None)
-        if memo is None or memo[0] != pk:
-            pos_of = {g: i for i, g in enumerate(self.path)}
-            sl = sorted(self.plan.head + self.plan.tail, key=lambda s: pos_of[s.gid])
-            memo = (pk, sl, [pos_of[s.gid] for s in sl], tuple((s.li, s.gid, s.left, s.right) for s in sl), self.plan)
-            self._slot_memo = memo
-        _, slots, pos, slot_key, _ = memo
-        key = (ring, slot_key, id(fabric), epochs is not None)
-        if getattr(self, "_pbuf", None) is None or self._pbuf[0] != key:
-            with torch.cuda.stream(self.stream):
-                slot_t = torch.tensor([[s.li, s.gid, s.left, s.right] for s in slots], dtype=torch.int32,
-                                      device=dev).reshape(-1)
-                pos_t = torch.tensor(pos, dtype=torch.int32, device=dev)
-                if fabric is None:
-                    # D-GADMM (epochs): one theta slot per ring iteration (see chain_persistent.hip)
-                    thg = torch.zeros(((ring if epochs is not None else 1) * self.n_total * self.d * 4,),
-                                      dtype=torch.int32, device=dev)
-                    objg = torch.zeros((ring * self.n_total * 4,), dtype=torch.int32, device=dev)
-                    decg = torch.zeros((ring,), dtype=torch.int64, device=dev)
-                    ptrs = (thg.data_ptr(), objg.data_ptr(), decg.data_ptr())
-                    push = None
-                    dec_push = torch.tensor([decg.data_ptr()], dtype=torch.int64, device=dev)
-                    keep = (thg, objg, decg)
-                elif epochs is not None:
-                    # D-GADMM across GPUs: push targets change per epoch (ep_push masks below)
-                    if getattr(fabric, "table_slots", 1) < ring:
-                        raise RuntimeError("fabric theta tables hold %d slots, D-GADMM needs %d"
-                                           % (getattr(fabric, "table_slots", 1), ring))
-                    push = None
-                else:
-                    owner = self._placement_owner
-                    pl = []
-                    for s in slots:
-                        peers = sorted({int(owner[u]) for u in (s.left, s.right) if u >= 0} - {self.rank})
-                        ps = [fabric.thg_peer[r] for r in peers] + [0, 0]
-                        pl += ps[:2]
-                    push = torch.tensor(pl, dtype=torch.int64, device=dev)
-                if fabric is not None:
-                    ptrs = (fabric.thg.ptr.value, fabric.objg_mon, fabric.decg.ptr.value)
-                    dec_push = torch.tensor(fabric.dec_all if fabric.dec_all else [0], dtype=torch.int64,
-                                            device=dev)
-                    keep = (torch.tensor(fabric.table_ptrs(), dtype=torch.int64, device=dev),) \
-                        if epochs is not None else ()
-            self._pbuf = (key, slot_t, pos_t, ptrs, push, dec_push, keep, [0])
-        _, slot_t, pos_t, ptrs, push, dec_push, keep, epoch_box = self._pbuf
-        if cont:  # same salt: the tables still hold theta^{start_iter - 1} of the previous chunk
-            epoch = self._salt
-            native.check(self.lib.gadmm_chain_engine_reset(self.handle, int(start_iter), int(pending_in)), "reset")
-        elif fabric is not None:
-            epoch = fabric.next_epoch()
-        else:
-            epoch_box[0] = epoch_box[0] % 4095 + 1
-            epoch = epoch_box[0]
-        self._salt = epoch
-        if fabric is None and getattr(self, "_xchk", None) is None:  # XCD packing (one GPU): PersistArgs::xcd
-            # zeroed on the engine stream, ordered before the kernel: a fill on torch's current stream
-            # could land while the blocks post their placement granules (they then spin to the deadline)
-            with torch.cuda.stream(self.stream):
-                self._xchk = torch.zeros((256 * 4,), dtype=torch.int32, device=dev)
-        # the launch-invariant fields, set once per (buffers, targets, layout) and copied per launch (a
-        # D-GADMM solve launches every ~1 ms: ~40 ctypes field stores were ~3 us of its host path). The
-        # buffers are held by the key itself, compared by identity, so a freed one cannot alias a new one
-        objs = (self._pbuf, self.Minv, self.A, self.b, self.yy, self.theta, self.mu, self.trace, self.ctl,
-                self.tstamp, self.rres, fabric, getattr(self, "_xchk", None))
-        nums = (int(lag), ring, self.rho, self.obj0, self.tol, float(timeout_s), epochs is not None, self.rank,
-                self.nranks, int(self.xcd), self.nvar, tuple(self.deg_to_var), self.max_iter, len(slots))
-        tmpl = self.__dict__.get("_pa_tmpl")
-        if tmpl is None or tmpl[1] != nums or any(x is not y for x, y in zip(tmpl[0], objs)):
-            pt = native.PersistArgs()
-            pt.d, pt.n, pt.n_local, pt.max_iter = self.d, self.n_total, len(slots), self.max_iter
-            pt.lag, pt.ring, pt.nvar, pt.obj_mode = int(lag), ring, self.nvar, self._obj_mode(epochs is not None)
-            for i, v in enumerate(self.deg_to_var):
-                pt.deg_to_var[i] = v
-            pt.has_monitor = 1 if (fabric is None or self.rank == 0) else 0
-            pt.nranks = 1 if fabric is None else self.nranks
-            pt.sys_scope = 0 if fabric is None else 1
-            pt.rho, pt.obj0, pt.tol = self.rho, self.obj0, self.tol
-            pt.timeout_ticks = int(timeout_s * 1e8)
-            pt.slots, pt.pos = slot_t.data_ptr(), pos_t.data_ptr()
-            pt.Minv, pt.A, pt.b, pt.yy = native.ptr(self.Minv), native.ptr(self.A), native.ptr(self.b), native.ptr(self.yy)
-            pt.theta, pt.mu = self.theta.data_ptr(), self.mu.data_ptr()
-            pt.thg, pt.objg, pt.decg = ptrs
-            pt.push = push.data_ptr() if push is not None else None
-            pt.dec_push = dec_push.data_ptr()
-            pt.trace, pt.ctl = self.trace.data_ptr(), self.ctl.data_ptr()
-            pt.tstamp = self.tstamp.data_ptr()
-            pt.rres = native.ptr(self.rres)
-            if fabric is None:
-                pt.xchk, pt.xcd = self._xchk.data_ptr(), int(self.xcd)
-            tmpl = (objs, nums, pt)
-            self._pa_tmpl = tmpl
-        pa = native.PersistArgs.from_buffer_copy(tmpl[2])
-        pa.start_iter, pa.pending_in, pa.epoch = int(start_iter), int(pending_in), int(epoch)
-        pa.hard_stop, pa.cont = int(hard_stop), 1 if cont else 0
+        pa, slots, pos, keep = self._persist_args(lag, ring, timeout_s, start_iter, pending_in, fabric,
+                                                  epochs is not None, hard_stop, cont)
         _timing.host_stamp("rp:args")
         fused = epochs is not None and plan is not None and fabric is None and isinstance(epochs, tuple) \
             and len(epochs) == 2 and isinstance(epochs[1], np.ndarray) and isinstance(epochs[0], np.ndarray) \
@@ -877,13 +976,7 @@ class NativeChainEngine:
             pa.timeline, pa.timeline_iters = tl.data_ptr(), int(timeline_iters)
         import time as _time
         if plan is not None:  # temporally blocked kernel: one halo hand-off per k iterations
-            ng = int((self.lib.gadmm_chain_blocked_tab_granules_dyn if epochs is not None else
-                      self.lib.gadmm_chain_blocked_tab_granules)(self.n_total, self.d, ring))
-            if getattr(self, "_blk_tab", None) is None or self._blk_tab.numel() != ng * 4:
-                with torch.cuda.stream(self.stream):  # (ordered before the kernel, as _xchk)
-                    self._blk_tab = torch.zeros((ng * 4,), dtype=torch.int32, device=dev)
-            pa.blk_k, pa.blk_len, pa.blk_pw = plan[0], plan[1], plan[3]
-            pa.blk_tab = self._blk_tab.data_ptr()
+            self._attach_blocked(pa, plan, ring, epochs is not None)
             if epochs is not None:
                 # D-GADMM in the blocked kernel: every inverse as a lane-major image of the kernel's quad
                 # register layout (quad_pad_image), reloaded by a re-chain with coalesced unmasked loads
@@ -940,23 +1033,7 @@ class NativeChainEngine:
             if rc == -2:
                 raise ResidencyError(self.lib.gadmm_last_error().decode())
             native.check(rc, "chain_persistent_launch")
-        # the control block comes back with the same stream sync (pinned buffer, async copy queued
-        # behind the kernel): no second blocking round trip per solve
-        # the objective trace and the clock come back behind the same sync as the control block, in
-        # one copy of the read-back block (short traces: traces() then reads the pinned copy instead of
-        # a second blocking device round trip); without them, only the control block's words
-        nt = self.trace.numel()
-        fetch = fetch_trace and nt <= 16384
-        if getattr(self, "_rb_host", None) is None:
-            self._rb_host = torch.empty(self._rb.shape, dtype=torch.float64, pin_memory=True)
-            self._rb_host_np = self._rb_host.numpy()
-            self._ctl_host = self._rb_host[0:4].view(torch.int32)
-        # queued on the engine stream (every launch above names that stream explicitly, so no torch stream
-        # context is needed around this block) as a small kernel writing the pinned buffer: an SDMA copy
-        # started ~10 us after the solve kernel ended (csrc/kernels/readback.hip)
-        nb = self._rb.numel() * 8 if fetch else 32  # all of it, or the control block (8 x i32)
-        native.check(self.lib.gadmm_readback_d2h(self._rb_host.data_ptr(), self._rb.data_ptr(), nb,
-                                                 self.stream.cuda_stream), "readback")
+        fetch = self._queue_readback(fetch_trace)
         _timing.host_stamp("rp:copies_queued")
         if on_enqueued is not None:
             on_enqueued()
@@ -967,11 +1044,7 @@ class NativeChainEngine:
         t1 = _time.perf_counter()
         self.last_timeline = tl.cpu().numpy() if tl is not None else None
         self.last_timeline_slots = [(s.gid, p) for s, p in zip(slots, pos)] if tl is not None else None
-        c = self._ctl_host.tolist()
-        done, conv, nxt = c[1], c[2], c[0]
-        self.last_placed = c[6]  # ChainCtl::placed: the XCD packing this launch got (0 / 1 / 2)
-        if done == 4:
-            raise HandoffTimeout("persistent chain kernel timed out (hand-off never completed)")
+        done, conv, nxt = self._decode_ctl()
         # a chunk that ran to its hard stop: count iterations start..hard_stop (only the monitor rank
         # knows the outcome; callers agree on it across ranks)
         last = conv if done in (1, 2, 3) else (int(hard_stop) if hard_stop > 0 else conv)

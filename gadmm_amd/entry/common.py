@@ -310,12 +310,26 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
                 ) -> Dict[str, object]:
     """The reference's rho sweep (LinearRegression_Synthetic.m:78-94, LogisticRegression_Synthetic.m:88-100):
     one GADMM solve per rho on its engine (``gadmm_solve``); ``state_rho``: that run keeps its state for
-    a checkpoint."""
+    a checkpoint. With the preset field ``sweep='concurrent'`` the linear closed-form rho list runs
+    side by side in one kernel launch (``chain_admm_sweep``) on a one-GPU session, unless the backend
+    is torch or a run must keep its state; each run's summary then names the sweep kernel and its slot."""
     from ..utils.timing import roctx_range
 
     cfg = prob.cfg
     out = {}
-    for rho in cfg.rhos:
+    concurrent = (cfg.sweep == "concurrent" and cfg.model == "linear" and sess.world == 1
+                  and sess.device.type == "cuda" and backend != "torch" and state_rho is None and len(cfg.rhos) > 0)
+    if concurrent:
+        from ..algorithms import chain_admm_sweep
+
+        with roctx_range("gadmm_sweep concurrent"):
+            rs = chain_admm_sweep(prob.model, prob.local_ids, prob.n_total, list(cfg.rhos), prob.obj0, cfg.acc,
+                                  cfg.gadmm_iters, placement=prob.placement, backend=backend, comm=sess.comm)
+        for rho, r in zip(cfg.rhos, rs):
+            r.algorithm = "GADMM(rho=%g)" % rho
+            r.extra.pop("engine_obj", None)  # (the summary carries sweep_kernel / sweep_slot of each run)
+            out["GADMM_rho%g" % rho] = attach_modelled_clock(r, prob.model, rho, sess)
+    for rho in ([] if concurrent else cfg.rhos):
         with roctx_range("gadmm_sweep rho=%g" % rho):
             r = gadmm_solve(prob, sess, rho, cfg.acc, cfg.gadmm_iters, backend, name="GADMM(rho=%g)" % rho,
                             need_state=(state_rho is not None and rho == state_rho))
