@@ -794,6 +794,25 @@ __global__ void __launch_bounds__(64 * MAXW) chain_blocked_sweep_kernel(const Pe
   chain_blocked_body<DB, false, false, false, false, true>(*(const SweepArgs*)(batch + j));
 }
 
+// The same for D-GADMM: slot j runs one epoch chunk of dynamic solve j (DYN + SWEEP). Per slot, as in
+// the single dynamic launch: its own epoch tables (staged into the LDS of its own workgroups only,
+// after the early exit of a wider slot's blocks, so no barrier or staging ever runs in a block that
+// leaves), its own xchk / xtag, and its own ctl for the stop and hard-stop outcomes of the worker,
+// objective and monitor waves. A member's chunks may land on different XCDs from launch to launch.
+// Its cross-chunk state is (theta, mu, ctl), written with plain stores and made visible by the kernel
+// boundary (release at the end of a launch, acquire at the start of the next one), and the granule
+// tables, whose readers match tags: every granule this kernel waits for carries an iteration >=
+// start_iter, i.e. is stored by the same launch (the first iteration of a continuation takes its
+// neighbours' theta from a.theta, and the previous chunk's granules, same salt, older iterations,
+// never match), and whether those stores may stay in an XCD's L2 is decided anew per launch by the
+// slot's own xcd_verdict under a fresh xtag. Nothing else is carried, so nothing depends on the XCD.
+template <int DB>
+__global__ void __launch_bounds__(64 * MAXW) chain_blocked_dyn_sweep_kernel(const PersistArgs* __restrict__ batch, int nb) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  chain_blocked_body<DB, false, false, true, false, true>(*(const SweepArgs*)(batch + j));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Paired-wave variant (PW = 2, opt-in: GADMM_BLOCK_PW=2): a workgroup of PWW = 8 waves computes up to 16 chain positions, wave
 // v the adjacent pair (2v, 2v + 1) = one head + one tail, with BOTH rows of (A + deg rho I)^{-1} in
@@ -1403,6 +1422,125 @@ int gadmm_chain_blocked_sweep_launch(const PersistArgs* batch, int nb, PersistAr
     const int x = xenv >= 0 ? xenv : ka.xcd;
     ka.xcd = x >= 2 ? 2 : 1;
     ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
+  const PersistArgs* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb};
+  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64 * MAXW), kargs, (size_t)lds, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
+// nb <= 8 independent D-GADMM epoch chunks (one GPU each, 12-wave layout, one DB class) in ONE launch of
+// chain_blocked_dyn_sweep_kernel, chunk j on the blocks b % 8 == j. Every entry passes the checks of the
+// single dynamic launch (epoch tables, padded inverse image, 1..EPL epochs, hard stop at or after the
+// start) and of the static sweep (own written buffers and xchk, block counts, residency); a static entry
+// (n_epochs == 0) belongs in gadmm_chain_blocked_sweep_launch. Entries may be first chunks and
+// continuations (cont) side by side. Staging buffers and return codes as the static sweep launcher.
+int gadmm_chain_blocked_dyn_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage,
+                                         PersistArgs* dev_stage, hipStream_t st) {
+  if (nb < 1 || nb > gadmm_chain_blocked_sweep_capacity()) {
+    gadmm_set_error("blocked dynamic sweep: %d solves, one launch takes 1..%d", nb, gadmm_chain_blocked_sweep_capacity());
+    return -1;
+  }
+  if (!batch || !host_stage || !dev_stage) {
+    gadmm_set_error("blocked dynamic sweep: null batch or staging buffer");
+    return -1;
+  }
+  int blocks[8], max_blocks = 0, sum_blocks = 0;
+  long lds = gadmm_chain_blocked_lds(0, 0) + DYN_LDS_BYTES;  // + the staged epoch tables
+  for (int j = 1; j < nb; ++j)
+    if ((batch[j].d <= 32) != (batch[0].d <= 32)) {
+      gadmm_set_error("blocked dynamic sweep: solves of different register classes (d = %d and %d; d <= 32 or "
+                      "33..52)", batch[0].d, batch[j].d);
+      return -1;
+    }
+  for (int j = 0; j < nb; ++j) {
+    const PersistArgs& a = batch[j];
+    if (a.n_epochs < 1) {
+      gadmm_set_error("blocked dynamic sweep: solve %d is static (no epochs): it belongs in the static sweep", j);
+      return -1;
+    }
+    if (a.nranks > 1 || a.sys_scope || a.blk_pw == 2 || a.timeline || a.blk_dl || a.dl_halo || a.blk_npeer != 0) {
+      gadmm_set_error("blocked dynamic sweep: solve %d is multi-rank, system-scope, paired-wave, instrumented or "
+                      "data-local (one-GPU 12-wave solves only)", j);
+      return -1;
+    }
+    if (a.n_epochs > EPL) {
+      gadmm_set_error("blocked dynamic sweep: solve %d has %d epochs, a launch stages at most %d", j, a.n_epochs, EPL);
+      return -1;
+    }
+    if (!a.epoch_start || !a.ep_slots || !a.ep_pos || !a.ep_flush || !a.minv_pad) {
+      gadmm_set_error("blocked dynamic sweep: solve %d lacks epoch tables or the padded inverse image "
+                      "(gadmm_chain_blocked_pad_len)", j);
+      return -1;
+    }
+    if (a.hard_stop < 0 || (a.hard_stop > 0 && a.hard_stop < a.start_iter)) {
+      gadmm_set_error("blocked dynamic sweep: solve %d: hard stop %d before its start %d", j, a.hard_stop, a.start_iter);
+      return -1;
+    }
+    if (!a.xchk) {
+      gadmm_set_error("blocked dynamic sweep: solve %d has no placement-check buffer (xchk)", j);
+      return -1;
+    }
+    if (a.blk_k < 1 || a.blk_len < 1 || a.blk_len + 4 * a.blk_k > MAXW || a.d < 1 || a.d > 52 || a.n < 2 ||
+        !a.blk_tab || !a.dec_push || !a.objg || !a.decg || !a.ctl || !a.trace || !a.theta || !a.mu || !a.slots ||
+        !a.Minv || !a.A || !a.b || !a.yy || !a.has_monitor || a.n != a.n_local) {
+      gadmm_set_error("blocked dynamic sweep: solve %d: unsupported configuration", j);
+      return -1;
+    }
+    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+      gadmm_set_error("blocked dynamic sweep: solve %d: ring/lag/tag range", j);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i) {
+      const PersistArgs& o = batch[i];
+      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.blk_tab == a.blk_tab ||
+          o.objg == a.objg || o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) ||
+          (a.rres && o.rres == a.rres)) {
+        gadmm_set_error("blocked dynamic sweep: solves %d and %d share a buffer that both write", i, j);
+        return -1;
+      }
+    }
+    const int W = (a.n + a.blk_len - 1) / a.blk_len, Wo = (a.n + MAXW - 1) / MAXW;
+    blocks[j] = W + Wo + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("blocked dynamic sweep: solve %d has %d workgroups, the placement check holds %d", j, blocks[j],
+                      XCHK);
+      return -1;
+    }
+    sum_blocks += blocks[j];
+    if (blocks[j] > max_blocks) max_blocks = blocks[j];
+    if (lds < (long)a.n * 8) lds = (long)a.n * 8;
+  }
+  if (lds > 160 * 1024) {
+    gadmm_set_error("blocked dynamic sweep: %ld B of LDS", lds);
+    return -1;
+  }
+  const void* fn = batch[0].d <= 32 ? (const void*)chain_blocked_dyn_sweep_kernel<32>
+                                    : (const void*)chain_blocked_dyn_sweep_kernel<52>;
+  const long cap = gadmm_resident_capacity(fn, 64 * MAXW, (size_t)lds);
+  const long cus_xcd = gadmm_cu_count() / 8;
+  if (sum_blocks > cap) {
+    gadmm_set_error("blocked dynamic sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
+    return -2;
+  }
+  for (int j = 0; j < nb; ++j)
+    if (blocks[j] > cus_xcd) {
+      gadmm_set_error("blocked dynamic sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
+      return -2;
+    }
+  if (lds > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int dbg = 0, xenv = -1;
+  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
+  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
+  for (int j = 0; j < nb; ++j) {
+    PersistArgs& ka = host_stage[j];
+    ka = batch[j];
+    ka.dbg = dbg;
+    const int x = xenv >= 0 ? xenv : ka.xcd;  // the 8-strided layout is inherent to a sweep (see above)
+    ka.xcd = x >= 2 ? 2 : 1;
+    ka.xtag = (int)gadmm_next_xtag();  // fresh per slot and per launch: a continuation re-runs the check
   }
   GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
   const PersistArgs* dbatch = dev_stage;

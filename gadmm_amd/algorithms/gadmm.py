@@ -986,6 +986,149 @@ def dynamic_group_admm(model, rho, obj0, acc, max_iter, path, path_cost, coheren
                       name="D-GADMM(coh=%s)" % coherence, **kw)
 
 
+def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, coherences, seeds, kind="findPath2",
+                             max_iters: Optional[Sequence[int]] = None, backend: str = "auto",
+                             engine_opts: Optional[dict] = None, comm: Optional[Comm] = None, **kw) -> List[RunResult]:
+    """``dynamic_group_admm`` at every coherence of ``coherences`` (member j re-chains from its own
+    ``PathSchedule`` seeded ``seeds[j]``): one ``RunResult`` per coherence, in the order given, equal to
+    ``[dynamic_group_admm(model, ..., coh, seed=s) for coh, s in zip(coherences, seeds)]`` in iterations,
+    objective trace, ``com_cost``, ``comm_units``, primal residual and ``converged``. On one HIP device
+    the solves run side by side, up to eight per kernel launch, one per XCD (engine/dyn_sweep.py; more
+    run in groups): every member on the blocked kernel's dynamic mode, in rounds of epoch chunks, each
+    to its own stop; a member that never re-chains within ``max_iter`` runs as a one-epoch slot. Only
+    the chains a member reaches are drawn. Each result carries ``extra['sweep'] = {width, slot, kernel,
+    placed, launches, wall_ms_launch}``; its ``wall_s`` is that solve's OWN time: the wall clock of the
+    rounds it took part in less the device time between its stop decision and the end of its last
+    round. ``extra['state']`` is not produced. ``max_iters``: one cap per member (default ``max_iter``).
+    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, ``GADMM_CHECK_EXCHANGE=1``, no
+    native library, a shape the kernel does not take, or a device that cannot hold the group's
+    workgroups -- it IS that loop, and every result records ``extra['sweep_fallback'] = reason``.
+    ``engine_opts``: ``refresh``, ``residual``, ``cache``, ``epoch_chunk`` as in ``chain_admm``."""
+    coherences, seeds = list(coherences), list(seeds)
+    if len(coherences) != len(seeds):
+        raise ValueError("seeds: one per coherence (%d coherences, %d seeds)" % (len(coherences), len(seeds)))
+    caps = [int(max_iter)] * len(coherences) if max_iters is None else [int(v) for v in max_iters]
+    if len(caps) != len(coherences):
+        raise ValueError("max_iters: one per coherence")
+    n_total = kw.pop("n_total", model.n_local)
+    local_ids = kw.pop("local_ids", list(range(model.n_local)))
+    opts = dict(engine_opts or {})
+    nranks = comm.nranks if comm is not None else 1
+
+    def sequential(reason: str) -> List[RunResult]:
+        out = []
+        for coh, s, mi in zip(coherences, seeds, caps):
+            r = dynamic_group_admm(model, rho, obj0, acc, mi, path, path_cost, coh, seed=s, kind=kind,
+                                   n_total=n_total, local_ids=local_ids, backend=backend, engine_opts=engine_opts,
+                                   comm=comm, **kw)
+            r.extra["sweep_fallback"] = reason
+            out.append(r)
+        return out
+
+    if not coherences:
+        return []
+    if model.device.type != "cuda":
+        return sequential("cpu tensors")
+    if backend == "torch":
+        return sequential("torch backend")
+    if nranks > 1:
+        return sequential("several ranks")
+    if model.kind != "linear" or sorted(int(w) for w in local_ids) != list(range(n_total)) \
+            or kw.get("local_solver") not in (None, "closed") or kw.get("state") is not None or kw.get("failures"):
+        return sequential("not a one-GPU linear closed-form chain")
+    if kw.get("check_exchange") or (kw.get("check_exchange") is None and getenv("GADMM_CHECK_EXCHANGE", "0") == "1"):
+        return sequential("exchange checker")
+    from ..ops import native
+    if not native.available():
+        return sequential("native library unavailable")
+    from ..engine.chain_engine import ResidencyError
+    from ..engine.chain_sweep import sweep_capacity
+    from ..engine.dyn_sweep import DynSweepEngine
+
+    refresh = bool(opts.get("refresh", False))
+    residual = bool(opts.get("residual", True))
+    cost_quirk = bool(kw.get("cost_quirk", True))
+    placement = kw.get("placement") or Placement.contiguous(n_total, 1)
+    n_heads = (n_total + 1) // 2
+
+    def run_group(g_cohs, idx):
+        _timing.host_stamp("dsw:begin")
+        g_caps = [caps[i] for i in idx]
+        key = ("dyn-sweep", n_total, tuple(map(int, local_ids)), float(rho), len(g_cohs), tuple(g_caps), residual)
+        cache = getattr(model, "_chain_engines", None)
+        sw = cache.get(key) if cache is not None else None
+        if sw is None:
+            if refresh:
+                from ..ops.linalg import gram
+                gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
+            sw = DynSweepEngine.coherence_sweep(model.X, model.y, local_ids, n_total, rho, len(g_cohs), obj0=obj0,
+                                                tol=acc, max_iters=g_caps, precomputed=(model.A, model.b, model.yy),
+                                                residual=residual)
+            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
+            if opts.get("cache", True):
+                if cache is None:
+                    cache = {}
+                    model._chain_engines = cache
+                cache[key] = sw
+        else:
+            sw.set_targets(obj0, acc)
+            if refresh:
+                sw.refresh(model.X, model.y)
+        scheds = []
+        for m, i in zip(sw.members, idx):
+            sc = PathSchedule(n_total, path, path_cost, coherences[i], kind=kind, seed=seeds[i])
+            m.set_path(sc.path, placement, 0)
+            scheds.append(sc)
+        runs = sw.run(scheds, epoch_chunk=opts.get("epoch_chunk"))
+        out = []
+        for j, (m, r, i) in enumerate(zip(sw.members, runs, idx)):
+            iters, coh = int(r.iters), coherences[i]
+            tr, tt = m.traces(iters)
+            if _static_schedule(scheds[j], g_caps[j]):  # chain_admm's static-chain accounting
+                com = np.arange(1, iters + 1) * (float(np.sum(r.cost0)) * (n_heads if cost_quirk else 1))
+            else:
+                com = _dyn_com_cost(r, n_total, n_heads if cost_quirk else 1)[:iters]
+            own = sum(sw.last_round_ms[:r.rounds]) * 1e-3 - r.tail_ticks * 1e-8
+            res = RunResult(algorithm="D-GADMM(coh=%s)" % coh, obj=tr, loss=np.abs(tr - obj0), iters=iters,
+                            converged=(int(r.done) == 1), wall_s=own, time_trace=tt,
+                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
+                            com_cost=np.asarray(com[:iters]), bytes_sent=0, bytes_total=0,
+                            primal_res=m.primal_residual(iters),
+                            extra={"backend": "native", "engine": "persistent-dynamic", "rank": 0, "nranks": 1,
+                                   "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0, "transport": "local",
+                                   "obj_mode": m.obj_mode_name, "engine_obj": m,
+                                   "sweep": {"width": len(g_cohs), "slot": j, "kernel": sw.last_kernel,
+                                             "placed": int(r.placed), "launches": int(r.rounds),
+                                             "wall_ms_launch": sw.last_wall_ms},
+                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j, "sweep_launches": int(r.rounds)})
+            out.append(res)
+        _timing.host_stamp("dsw:end")
+        return out
+
+    try:
+        with roctx_range("D-GADMM sweep native N=%d K=%d" % (n_total, len(coherences))):
+            return run_in_groups(coherences, sweep_capacity(), run_group)
+    except ResidencyError as e:
+        return sequential("ResidencyError: %s" % e)
+    except ValueError as e:  # a shape the sweep kernel does not take (d > 52, no blocked plan, ...)
+        return sequential("not eligible: %s" % e)
+
+
+def _dyn_com_cost(r, n_total: int, scale: int) -> np.ndarray:
+    """Cumulative ``com_cost`` of the iterations covered by the epochs a sweep member drew, with the
+    arithmetic of ``_chain_admm_native``'s ``cost_arrays`` (per-epoch hop-cost sums, scaled, one cumsum)."""
+    drawn_C, nd = r.costs, len(r.starts)
+    if drawn_C and any(c.dtype == object for c in drawn_C):
+        Cn = np.empty(sum(len(c) for c in drawn_C), dtype=object)
+        Cn[:] = [c for cc in drawn_C for c in cc]
+    else:
+        Cn = np.concatenate(drawn_C) if drawn_C else np.zeros((0, max(n_total - 1, 0)))
+    csum = Cn.sum(axis=1) if (len(Cn) and Cn.dtype != object) else np.asarray([float(np.sum(c)) for c in Cn])
+    per_it = np.concatenate([[float(np.sum(r.cost0))], csum]) * scale
+    which = np.searchsorted(r.starts[:nd], np.arange(1, int(r.span) + 1), side="right") - 1
+    return np.cumsum(per_it[which])
+
+
 def dynamic_group_admm_v0(model, rho, obj0, acc, max_iter, path_matrix, cost_matrix, coherence,
                           faithful_initial_cost=True, **kw) -> RunResult:
     """``dynamic_group_ADMM_closedForm_v0`` (A5): consume pre-generated chains. With

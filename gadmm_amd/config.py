@@ -44,7 +44,9 @@ class ExperimentConfig:
     reference: str = ""             # reference script this preset mirrors
     # the rho sweep of the linear closed-form entries: 'sequential' = one solve after the other,
     # 'concurrent' = up to eight rho values side by side in one kernel launch, one per XCD (one GPU;
-    # algorithms.chain_admm_sweep)
+    # algorithms.chain_admm_sweep). The D-GADMM coherence loops of E5 (part 2), E6 and E7 follow the
+    # same field: 'concurrent' = up to eight coherences side by side, in rounds of epoch-chunk
+    # launches (algorithms.dynamic_group_admm_sweep)
     sweep: str = "sequential"
 
     def override(self, **kw) -> "ExperimentConfig":

@@ -803,6 +803,77 @@ class NativeChainEngine:
         self._attach_blocked(pa, plan, ring, False)
         return pa, plan
 
+    # ---- a D-GADMM epoch chunk on the blocked kernel in the same halves (dyn_sweep.py)
+    def _stage_epochs_fused(self, pa, starts: np.ndarray, P: np.ndarray, start_iter: int, cont: bool):
+        """Blocked kernel on one GPU: checks, epoch tables, staging and the H2D copy (queued on the
+        engine stream) in one native call (gadmm_epoch_stage_blocked), the layout of run_persistent's
+        general path with no push masks. ``starts`` (E,), ``P`` (E, n): contiguous int64. Fills
+        ``pa.n_epochs`` and the table pointers."""
+        E, n = P.shape
+        total = E + 7 * E * n
+        stage = getattr(self, "_ep_stage", None)
+        if stage is None or stage[0].numel() < total:
+            cap = max(total, 4096)
+            h_t = torch.empty((cap,), dtype=torch.int32, pin_memory=True)
+            d_t = torch.empty((cap,), dtype=torch.int32, device=self.device)
+            stage = (h_t, d_t, h_t.numpy(), h_t.data_ptr(), d_t.data_ptr())
+            self._ep_stage = stage
+        if len(starts) != E:
+            raise ValueError("epochs: one chain per start")
+        got = int(self.lib.gadmm_epoch_stage_blocked(starts.ctypes.data, P.ctypes.data, E, n, int(start_iter),
+                                                     1 if cont else 0, stage[3], stage[0].numel(), stage[4],
+                                                     self.stream.cuda_stream))
+        if got < 0:
+            raise ValueError(self.lib.gadmm_last_error().decode())
+        dptr = stage[4]
+        pa.n_epochs = E
+        pa.epoch_start, pa.ep_slots = dptr, dptr + 4 * E
+        pa.ep_pos, pa.ep_flush = dptr + 4 * (E + 4 * E * n), dptr + 4 * (E + 5 * E * n)
+
+    def _attach_minv_pad(self, pa):
+        """D-GADMM in the blocked kernel: every inverse as a lane-major image of the kernel's quad
+        register layout (quad_pad_image), reloaded by a re-chain with coalesced unmasked loads
+        (PersistArgs::minv_pad); rebuilt from this solve's inverses on the engine stream, ahead of
+        the launch, only after the inverses changed."""
+        if getattr(self, "_minv_pad", None) is None or self._minv_pad_version != self._minv_version:
+            pf = getattr(self, "_pad_fast", None)
+            if pf is not None and pf[0] is self.Minv and pf[1] is self._minv_pad:
+                native.check(self.lib.gadmm_pad_image_f64(*pf[2]), "pad_image")  # in place, one launch
+            else:
+                with torch.cuda.stream(self.stream):  # in place after the first build (one launch)
+                    self._minv_pad = quad_pad_image(self.Minv.reshape(self.n_local * self.nvar, self.d, self.d),
+                                                    int(self.lib.gadmm_chain_blocked_pad_dim(self.d)),
+                                                    out=getattr(self, "_minv_pad", None))
+                src = _QUAD_SRC.get((self.d, int(self.lib.gadmm_chain_blocked_pad_dim(self.d)), self.device))
+                if src is not None and self.Minv.is_contiguous():
+                    # later rebuilds: the same native launch with its arguments bound once
+                    self._pad_fast = (self.Minv, self._minv_pad,
+                                      (self.Minv.data_ptr(), self.d * self.d, src.data_ptr(), int(src.numel()),
+                                       self.n_local * self.nvar, self._minv_pad.data_ptr(),
+                                       self.stream.cuda_stream))
+            self._minv_pad_version = self._minv_version
+        pa.minv_pad = self._minv_pad.data_ptr()
+
+    def prepare_blocked_dyn(self, starts: np.ndarray, P: np.ndarray, lag: int = 4, timeout_s: float = 20.0,
+                            start_iter: int = 1, pending_in: int = 0, hard_stop: int = 0, cont: bool = False):
+        """``(PersistArgs, plan)`` of one D-GADMM epoch chunk on the 12-wave blocked kernel's dynamic
+        mode, as ``run_persistent(epochs=(starts, P), blocked_dyn=True, ...)`` builds them, without
+        launching: the epoch tables are staged and their copy is queued on the engine stream, which the
+        launch must use. ``starts`` / ``P``: contiguous int64 arrays. State is reset or resumed by the
+        caller. Raises ValueError when the engine has no such plan."""
+        if self.nranks != 1 or not self.dynamic_eligible(None):
+            raise ValueError("dynamic persistent kernel not eligible for this engine/config")
+        plan = self.blocked_plan(None) if self.model == "linear" else None
+        if plan is None or plan[3] != 1:
+            raise ValueError("no 12-wave blocked plan for this engine (n=%d, d=%d)" % (self.n_total, self.d))
+        lag = max(lag, 8)
+        ring = lag + 4
+        pa, _, _, _ = self._persist_args(lag, ring, timeout_s, start_iter, pending_in, None, True, hard_stop, cont)
+        self._stage_epochs_fused(pa, starts, P, start_iter, cont)
+        self._attach_blocked(pa, plan, ring, True)
+        self._attach_minv_pad(pa)
+        return pa, plan
+
     def finish_blocked(self, start_iter: int, wall_ms: float, fetch: bool, what: str) -> EngineRun:
         """The ``EngineRun`` of a static blocked solve whose read-back (``_queue_readback``) has
         completed: decodes the control block as ``run_persistent`` does."""
@@ -873,29 +944,7 @@ class NativeChainEngine:
             and epochs[0].dtype == np.int64 and epochs[1].dtype == np.int64 and epochs[1].flags.c_contiguous \
             and epochs[0].flags.c_contiguous
         if fused:
-            # blocked kernel on one GPU: checks, tables, staging and the H2D copy in one native call
-            # (gadmm_epoch_stage_blocked), the layout of the general path below with no push masks
-            starts, P = epochs
-            E, n = P.shape
-            total = E + 7 * E * n
-            stage = getattr(self, "_ep_stage", None)
-            if stage is None or stage[0].numel() < total:
-                cap = max(total, 4096)
-                h_t = torch.empty((cap,), dtype=torch.int32, pin_memory=True)
-                d_t = torch.empty((cap,), dtype=torch.int32, device=dev)
-                stage = (h_t, d_t, h_t.numpy(), h_t.data_ptr(), d_t.data_ptr())
-                self._ep_stage = stage
-            if len(starts) != E:
-                raise ValueError("epochs: one chain per start")
-            got = int(self.lib.gadmm_epoch_stage_blocked(starts.ctypes.data, P.ctypes.data, E, n, int(start_iter),
-                                                         1 if cont else 0, stage[3], stage[0].numel(), stage[4],
-                                                         self.stream.cuda_stream))
-            if got < 0:
-                raise ValueError(self.lib.gadmm_last_error().decode())
-            dptr = stage[4]
-            pa.n_epochs = E
-            pa.epoch_start, pa.ep_slots = dptr, dptr + 4 * E
-            pa.ep_pos, pa.ep_flush = dptr + 4 * (E + 4 * E * n), dptr + 4 * (E + 5 * E * n)
+            self._stage_epochs_fused(pa, epochs[0], epochs[1], start_iter, cont)
         elif epochs is not None:
             if isinstance(epochs, tuple) and len(epochs) == 2 and isinstance(epochs[1], np.ndarray):
                 starts = np.asarray(epochs[0], dtype=np.int64)                      # (starts, paths) arrays
@@ -978,28 +1027,7 @@ class NativeChainEngine:
         if plan is not None:  # temporally blocked kernel: one halo hand-off per k iterations
             self._attach_blocked(pa, plan, ring, epochs is not None)
             if epochs is not None:
-                # D-GADMM in the blocked kernel: every inverse as a lane-major image of the kernel's quad
-                # register layout (quad_pad_image), reloaded by a re-chain with coalesced unmasked loads
-                # (PersistArgs::minv_pad); rebuilt from this solve's inverses on the engine stream, ahead of
-                # the launch, only after the inverses changed
-                if getattr(self, "_minv_pad", None) is None or self._minv_pad_version != self._minv_version:
-                    pf = getattr(self, "_pad_fast", None)
-                    if pf is not None and pf[0] is self.Minv and pf[1] is self._minv_pad:
-                        native.check(self.lib.gadmm_pad_image_f64(*pf[2]), "pad_image")  # in place, one launch
-                    else:
-                        with torch.cuda.stream(self.stream):  # in place after the first build (one launch)
-                            self._minv_pad = quad_pad_image(self.Minv.reshape(self.n_local * self.nvar, self.d, self.d),
-                                                            int(self.lib.gadmm_chain_blocked_pad_dim(self.d)),
-                                                            out=getattr(self, "_minv_pad", None))
-                        src = _QUAD_SRC.get((self.d, int(self.lib.gadmm_chain_blocked_pad_dim(self.d)), self.device))
-                        if src is not None and self.Minv.is_contiguous():
-                            # later rebuilds: the same native launch with its arguments bound once
-                            self._pad_fast = (self.Minv, self._minv_pad,
-                                              (self.Minv.data_ptr(), self.d * self.d, src.data_ptr(), int(src.numel()),
-                                               self.n_local * self.nvar, self._minv_pad.data_ptr(),
-                                               self.stream.cuda_stream))
-                    self._minv_pad_version = self._minv_version
-                pa.minv_pad = self._minv_pad.data_ptr()
+                self._attach_minv_pad(pa)
         self.last_kernel = ("blocked%s(k=%d,L=%d,W=%d,pw=%d)" % ((("-dyn" if epochs is not None else ""),) + tuple(plan))
                             if plan is not None else "per-worker")
         # launches name the engine stream explicitly

@@ -9,9 +9,9 @@ Part 2 (:142-173): D-GADMM (A4, findPath2 re-chaining) for coherence in {1e9, 1,
 All chains come from one seeded RNG, so every rank derives the same sequence with no message."""
 import numpy as np
 
-from ..algorithms import dynamic_group_admm, dynamic_group_admm_v0, static_group_admm
+from ..algorithms import dynamic_group_admm_v0, static_group_admm
 from ..parallel import topology as T
-from .common import Problem, run_entry
+from .common import Problem, dgadmm_coherences, run_entry
 
 ENTRY = "Dynamic_LinearRegression_Synthetic"
 
@@ -47,10 +47,9 @@ def body(cfg, sess, args, writer):
     r0.extra["inflation"] = infl
     runs["D-GADMM_v0(coh=%g)" % cfg.coherence_v0] = r0
     p1, c1, _ = T.find_path(N, rng)
-    for coh in cfg.coherences:
-        r = dynamic_group_admm(prob.model, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, p1, c1, coh,
-                               seed=cfg.path_seed + int(min(coh, 1e6)), **kw, **fab(coh))
-        runs["D-GADMM(coh=%g)" % coh] = r
+    # (--set sweep=concurrent on one GPU: the five coherences side by side, one per XCD)
+    runs.update(dgadmm_coherences(prob, sess, args, rho, p1, c1,
+                                  [cfg.path_seed + int(min(coh, 1e6)) for coh in cfg.coherences]))
     for r in runs.values():
         r.extra.pop("engine_obj", None)
         r.extra.pop("state", None)

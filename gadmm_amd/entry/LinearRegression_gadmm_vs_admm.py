@@ -5,9 +5,9 @@ sum(P_central) + max(P_central), chain cost = sum(pathCost) of the *initial* cha
 variant (:128-179; the quirk that ignores D-GADMM's own com_cost is kept)."""
 import numpy as np
 
-from ..algorithms import dynamic_group_admm, standard_admm
+from ..algorithms import standard_admm
 from ..parallel import topology as T
-from .common import Problem, gadmm_solve, run_entry
+from .common import Problem, dgadmm_coherences, gadmm_solve, run_entry
 
 ENTRY = "LinearRegression_gadmm_vs_admm"
 
@@ -28,11 +28,9 @@ def body(cfg, sess, args, writer):
     runs["ADMM(star)"] = r
     g = gadmm_solve(prob, sess, rho, cfg.acc, cfg.gadmm_iters, args.backend, name="GADMM")
     runs["GADMM"] = g
-    for coh in cfg.coherences:
-        runs["D-GADMM(coh=%g)" % coh] = dynamic_group_admm(
-            prob.model, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, path, cost, coh, seed=cfg.path_seed + int(coh),
-            n_total=prob.n_total, local_ids=prob.local_ids, placement=prob.placement, backend=args.backend,
-            **sess.chain_kw(prob.n_total, prob.d, dynamic=float(coh) < cfg.gadmm_iters + 1))
+    # (--set sweep=concurrent on one GPU: the coherences side by side, one per XCD)
+    runs.update(dgadmm_coherences(prob, sess, args, rho, path, cost,
+                                  [cfg.path_seed + int(coh) for coh in cfg.coherences]))
     for k, v in runs.items():
         v.extra.pop("engine_obj", None)
         v.extra.pop("state", None)

@@ -345,6 +345,38 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
     return out
 
 
+def dgadmm_coherences(prob: Problem, sess: Session, args, rho: float, path, cost, seeds) -> Dict[str, object]:
+    """The reference's coherence loops of D-GADMM (Dynamic_LinearRegression_Synthetic.m:142-173,
+    LinearRegression_gadmm_vs_admm.m, dynamic_LinearRegression_Real.m): one ``dynamic_group_admm`` per
+    coherence of the preset, seeded ``seeds[j]``, over the same shards and initial chain. With the preset
+    field ``sweep='concurrent'`` on a one-GPU session they run side by side, one per XCD
+    (``dynamic_group_admm_sweep``), unless the backend is torch or a checkpoint is requested; each run's
+    summary then names the sweep kernel, its slot and its launches."""
+    from ..algorithms import dynamic_group_admm, dynamic_group_admm_sweep
+    from ..utils.timing import roctx_range
+
+    cfg = prob.cfg
+    cohs = list(cfg.coherences)
+    out = {}
+    concurrent = (cfg.sweep == "concurrent" and cfg.model == "linear" and sess.world == 1 and len(cohs) > 0
+                  and sess.device.type == "cuda" and args.backend != "torch" and not getattr(args, "checkpoint", None))
+    if concurrent:
+        with roctx_range("dgadmm coherences concurrent"):
+            rs = dynamic_group_admm_sweep(prob.model, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, path, cost, cohs,
+                                          list(seeds), n_total=prob.n_total, local_ids=prob.local_ids,
+                                          placement=prob.placement, backend=args.backend, comm=sess.comm)
+        for coh, r in zip(cohs, rs):
+            out["D-GADMM(coh=%g)" % coh] = r
+        return out
+    for coh, seed in zip(cohs, seeds):
+        with roctx_range("dgadmm coh=%g" % coh):
+            out["D-GADMM(coh=%g)" % coh] = dynamic_group_admm(
+                prob.model, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, path, cost, coh, seed=seed,
+                n_total=prob.n_total, local_ids=prob.local_ids, placement=prob.placement, backend=args.backend,
+                **sess.chain_kw(prob.n_total, prob.d, dynamic=float(coh) < cfg.gadmm_iters + 1))
+    return out
+
+
 def baselines(prob: Problem, sess: Session) -> Dict[str, object]:
     from ..algorithms import gd_dgd_lag, dual_averaging
 
