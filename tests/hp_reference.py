@@ -1,0 +1,314 @@
+"""Plain high-precision references of the solvers the HIP kernels implement (CPU, NumPy only).
+
+Every function takes ``dtype`` (``np.longdouble`` or ``np.float64``) and does all of its arithmetic in
+that dtype: the long-double run is the reference a kernel is held against, the float64 run of the very
+same recurrence measures how far two correct float64 implementations may sit apart
+(``noise_level``). The recurrences follow gadmm_amd/oracle/reference.py (the executable
+specification), in the form the kernels evaluate them:
+
+* the closed-form local solve applies an explicit inverse of ``A_n + deg rho I`` (the kernels cache
+  it); NumPy has no long-double solve, so the long-double inverse is the float64 one refined by
+  three Newton-Schulz steps ``X <- X (2 I - M X)`` (quadratic: 1e-13 -> 1e-26 -> below 2^-63);
+* the linear objective is the Gram form ``1/2 th'A th - b'th + 1/2 y'y``;
+* chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form).
+
+This is a helper module, not a conftest: test modules import it as ``import hp_reference``.
+"""
+import numpy as np
+
+# x86 long double: 64-bit mantissa. Anything narrower is no reference for float64 kernels.
+assert np.finfo(np.longdouble).eps <= 2.0 ** -63, \
+    "hp_reference needs an extended-precision long double (eps %g)" % np.finfo(np.longdouble).eps
+
+LD = np.longdouble
+FACTOR = 8.0  # kernel error <= FACTOR * max(float64 noise of the recurrence, dot-product floor)
+
+
+def spd_inverse(M, dtype):
+    """Explicit inverse of the SPD matrix ``M`` in ``dtype``."""
+    M = np.asarray(M, dtype=dtype)
+    if np.dtype(dtype) == np.float64:
+        return np.linalg.inv(M)
+    X = np.linalg.inv(M.astype(np.float64)).astype(dtype)
+    two_i = 2 * np.eye(M.shape[0], dtype=dtype)
+    for _ in range(3):
+        X = X @ (two_i - M @ X)
+    return X
+
+
+def _gram(X, y, dtype):
+    X = np.asarray(X, dtype=dtype)
+    y = np.asarray(y, dtype=dtype)
+    A = np.einsum("nmi,nmj->nij", X, X)
+    b = np.einsum("nmi,nm->ni", X, y)
+    yy = np.einsum("nm,nm->n", y, y)
+    return A, b, yy
+
+
+def _gram_objective(A, b, yy, th):
+    half = np.asarray(0.5, dtype=th.dtype)
+    tot = np.zeros((), dtype=th.dtype)
+    for n in range(th.shape[0]):
+        tot = tot + (half * (th[n] @ (A[n] @ th[n])) - b[n] @ th[n] + half * yy[n])
+    return tot
+
+
+def gadmm_linear(X, y, rho, K, dtype=LD):
+    """Per-worker-dual GADMM on the identity chain (``oracle.reference.dgadmm_linear`` without
+    re-chaining): heads, tails, then every worker's ``mu``. ``X`` (N, m, d), ``y`` (N, m).
+    Returns ``(theta (K, N, d), mu (N, d) after iteration K, objectives (K,))``."""
+    N, m, d = X.shape
+    A, b, yy = _gram(X, y, dtype)
+    rho = np.asarray(rho, dtype=dtype)
+    eye = np.eye(d, dtype=dtype)
+    deg = [(n > 0) + (n < N - 1) for n in range(N)]
+    Minv = [spd_inverse(A[n] + deg[n] * rho * eye, dtype) for n in range(N)]
+    th = np.zeros((N, d), dtype=dtype)
+    mu = np.zeros((N, d), dtype=dtype)
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    for k in range(K):
+        for phase in (0, 1):
+            for n in range(phase, N, 2):
+                r = b[n] - mu[n]
+                if n > 0:
+                    r = r + rho * th[n - 1]
+                if n < N - 1:
+                    r = r + rho * th[n + 1]
+                th[n] = Minv[n] @ r
+        for n in range(N):
+            upd = np.zeros(d, dtype=dtype)
+            if n < N - 1:
+                upd = upd + rho * (th[n] - th[n + 1])
+            if n > 0:
+                upd = upd - rho * (th[n - 1] - th[n])
+            mu[n] = mu[n] + upd
+        thetas[k] = th
+        obj[k] = _gram_objective(A, b, yy, th)
+    return thetas, mu, obj
+
+
+def star_admm_linear(X, y, rho, K, dtype=LD):
+    """Star ADMM, the hub is worker N - 1 and holds a shard (``oracle.reference.std_admm_linear``).
+    Returns ``(theta (K, N, d), lam (N, d) after iteration K (the hub's row stays 0), objectives)``."""
+    N, m, d = X.shape
+    A, b, yy = _gram(X, y, dtype)
+    rho = np.asarray(rho, dtype=dtype)
+    eye = np.eye(d, dtype=dtype)
+    hub = N - 1
+    Minv = [spd_inverse(A[n] + (rho if n != hub else (N - 1) * rho) * eye, dtype) for n in range(N)]
+    th = np.zeros((N, d), dtype=dtype)
+    lam = np.zeros((N, d), dtype=dtype)
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    for k in range(K):
+        for n in range(hub):
+            th[n] = Minv[n] @ (b[n] - lam[n] + rho * th[hub])
+        c1 = np.zeros(d, dtype=dtype)
+        s1 = np.zeros(d, dtype=dtype)
+        for n in range(hub):
+            c1 = c1 + lam[n]
+            s1 = s1 + th[n]
+        th[hub] = Minv[hub] @ (b[hub] + c1 + rho * s1)
+        for n in range(hub):
+            lam[n] = lam[n] + rho * (th[n] - th[hub])
+        thetas[k] = th
+        obj[k] = _gram_objective(A, b, yy, th)
+    return thetas, lam, obj
+
+
+def gadmm_logistic_gd(X, y, rho, lam, step, K, max_inner, inner_tol, dtype=LD):
+    """GADMM logistic regression with the inexact inner gradient descent
+    (``oracle.reference.gadmm_logistic_gd`` / ``logreg_gd``): the prox terms are frozen at the
+    pre-update iterate, an inner solve takes at most ``max_inner`` steps and stops after the first
+    step with all ``|dx| < inner_tol`` (strict). Returns ``(theta (K, N, d), mu (N, d) per-worker
+    duals after iteration K, objectives (K,), inner step counts (K, N), margin)``; ``margin`` is the
+    smallest relative distance ``|max|dx| / inner_tol - 1|`` of any stop test from its threshold
+    (inf when ``inner_tol`` is 0: no test can pass)."""
+    N, m, d = X.shape
+    X = np.asarray(X, dtype=dtype)
+    y = np.asarray(y, dtype=dtype)
+    rho, lam, step, tol = (np.asarray(v, dtype=dtype) for v in (rho, lam, step, inner_tol))
+    one = np.asarray(1.0, dtype=dtype)
+    half = np.asarray(0.5, dtype=dtype)
+    th = np.zeros((N, d), dtype=dtype)
+    dual = np.zeros((N, d), dtype=dtype)  # edge duals; row N - 1 stays 0
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    inner = np.zeros((K, N), dtype=np.int64)
+    margin = [np.inf]
+    z = np.zeros(d, dtype=dtype)
+
+    def update(n, k):
+        c1 = dual[n - 1] if n > 0 else z
+        t1 = rho * (th[n] - th[n - 1]) if n > 0 else z
+        c2 = dual[n] if n < N - 1 else z
+        t2 = rho * (th[n] - th[n + 1]) if n < N - 1 else z
+        H, Y = X[n], y[n]
+        x = th[n].copy()
+        steps = 0
+        for _ in range(int(max_inner)):
+            g = -(H.T @ (Y / (one + np.exp(Y * (H @ x))))) + lam * x - c1 + c2 + t1 + t2
+            x_new = x - step * g
+            dx = np.max(np.abs(x_new - x))
+            x = x_new
+            steps += 1
+            if tol > 0:
+                margin[0] = min(margin[0], float(abs(dx / tol - one)))
+            if dx < tol:
+                break
+        th[n] = x
+        inner[k, n] = steps
+
+    for k in range(K):
+        for n in range(0, N, 2):
+            update(n, k)
+        for n in range(1, N, 2):
+            update(n, k)
+        for n in range(N - 1):
+            dual[n] = dual[n] + rho * (th[n] - th[n + 1])
+        thetas[k] = th
+        tot = np.zeros((), dtype=dtype)
+        for n in range(N):
+            tot = tot + (lam * half * (th[n] @ th[n]) + np.sum(np.log1p(np.exp(-y[n] * (X[n] @ th[n])))))
+        obj[k] = tot
+    mu = dual.copy()
+    mu[1:] = mu[1:] - dual[:-1]
+    return thetas, mu, obj, inner, margin[0]
+
+
+def edge_to_worker_duals(lam_edge):
+    """Per-worker aggregate ``mu_n = lam_n - lam_{n-1}`` of edge duals (N, d) whose last row is 0."""
+    mu = np.array(lam_edge, copy=True)
+    mu[1:] = mu[1:] - lam_edge[:-1]
+    return mu
+
+
+def make_linear(n, m, d, seed):
+    """Gaussian shards with noise-dominated labels ``y = X th* + N(0, 1)``, ``|th*| = 1``: the final
+    objective stays a fixed fraction of ``1/2 y'y``, so the Gram-form objective does not cancel and a
+    relative tolerance means something. Returns ``(X (n, m, d), y (n, m), rho = 0.5 m)``."""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, m, d))
+    ts = rng.standard_normal(d)
+    ts = ts / np.linalg.norm(ts)
+    y = X @ ts + rng.standard_normal((n, m))
+    return X, y, 0.5 * m
+
+
+def make_logistic(n, m, d, seed):
+    """Gaussian shards ``/ sqrt(d)``, labels +-1. Returns ``(X, y, rho, lam, step)`` with
+    ``lam = 1e-3``, ``step = 1 / max_n(lambda_max(X_n'X_n) / 4 + lam)`` and ``rho = 0.1 / step``."""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, m, d)) / np.sqrt(d)
+    y = np.where(rng.standard_normal((n, m)) > 0, 1.0, -1.0)
+    lam = 1e-3
+    L = max(0.25 * float(np.linalg.eigvalsh(X[i].T @ X[i])[-1]) + lam for i in range(n))
+    step = 1.0 / L
+    return X, y, 0.1 / step, lam, step
+
+
+def noise_level(ref_ld, ref_f64, scale):
+    """Largest absolute difference of two runs, divided by ``scale`` (a scalar, or per value)."""
+    diff = np.abs(np.asarray(ref_ld, dtype=LD) - np.asarray(ref_f64, dtype=LD)) / np.asarray(scale, dtype=LD)
+    return float(np.max(diff)) if diff.size else 0.0
+
+
+def bound(e64, d, m_logistic=0):
+    """``FACTOR * max(e64, max(d, m_logistic, 16) * 2^-53)``: the float64 noise of the recurrence, with
+    the standard dot-product bound as the floor for runs that happen to round luckily."""
+    return FACTOR * max(float(e64), max(int(d), int(m_logistic), 16) * 2.0 ** -53)
+
+
+class Reference:
+    """A case's long-double run, the float64 noise of the same recurrence, and the bounds from them.
+
+    ``theta`` (K, N, d), ``dual`` (N, d), ``obj`` (K,) in long double; ``rho``; ``scale_theta`` =
+    max |theta| over the run; ``b_theta`` / ``b_dual`` / ``b_obj``: the bounds of the three relative
+    errors ``err_theta`` / ``err_dual`` / ``err_obj`` measure."""
+
+    def __init__(self, ld, f64, rho, d, m_logistic=0):
+        self.theta, self.dual, self.obj = ld[0], ld[1], ld[2]
+        self.extra = ld[3:]
+        self.rho = float(rho)
+        self.scale_theta = float(np.max(np.abs(self.theta)))
+        self.e_theta = noise_level(self.theta, f64[0], self.scale_theta)
+        self.e_dual = noise_level(self.dual, f64[1], self.rho * self.scale_theta)
+        self.e_obj = noise_level(self.obj, f64[2], np.abs(self.obj))
+        self.b_theta = bound(self.e_theta, d, m_logistic)
+        self.b_dual = bound(self.e_dual, d, m_logistic)
+        self.b_obj = bound(self.e_obj, d, m_logistic)
+
+    def err_theta(self, theta, k=None):
+        """``theta`` (N, d) against the reference after iteration ``k`` (1-based; None: the last)."""
+        ref = self.theta[-1 if k is None else k - 1]
+        return noise_level(ref, theta, self.scale_theta)
+
+    def err_dual(self, dual, ref=None):
+        return noise_level(self.dual if ref is None else ref, dual, self.rho * self.scale_theta)
+
+    def err_obj(self, obj):
+        obj = np.asarray(obj)
+        return noise_level(self.obj[:len(obj)], obj, np.abs(self.obj[:len(obj)]))
+
+
+# ------------------------------------------------------------------------------------------------
+# The shapes of tests/test_gpu_dispatch_classes.py (why each is there is written next to the
+# parameter lists of that file) and their references, built once per process and shared.
+K_ITERS = 20
+MAX_INNER = 6
+
+LINEAR_SHAPES = [(2, 3, 1), (3, 7, 3), (5, 40, 32), (4, 40, 33), (5, 60, 52), (5, 70, 53), (4, 40, 64),
+                 (3, 80, 65), (4, 150, 128), (3, 150, 129), (3, 280, 256), (3, 280, 257)]
+LOGISTIC_SHAPES = [(3, 5, 3), (4, 30, 20), (3, 40, 52), (3, 52, 20), (3, 40, 53), (3, 64, 64), (3, 100, 20),
+                   (2, 60, 128), (3, 200, 30), (3, 250, 40), (3, 100, 100)]
+STAR_SHAPES = [(3, 7, 3), (4, 60, 52), (4, 70, 53), (3, 40, 64), (3, 80, 65)]
+LIVE_STOP = ((4, 30, 20), 1e-3)  # the one logistic case with a live inner stop rule
+
+_CACHE = {}
+
+
+def seed_of(n, m, d):
+    return 1000003 * n + 1009 * m + d
+
+
+def _cached(key, build):
+    if key not in _CACHE:
+        _CACHE[key] = build()
+    return _CACHE[key]
+
+
+def _freeze(*arrs):
+    for a in arrs:
+        a.setflags(write=False)
+
+
+def linear_case(n, m, d, K=K_ITERS):
+    """``(X, y, rho, Reference)`` of ``gadmm_linear`` on ``make_linear(n, m, d, seed_of(n, m, d))``."""
+    def build():
+        X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
+        _freeze(X, y)
+        return X, y, rho, Reference(gadmm_linear(X, y, rho, K, LD), gadmm_linear(X, y, rho, K, np.float64), rho, d)
+    return _cached(("lin", n, m, d, K), build)
+
+
+def star_case(n, m, d, K=K_ITERS):
+    """As ``linear_case`` for ``star_admm_linear`` (the same data)."""
+    def build():
+        X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
+        _freeze(X, y)
+        return X, y, rho, Reference(star_admm_linear(X, y, rho, K, LD), star_admm_linear(X, y, rho, K, np.float64),
+                                    rho, d)
+    return _cached(("star", n, m, d, K), build)
+
+
+def logistic_case(n, m, d, K=K_ITERS, max_inner=MAX_INNER, inner_tol=0.0):
+    """``(X, y, rho, lam, step, Reference)`` of ``gadmm_logistic_gd``; ``Reference.extra`` holds the
+    inner step counts (K, N) and the decision margin."""
+    def build():
+        X, y, rho, lam, step = make_logistic(n, m, d, seed_of(n, m, d))
+        _freeze(X, y)
+        ld = gadmm_logistic_gd(X, y, rho, lam, step, K, max_inner, inner_tol, LD)
+        f64 = gadmm_logistic_gd(X, y, rho, lam, step, K, max_inner, inner_tol, np.float64)
+        return X, y, rho, lam, step, Reference(ld, f64, rho, d, m)
+    return _cached(("log", n, m, d, K, max_inner, inner_tol), build)

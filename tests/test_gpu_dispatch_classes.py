@@ -1,0 +1,446 @@
+"""Every kernel dispatch class of the chain, logistic and star solvers against a long-double reference.
+
+The kernels dispatch on d (and on m for logistic) into separately instantiated templates; the rest of
+the suite solves end to end at d = 50 almost only, and holds the odd shapes against another kernel,
+not against an independent reference. Here each class runs K = 20 iterations of a tiny problem with no
+stop rule (tol = 0, obj0 = 0, max_iter = K: the comparisons in the kernels are strict, nothing stops
+early, no discrete decision can tie) and theta, the duals and the objectives are compared with
+tests/hp_reference.py (plain NumPy in long double). The tolerance is not a fixed rtol: per case,
+
+    err_kernel <= 8 * max(e64, max(d, m_logistic, 16) * 2^-53)
+
+where e64 is the distance of the SAME recurrence run in float64 NumPy from its long-double run (taken
+separately for theta / max|theta|, the dual / (rho max|theta|) and each objective value), and the
+second term is the dot-product bound, the floor for runs that round luckily. The factor 8 pays for a
+different summation order, FMA contraction and the ~2 ulp of the fast sigmoid; an indexing, tail or
+stale-LDS mistake moves theta by ~1/d relative, eleven orders of magnitude above the bound.
+Each test prints err / bound; profiles/dispatch_classes/README.md records the measured table.
+
+Each parameter list names the dispatch condition that puts its d in its class: if a threshold moves,
+the list next to it is the one to revisit.
+
+Run with: pytest -m gpu tests/test_gpu_dispatch_classes.py -s
+"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import hp_reference as H
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K = H.K_ITERS
+BLOCK = 4  # iterations per graph replay: divides K, so the graph engine replays every iteration
+assert K % BLOCK == 0
+
+
+@pytest.fixture(autouse=True)
+def _poison_lds():
+    """Every test starts with NaN-filled LDS on every CU (as tests/test_gpu.py)."""
+    if torch.cuda.is_available():
+        from gadmm_amd.ops import native
+        native.poison_lds()
+    yield
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _host(t):
+    return t.detach().cpu().numpy()
+
+
+def _report(tag, ratios):
+    """Print err / bound of every quantity, then assert all of them <= 1."""
+    print("%s: err/bound %s" % (tag, " ".join("%s %.3f" % kv for kv in ratios.items())))
+    bad = {k: v for k, v in ratios.items() if not v <= 1.0}
+    assert not bad, (tag, bad)
+
+
+# ------------------------------------------------------------------------------------------------
+# Linear chain
+def _linear_engine(n, m, d, **kw):
+    from gadmm_amd.engine.chain_engine import NativeChainEngine
+    from gadmm_amd.parallel.topology import Placement
+    X, y, rho, _ = H.linear_case(n, m, d)
+    eng = NativeChainEngine(_dev(X), _dev(y), list(range(n)), n, "linear", rho=rho, obj0=0.0, tol=0.0, max_iter=K,
+                            obj_mode="exact", block=BLOCK, **kw)
+    eng.set_path(list(range(n)), Placement.contiguous(n, 1), 0)
+    eng.reset()
+    return eng
+
+
+def _state_ratios(eng, ref, last, prefix=""):
+    """theta after iteration ``last`` and, once the heads' lazy last dual update is applied
+    (flush_duals; header of csrc/kernels/chain_small.hip), mu after it."""
+    th = _host(eng.local_theta())
+    eng.flush_duals()
+    eng.stream.synchronize()
+    mu = _host(eng.mu)
+    assert np.all(np.isfinite(th)) and np.all(np.isfinite(mu))
+    return {prefix + "theta": ref.err_theta(th, last) / ref.b_theta, prefix + "dual": ref.err_dual(mu) / ref.b_dual}
+
+
+def run_linear_graph(n, m, d, use_graph=True):
+    """The phase kernels (chain_small.hip chain_phase_linear<NC>, chain_big.hip), replayed as a graph
+    or launched eagerly: K iterations, then theta, mu and the K objectives."""
+    ref = H.linear_case(n, m, d)[3]
+    eng = _linear_engine(n, m, d)
+    r = eng.run(stop_iter=K, use_graph=use_graph)
+    assert r.iters == K and eng.ctl_state()["iter"] == K + 1, (r.iters, r.done, eng.ctl_state())
+    # (a block shorter than the captured one is enqueued kernel by kernel: BLOCK divides K, none is)
+    assert r.replays == K // BLOCK and (eng.graph_ok() or not use_graph) and eng.obj_mode_name == "exact"
+    out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
+    out.update(_state_ratios(eng, ref, K))
+    eng.close()
+    return out
+
+
+def run_linear_persistent(n, m, d, family):
+    """One persistent launch (``family``: "per-worker" or "blocked(", chosen by the environment the
+    caller set). The kernel learns the cap's stop decision ``lag`` iterations late and stops after
+    iteration ctl.iter - 1: theta and mu are compared with the reference run that far."""
+    eng = _linear_engine(n, m, d)
+    assert eng.persistent_eligible()
+    if family == "blocked(":
+        assert eng.blocked_plan() is not None
+    r = eng.run_persistent()
+    assert eng.last_kernel.startswith(family), eng.last_kernel
+    last = eng.ctl_state()["iter"] - 1
+    assert r.iters == K and K <= last <= K + 16, (r.iters, r.done, last)
+    ref = H.linear_case(n, m, d, last)[3]
+    out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
+    out.update(_state_ratios(eng, ref, last))
+    kern = eng.last_kernel
+    eng.close()
+    return out, kern
+
+
+# d -> class of the graph phases: gadmm_chain_phase (chain_small.hip) sends d > 256 to
+# gadmm_chain_phase_big (chain_big.hip) and switches on nc = (d + 63) / 64 between
+# chain_phase_linear<1> (d <= 64), <2> (65..128) and <4> (129..256).
+LINEAR_GRAPH = [
+    (2, 3, 1),       # <1>: the smallest possible; every worker has degree 1 (one inverse variant)
+    (3, 7, 3),       # <1>: odd n, the last worker is a head
+    (5, 40, 32),     # <1>
+    (4, 40, 33),     # <1>
+    (5, 60, 52),     # <1>
+    (5, 70, 53),     # <1>
+    (4, 40, 64),     # <1>: the top of nc = 1; m < d, the Gram is rank-deficient and the shift makes it SPD
+    (3, 80, 65),     # <2>: the first nc = 2 shape
+    (4, 150, 128),   # <2>: the top of nc = 2
+    (3, 150, 129),   # <4>: the first
+    (3, 280, 256),   # <4>: the top
+    (3, 280, 257),   # chain_big: the first d > 256
+]
+assert LINEAR_GRAPH == H.LINEAR_SHAPES
+
+
+@pytest.mark.parametrize("n,m,d", LINEAR_GRAPH)
+def test_linear_graph_engine(n, m, d):
+    _report("linear graph %s" % ((n, m, d),), run_linear_graph(n, m, d))
+
+
+# the same kernels launched one by one (run(use_graph=False)): one shape per phase-kernel family
+@pytest.mark.parametrize("n,m,d", [(2, 3, 1), (3, 80, 65), (3, 280, 257)])
+def test_linear_eager_phases(n, m, d):
+    _report("linear eager %s" % ((n, m, d),), run_linear_graph(n, m, d, use_graph=False))
+
+
+# per-worker persistent kernel: pick_variant (chain_persistent.hip) takes the register kernel at
+# d <= DREG = 64 -- QT = 13 at d <= 52, QT = 16 above -- and the LDS kernel with NC = 2 at 65..128;
+# gadmm_chain_persistent_lds returns 0 (not eligible) at d > 128.
+LINEAR_PER_WORKER = [
+    (2, 3, 1), (3, 7, 3), (5, 40, 32), (4, 40, 33),
+    (5, 60, 52),     # REG QT = 13: the top
+    (5, 70, 53),     # REG QT = 16: the first
+    (4, 40, 64),     # REG QT = 16: the top
+    (3, 80, 65),     # LDS NC = 2: the first
+    (4, 150, 128),   # LDS NC = 2: the top, and the top of the persistent kernel
+]
+
+
+@pytest.mark.parametrize("n,m,d", LINEAR_PER_WORKER)
+def test_linear_per_worker_persistent(n, m, d, monkeypatch):
+    monkeypatch.setenv("GADMM_BLOCKED", "0")
+    out, kern = run_linear_persistent(n, m, d, "per-worker")
+    assert kern == "per-worker"
+    _report("linear per-worker %s" % ((n, m, d),), out)
+
+
+def test_linear_persistent_not_eligible_above_128():
+    eng = _linear_engine(3, 150, 129)
+    assert not eng.persistent_eligible() and eng.blocked_plan() is None
+    eng.close()
+
+
+# blocked kernel: gadmm_chain_blocked_plan2 (chain_blocked.hip) returns no plan at d > 52; the launcher
+# takes chain_blocked_kernel<32> at d <= 32 and <52> at 33..52 (gadmm_chain_blocked_pad_dim), and
+# chain_blocked_pair_kernel<DB> under GADMM_BLOCK_PW=2.
+LINEAR_BLOCKED = [
+    (2, 3, 1, 1), (3, 7, 3, 1),
+    (5, 40, 32, 1),  # DB = 32: the top
+    (4, 40, 33, 1),  # DB = 52: the first
+    (5, 60, 52, 1),  # DB = 52: the top
+    (5, 60, 52, 2),  # DB = 52, a head + tail pair per wave
+]
+
+
+@pytest.mark.parametrize("n,m,d,pw", LINEAR_BLOCKED)
+def test_linear_blocked_persistent(n, m, d, pw, monkeypatch):
+    monkeypatch.delenv("GADMM_BLOCKED", raising=False)
+    if pw != 1:
+        monkeypatch.setenv("GADMM_BLOCK_PW", str(pw))
+    out, kern = run_linear_persistent(n, m, d, "blocked(")
+    assert ("pw=%d" % pw) in kern, kern
+    _report("linear blocked pw=%d %s" % (pw, (n, m, d)), out)
+
+
+def test_blocked_kernel_stops_at_52(monkeypatch):
+    monkeypatch.delenv("GADMM_BLOCKED", raising=False)
+    eng = _linear_engine(5, 70, 53)
+    assert eng.blocked_plan() is None and eng.persistent_eligible()
+    eng.close()
+
+
+# D-GADMM on the per-worker kernel's dynamic mode (GADMM_BLOCKED_DYN=0): pick_variant's `dyn` branch,
+# register kernel with both degree variants resident (NV = 2), QT = 13 at d <= 52 and 16 at 53..64
+@pytest.mark.parametrize("n,m,d", [(5, 60, 52), (5, 70, 53)])
+def test_dgadmm_per_worker_dynamic(n, m, d, monkeypatch):
+    """Coherence 3 for K iterations against the float64 oracle (oracle.reference.dgadmm_linear, fed the
+    chains tests/test_gpu_dyn_sweep.py feeds it: find_path2 drawn from the schedule's seed). float64
+    against float64; the bound is the static chain's of the same shape (the long-double helper does not
+    re-chain). The kernel stops ``lag`` iterations after the cap and re-chains at none of them."""
+    from gadmm_amd.algorithms import dynamic_group_admm
+    from gadmm_amd.models import LinearRegression
+    from gadmm_amd.oracle import reference as R
+    from gadmm_amd.parallel import topology as T
+    monkeypatch.setenv("GADMM_BLOCKED_DYN", "0")
+    X, y, rho, _ = H.linear_case(n, m, d)
+    model = LinearRegression(_dev(X), _dev(y))
+    p0, c0, _ = T.find_path(n, np.random.default_rng(5))
+    a = dynamic_group_admm(model, rho, 0.0, 0.0, K, p0, c0, 3, seed=99, engine_opts={"cache": False})
+    eng = a.extra["engine_obj"]
+    assert a.extra["engine"] == "persistent-dynamic" and eng.last_kernel == "per-worker", (a.extra["engine"],
+                                                                                            eng.last_kernel)
+    theta, mu, nxt = a.extra["state"]
+    last = nxt - 1
+    assert a.iters == K and len(a.obj) == K and K <= last <= K + 16, (a.iters, last)
+    rng = np.random.default_rng(99)
+    seq = {}
+    cur = [(list(p0), c0)]
+
+    def rechain(it):
+        if it > K:  # the solve draws no chain past its cap
+            return cur[0]
+        if it not in seq:
+            p, c, _, _, _ = T.find_path2(n, rng)
+            seq[it] = cur[0] = (p, c)
+        return seq[it]
+
+    o = R.dgadmm_linear(X, y, rho, last, 0.0, 0.0, p0, c0, 3, rechain)
+    assert len(seq) == len([it for it in range(2, K + 1) if it % 3 == 0])
+    ref = H.linear_case(n, m, d, last)[3]
+    sc = float(np.max(np.abs(o.theta)))
+    out = {"objective": H.noise_level(np.asarray(o.obj[:K]), a.obj, np.abs(o.obj[:K])) / ref.b_obj,
+           "theta": H.noise_level(o.theta, _host(theta), sc) / ref.b_theta,
+           "dual": H.noise_level(o.dual, _host(mu), rho * sc) / ref.b_dual}
+    eng.close()
+    _report("D-GADMM per-worker dynamic %s" % ((n, m, d),), out)
+
+
+# ------------------------------------------------------------------------------------------------
+# Logistic, inner gradient descent: max_inner = 6, inner_tol = 0 (every local solve takes 6 steps)
+def _logistic_engine(n, m, d, inner_tol=0.0):
+    from gadmm_amd.engine.chain_engine import NativeChainEngine
+    from gadmm_amd.parallel.topology import Placement
+    X, y, rho, lam, step, _ = H.logistic_case(n, m, d, inner_tol=inner_tol)
+    eng = NativeChainEngine(_dev(X), _dev(y), list(range(n)), n, "logistic", rho=rho, obj0=0.0, tol=0.0, max_iter=K,
+                            lam=lam, step=step, max_inner=H.MAX_INNER, inner_tol=inner_tol, block=BLOCK)
+    eng.set_path(list(range(n)), Placement.contiguous(n, 1), 0)
+    eng.reset()
+    return eng
+
+
+def run_logistic_graph(n, m, d, inner_tol=0.0):
+    ref = H.logistic_case(n, m, d, inner_tol=inner_tol)[5]
+    eng = _logistic_engine(n, m, d, inner_tol)
+    r = eng.run(stop_iter=K)
+    assert r.iters == K and eng.graph_ok() and eng.ctl_state()["iter"] == K + 1, (r.iters, r.done)
+    assert r.replays == K // BLOCK
+    inner = _host(eng.inner_iters)[:n]
+    assert np.array_equal(inner, ref.extra[0][K - 1]), (inner, ref.extra[0][K - 1])
+    out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
+    out.update(_state_ratios(eng, ref, K))
+    eng.close()
+    return out
+
+
+def run_logistic_persistent(n, m, d):
+    eng = _logistic_engine(n, m, d)
+    assert eng.persistent_eligible()
+    r = eng.run_persistent()
+    assert eng.last_kernel == "per-worker-logistic", eng.last_kernel
+    last = eng.ctl_state()["iter"] - 1
+    assert r.iters == K and K <= last <= K + 16, (r.iters, r.done, last)
+    ref = H.logistic_case(n, m, d, last)[5]
+    assert np.all(_host(eng.inner_iters)[:n] == H.MAX_INNER)
+    out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
+    out.update(_state_ratios(eng, ref, last))
+    eng.close()
+    return out
+
+
+# gadmm_chain_phase (chain_small.hip), logistic branch: ldsx = m d <= 8192 && m <= 256; under ldsx,
+# dm = max(d, m) <= 64 takes chain_phase_logistic_quad<8> (dm <= 32), <13> (<= 52), <16> (<= 64), a
+# larger dm chain_phase_logistic_wave<cmax>, cmax = max(ceil(d / 64), ceil(m / 64)) -> 1 / 2 / 4;
+# without ldsx, chain_phase_logistic<1, 4, false> at d <= 64 and <4, 4, false> above.
+LOGISTIC_GRAPH = [
+    (3, 5, 3),       # quad<8>
+    (4, 30, 20),     # quad<8>
+    (3, 40, 52),     # quad<13> through d
+    (3, 52, 20),     # quad<13> through m
+    (3, 40, 53),     # quad<16>: the first
+    (3, 64, 64),     # quad<16>: the top, full register rows
+    (3, 100, 20),    # wave<2> through mc = 2
+    (2, 60, 128),    # wave<2> through nc = 2 (m d = 7680)
+    (3, 200, 30),    # wave<4> (mc = 4)
+    (3, 250, 40),    # non-LDSX <1, 4> (m d = 10000)
+    (3, 100, 100),   # non-LDSX <4, 4>
+]
+assert LOGISTIC_GRAPH == H.LOGISTIC_SHAPES
+
+
+@pytest.mark.parametrize("n,m,d", LOGISTIC_GRAPH)
+def test_logistic_graph_engine(n, m, d):
+    _report("logistic graph %s" % ((n, m, d),), run_logistic_graph(n, m, d))
+
+
+def test_logistic_live_stop_rule():
+    """(4, 30, 20) with inner_tol = 1e-3: the inner solves of the last iterations stop early, each at
+    the reference's step (tests/test_hp_reference_cpu.py holds every stop test 1e-6 off its threshold)."""
+    (n, m, d), tol = H.LIVE_STOP
+    ref = H.logistic_case(n, m, d, inner_tol=tol)[5]
+    assert ref.extra[0][K - 1].min() < H.MAX_INNER
+    _report("logistic graph live stop %s" % ((n, m, d),), run_logistic_graph(n, m, d, inner_tol=tol))
+
+
+# logi_variant (chain_persistent_logistic.hip): mx = max(d, m) <= 64 only; QT = 13 at mx <= 52, 16
+# above; GADMM_LOGISTIC_ZREC=0 the one-wave kernel, otherwise (default) the margins-recursion kernel
+LOGISTIC_PERSISTENT = [
+    (3, 5, 3), (4, 30, 20),
+    (3, 40, 52),     # QT = 13: the top, through d
+    (3, 52, 20),     # QT = 13: the top, through m
+    (3, 40, 53),     # QT = 16: the first
+    (3, 64, 64),     # QT = 16: the top
+]
+
+
+@pytest.mark.parametrize("zrec", ["0", "1"])
+@pytest.mark.parametrize("n,m,d", LOGISTIC_PERSISTENT)
+def test_logistic_persistent_kernel(n, m, d, zrec, monkeypatch):
+    monkeypatch.setenv("GADMM_LOGISTIC_ZREC", zrec)
+    _report("logistic persistent zrec=%s %s" % (zrec, (n, m, d)), run_logistic_persistent(n, m, d))
+
+
+# ------------------------------------------------------------------------------------------------
+# Star ADMM: star_variant (star_persistent.hip) takes QT = 13 at d <= 52 and 16 at 53..64;
+# standard_admm (algorithms/std_admm.py) sends d > 64 to the streaming engine (star_big.hip)
+STAR_PERSISTENT = [
+    (3, 7, 3),
+    (4, 60, 52),     # QT = 13: the top
+    (4, 70, 53),     # QT = 16: the first
+    (3, 40, 64),     # QT = 16: the top; m < d
+]
+assert STAR_PERSISTENT + [(3, 80, 65)] == H.STAR_SHAPES
+
+
+def run_star_persistent(n, m, d):
+    from gadmm_amd.engine.star_engine import StarEngine
+    X, y, rho, _ = H.star_case(n, m, d)
+    eng = StarEngine(_dev(X), _dev(y), list(range(n)), n, rho, 0.0, 0.0, K)
+    assert eng.eligible() and eng.last_kernel == "star-persistent"
+    iters, done, _ = eng.run()
+    last = int(eng.ctl.cpu()[0]) - 1  # the workers leave `lag` iterations after the cap's decision
+    assert iters == K and K <= last <= K + 16, (iters, done, last)
+    ref = H.star_case(n, m, d, last)[3]
+    lam_hub = _host(eng.lam_hub)[: n - 1]  # the hub's copies: updated through iteration `last`
+    # a worker's own dual is lazy: the update of iteration `last` would come with the next broadcast
+    th_l, rho_l = ref.theta[last - 1], np.asarray(rho, dtype=H.LD)
+    lam_prev = ref.dual[: n - 1] - rho_l * (th_l[: n - 1] - th_l[n - 1])
+    out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj,
+           "theta": ref.err_theta(_host(eng.theta), last) / ref.b_theta,
+           "dual": ref.err_dual(lam_hub, ref.dual[: n - 1]) / ref.b_dual,
+           "worker_dual": ref.err_dual(_host(eng.lam)[: n - 1], lam_prev) / ref.b_dual}
+    assert np.all(_host(eng.lam)[n - 1] == 0)
+    return out
+
+
+@pytest.mark.parametrize("n,m,d", STAR_PERSISTENT)
+def test_star_persistent_kernel(n, m, d):
+    _report("star persistent %s" % ((n, m, d),), run_star_persistent(n, m, d))
+
+
+@pytest.mark.parametrize("exact", [False, True])
+def test_star_big_first_shape(exact):
+    """(3, 80, 65): the first d of the streaming star engine, with its default objective (the identity
+    A th = r - shift th of the solve) and with the exact one (a second GEMV by the Gram)."""
+    from gadmm_amd.algorithms import standard_admm
+    from gadmm_amd.models import LinearRegression
+    n, m, d = 3, 80, 65
+    X, y, rho, ref = H.star_case(n, m, d)
+    model = LinearRegression(_dev(X), _dev(y))
+    a = standard_admm(model, list(range(n)), n, rho, 0.0, 0.0, K, engine_opts={"exact_objective": exact})
+    assert a.extra["backend"] == "native" and a.extra["engine"].startswith("star-big"), a.extra
+    assert a.extra["engine"] == "star-big(%s objective)" % ("exact" if exact else "identity")
+    eng = a.extra["engine_obj"]
+    assert a.iters == K and len(a.obj) == K
+    out = {"objective": ref.err_obj(a.obj) / ref.b_obj,
+           "theta": ref.err_theta(_host(eng.theta), K) / ref.b_theta,
+           "dual": ref.err_dual(_host(eng.lam)) / ref.b_dual}
+    _report("star-big %s %s" % ("exact" if exact else "identity", (n, m, d)), out)
+
+
+# ------------------------------------------------------------------------------------------------
+# Variants behind switches that are read once per process (static const in the launchers):
+# GADMM_PERSIST_LDS takes pick_variant's LDS kernel with NC = 1 at d <= 64, GADMM_LOGISTIC_QUAD=0
+# takes chain_phase_logistic_wave<1> at max(d, m) <= 64. monkeypatch cannot reach them.
+ONCE_LINEAR = [(3, 7, 3), (5, 70, 53), (4, 40, 64)]
+ONCE_LOGISTIC = [(3, 5, 3), (3, 64, 64)]
+
+
+def child_main():
+    """Runs in the fresh child process of test_variants_read_once_per_process: one JSON line."""
+    from gadmm_amd.ops import native
+    assert os.environ.get("GADMM_PERSIST_LDS") and os.environ.get("GADMM_LOGISTIC_QUAD") == "0"
+    os.environ["GADMM_BLOCKED"] = "0"
+    res = {}
+    for s in ONCE_LINEAR:
+        native.poison_lds()
+        out, kern = run_linear_persistent(*s, "per-worker")
+        res["linear per-worker LDS NC=1 %s" % (s,)] = out
+    for s in ONCE_LOGISTIC:
+        native.poison_lds()
+        res["logistic graph wave<1> %s" % (s,)] = run_logistic_graph(*s)
+    print("RATIOS " + json.dumps(res), flush=True)
+
+
+def test_variants_read_once_per_process():
+    env = dict(os.environ, GADMM_PERSIST_LDS="1", GADMM_LOGISTIC_QUAD="0",
+               PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    p = subprocess.run([sys.executable, "-c", "import test_gpu_dispatch_classes as t; t.child_main()"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-3000:])
+    line = [l for l in p.stdout.splitlines() if l.startswith("RATIOS ")][-1]
+    res = json.loads(line[len("RATIOS "):])
+    assert len(res) == len(ONCE_LINEAR) + len(ONCE_LOGISTIC)
+    for tag, ratios in res.items():
+        _report(tag, ratios)

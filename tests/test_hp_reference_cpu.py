@@ -1,0 +1,138 @@
+"""CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py.
+
+The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
+(gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
+kernel stands there, held to the same bound ``8 * max(e64, max(d, m, 16) * 2^-53)``."""
+import numpy as np
+import pytest
+
+import hp_reference as H
+from gadmm_amd.oracle import reference as R
+
+K = H.K_ITERS
+
+
+def _check(tag, ref, theta, dual, obj):
+    rt, rd, ro = ref.err_theta(theta) / ref.b_theta, ref.err_dual(dual) / ref.b_dual, ref.err_obj(obj) / ref.b_obj
+    print("%s: err/bound theta %.3f dual %.3f objective %.3f (e64 %.2e %.2e %.2e)"
+          % (tag, rt, rd, ro, ref.e_theta, ref.e_dual, ref.e_obj))
+    assert rt <= 1.0 and rd <= 1.0 and ro <= 1.0, (tag, rt, rd, ro)
+
+
+def _oracle_logistic(monkeypatch, X, y, rho, lam, step, iters, max_inner, inner_tol):
+    """The oracle's own GADMM loop and inner solver, with the inner solver's cap and tolerance (its
+    ``gadmm_logistic_gd`` does not forward them) set to the case's."""
+    inner = R.logreg_gd
+    monkeypatch.setattr(R, "logreg_gd", lambda *a: inner(*a, max_inner=max_inner, tol=inner_tol))
+    return R.gadmm_logistic_gd(X, y, rho, iters, 0.0, lam, 0.0, step)
+
+
+@pytest.mark.parametrize("n,m,d", H.LINEAR_SHAPES)
+def test_gadmm_linear_reproduces_oracle(n, m, d):
+    X, y, rho, ref = H.linear_case(n, m, d)
+    o = R.gadmm_linear(X, y, rho, K, 0.0, 0.0)
+    assert o.iters == K and len(o.obj) == K
+    _check("linear %s" % ((n, m, d),), ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+    # the per-worker form of the oracle (no re-chaining) is the same recurrence
+    o2 = R.dgadmm_linear(X, y, rho, K, 0.0, 0.0, list(range(n)), np.zeros(max(n - 1, 0)), 0)
+    _check("linear (per-worker duals) %s" % ((n, m, d),), ref, o2.theta, o2.dual, o2.obj)
+
+
+@pytest.mark.parametrize("n,m,d", H.STAR_SHAPES)
+def test_star_admm_reproduces_oracle(n, m, d):
+    X, y, rho, ref = H.star_case(n, m, d)
+    o = R.std_admm_linear(X, y, rho, K, 0.0, 0.0)
+    assert np.all(ref.dual[n - 1] == 0)
+    _check("star %s" % ((n, m, d),), ref, o.theta, o.dual, o.obj)
+
+
+@pytest.mark.parametrize("n,m,d", H.LOGISTIC_SHAPES)
+def test_gadmm_logistic_reproduces_oracle(n, m, d, monkeypatch):
+    X, y, rho, lam, step, ref = H.logistic_case(n, m, d)
+    inner, margin = ref.extra
+    assert np.all(inner == H.MAX_INNER) and margin == np.inf  # inner_tol = 0: no test can pass
+    o = _oracle_logistic(monkeypatch, X, y, rho, lam, step, K, H.MAX_INNER, 0.0)
+    _check("logistic %s" % ((n, m, d),), ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+
+
+def test_logistic_live_stop_margin(monkeypatch):
+    """Every logistic case with ``inner_tol > 0``: no stop test of the long-double run comes within
+    1e-6 (relative) of its threshold, so a correct float64 kernel takes the same decisions. A seed that
+    fails this is replaced, the margin is not loosened."""
+    (n, m, d), tol = H.LIVE_STOP
+    X, y, rho, lam, step, ref = H.logistic_case(n, m, d, inner_tol=tol)
+    inner, margin = ref.extra
+    print("live stop %s: margin %.3e, inner steps of the last iteration %s" % ((n, m, d), margin, inner[-1]))
+    assert margin > 1e-6
+    assert inner.min() < H.MAX_INNER and inner.max() == H.MAX_INNER  # the rule is live, and so is the cap
+    f64 = H.gadmm_logistic_gd(X, y, rho, lam, step, K, H.MAX_INNER, tol, np.float64)
+    assert np.array_equal(f64[3], inner)
+    o = _oracle_logistic(monkeypatch, X, y, rho, lam, step, K, H.MAX_INNER, tol)
+    _check("logistic live stop", ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+
+
+def test_fixtures_reproduce_oracle(lin24, log24):
+    """The suite's own fixtures (N = 24, m = d = 50), 30 iterations, the oracle's default inner solver
+    (100 steps, 1e-4)."""
+    X, y = lin24.numpy()
+    rho = 5.0
+    ref = H.Reference(H.gadmm_linear(X, y, rho, 30, H.LD), H.gadmm_linear(X, y, rho, 30, np.float64), rho, 50)
+    o = R.gadmm_linear(X, y, rho, 30, 0.0, 0.0)
+    _check("lin24", ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+    ref = H.Reference(H.star_admm_linear(X, y, 1.0, 30, H.LD), H.star_admm_linear(X, y, 1.0, 30, np.float64), 1.0, 50)
+    o = R.std_admm_linear(X, y, 1.0, 30, 0.0, 0.0)
+    _check("lin24 star", ref, o.theta, o.dual, o.obj)
+    X, y = log24.numpy()
+    args = (X, y, 2e-4, 1e-5, 2.2, 30, 100, 1e-4)
+    ld, f64 = H.gadmm_logistic_gd(*args, H.LD), H.gadmm_logistic_gd(*args, np.float64)
+    ref = H.Reference(ld, f64, 2e-4, 50, 50)
+    assert ld[4] > 1e-6 and np.array_equal(ld[3], f64[3])
+    o = R.gadmm_logistic_gd(X, y, 2e-4, 30, 0.0, 1e-5, 0.0, 2.2)
+    _check("log24", ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+
+
+@pytest.mark.parametrize("d", [1, 64, 256])
+def test_newton_schulz_inverse(d):
+    rng = np.random.default_rng(d)
+    Z = rng.standard_normal((2 * d, d))
+    M = (Z.T @ Z + 0.5 * d * np.eye(d)).astype(H.LD)
+    Xi = H.spd_inverse(M, H.LD)
+    assert Xi.dtype == H.LD
+    resid = float(np.max(np.abs(np.eye(d, dtype=H.LD) - M @ Xi)))
+    print("d=%d: |I - M X|_max = %.3e (bound %.3e)" % (d, resid, d * 2.0 ** -60))
+    assert resid <= d * 2.0 ** -60
+    assert H.spd_inverse(M.astype(np.float64), np.float64).dtype == np.float64
+
+
+def test_dtypes_and_noise_level():
+    X, y, rho = H.make_linear(3, 7, 3, 1)
+    for fn in (H.gadmm_linear, H.star_admm_linear):
+        for dt in (np.float64, H.LD):
+            th, du, ob = fn(X, y, rho, 3, dt)
+            assert th.dtype == du.dtype == ob.dtype == np.dtype(dt) and th.shape == (3, 3, 3)
+    X, y, rho, lam, step = H.make_logistic(3, 5, 3, 1)
+    assert set(np.unique(y)) <= {-1.0, 1.0} and lam == 1e-3 and abs(rho * step - 0.1) < 1e-15
+    th, du, ob, inner, margin = H.gadmm_logistic_gd(X, y, rho, lam, step, 2, 4, 0.0, H.LD)
+    assert th.dtype == H.LD and inner.shape == (2, 3) and np.all(inner == 4) and margin == np.inf
+    assert H.noise_level(np.array([1.0, 2.0]), np.array([1.0, 2.5]), 2.0) == 0.25
+    assert H.noise_level(np.array([1.0, 2.0]), np.array([1.5, 2.5]), np.array([1.0, 2.0])) == 0.5
+    assert H.bound(0.0, 3) == 8 * 16 * 2.0 ** -53 and H.bound(0.0, 40, 250) == 8 * 250 * 2.0 ** -53
+    assert H.bound(1e-15, 257) == 8 * 257 * 2.0 ** -53 and H.bound(1e-13, 257) == 8e-13
+
+
+@pytest.mark.parametrize("n,m,d", [(2, 3, 1), (5, 60, 52), (3, 280, 257)])
+def test_bound_catches_what_a_wrong_kernel_does(n, m, d):
+    """The bound is far below anything an indexing or tail mistake produces: one theta coordinate off
+    by 1e-11 relative (the suite's older rtol), or a solve whose last shard column of one worker is
+    wrong in the ninth digit, both land above it in every quantity; the float64 run of the recurrence
+    itself, a correct implementation by construction, lands below."""
+    X, y, rho, ref = H.linear_case(n, m, d)
+    th64, mu64, ob64 = H.gadmm_linear(X, y, rho, K, np.float64)
+    assert ref.err_theta(th64[-1]) <= ref.b_theta / 8 and ref.err_obj(ob64) <= ref.b_obj / 8
+    off = np.array(th64[-1])
+    off[0, d - 1] += 1e-11 * ref.scale_theta
+    assert ref.err_theta(off) > ref.b_theta
+    Xb = np.array(X)
+    Xb[0, :, d - 1] *= 1.0 + 1e-9  # the last column of worker 0's shard, nine digits in
+    thb, mub, obb = H.gadmm_linear(Xb, y, rho, K, np.float64)
+    assert ref.err_theta(thb[-1]) > ref.b_theta and ref.err_dual(mub) > ref.b_dual and ref.err_obj(obb) > ref.b_obj
