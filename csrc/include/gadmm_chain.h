@@ -85,6 +85,15 @@ struct PhaseArgs {
   // optional K4 primal residual: every tail writes ||th_l - th||^2 + ||th - th_r||^2 of iteration it
   // (its two chain edges; each edge has exactly one tail end) into rres[(it - 1) * n_total + gid]
   double* rres;        // [max_iter][n_total] or null
+  // Q-GADMM (csrc/kernels/chain_quant.hip, q_bits > 0): the theta table holds the PUBLIC models
+  // th_hat; a worker quantizes the difference of its solve to its own row at q_bits per coordinate
+  // (quant_device.h) and stores the updated th_hat. Optional outputs: the true iterates of the local
+  // workers and the messages as they would travel, [n_total][1 + words]: the bits of R, then the
+  // packed code words. q_bits = 0 (a zeroed PhaseArgs): off, every kernel as without these fields.
+  double* q_true;               // [n_local][d] or null
+  unsigned long long* q_msg;    // [n_total][1 + ceil(d * q_bits / 64)] or null
+  int q_bits;
+  unsigned long long q_seed;
 };
 
 // Engine construction arguments (Python mirrors it in gadmm_amd/ops/native.py).
@@ -202,5 +211,12 @@ struct PersistArgs {
   // with them at the re-chain), as int pairs [n_epochs][n][2]. Built on the host, so a re-chain
   // issues two independent table loads instead of a chain of three dependent ones.
   const int* ep_flush;
+  // Q-GADMM in one launch (csrc/kernels/chain_quant.hip: chain_persistent_q_kernel). qg: the packed
+  // hand-off table, [n][G] tagged granules with G = ceil(d * q_bits / 64) + 1: granule 0 carries the
+  // bits of R, granule 1 + k code word k. q_true: the true iterates at the end of the launch.
+  u32x4* qg;
+  double* q_true;           // [n_local][d] or null
+  int q_bits;
+  unsigned long long q_seed;
 };
 constexpr int XCHK = 256;  // placement-check granules (>= workgroups of any XCD-packed launch)

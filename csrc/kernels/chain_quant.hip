@@ -1,0 +1,594 @@
+// Q-GADMM (Elgabli et al., arXiv:1910.10453) on the chain engine: quantized neighbour exchange.
+//
+// Every worker n has a public model th_hat_n that its chain neighbours hold an identical copy of.
+// After its solve the worker sends the stochastically quantized difference theta_n - th_hat_n at
+// q_bits per coordinate, as (R, codes), and sender and receivers move th_hat_n by the same
+// dequantized step (quant_device.h; the specification is gadmm_amd/algorithms/quantize.py). A
+// closed-form GADMM solve never reads the worker's own previous theta, so the algorithm is GADMM
+// whose theta table holds th_hat: rhs and duals read th_hat of the neighbours (and of the worker
+// itself for the duals), the objective and the stop rule read the true theta.
+//
+// Two kernels, the same arithmetic in the same order (bit-identical iterates, as the unquantized
+// engines: symv_cols / quad_gemv sum in one order):
+//   chain_phase_linear_q     one GADMM phase of the graph engine, d <= 256 (body of chain_phase_linear
+//                            + the quantize stage): th_hat goes into the theta table.
+//   chain_persistent_q_kernel  the whole solve in one launch, d <= 64, one wave per worker, static
+//                            chain, one GPU: the hand-off is the packed message itself.
+#define GADMM_POLL_SLEEP 0  // one hand-off wait per phase on the critical path: poll back to back
+#include <stdlib.h>
+#include <cstddef>
+#include "gadmm_common.h"
+#include "gadmm_chain.h"
+#include "chain_device.h"
+#include "persist_device.h"
+#include "quad_gemv.h"
+#include "quant_device.h"
+
+using namespace quant;
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int NW = NT / 64;
+
+// out[i] = sum_j M[j*d + i] * x[j]  (M symmetric), for i < d. x, out in LDS; red: NW*64*NC.
+// The summation order of chain_small.hip's symv_cols (wave k of 4 sums j = k mod 4 ascending, the
+// partials added in wave order), which quad_gemv reproduces in registers.
+template <int NC>
+__device__ __forceinline__ void symv_cols_q(const double* __restrict__ M, const double* x, double* out,
+                                            double* red, int d) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  int j = w;
+  for (; j + NW < d; j += 2 * NW) {
+    const double x0 = x[j], x1 = x[j + NW];
+    const double* r0 = M + (long)j * d;
+    const double* r1 = M + (long)(j + NW) * d;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (i < d) acc[c] = fma(r1[i], x1, fma(r0[i], x0, acc[c]));
+    }
+  }
+  for (; j < d; j += NW) {
+    const double x0 = x[j];
+    const double* r0 = M + (long)j * d;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int i = lane + 64 * c;
+      if (i < d) acc[c] = fma(r0[i], x0, acc[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) red[w * 64 * NC + c * 64 + lane] = acc[c];
+  __syncthreads();
+  for (int i = threadIdx.x; i < d; i += NT) {
+    const int c = i >> 6, l = i & 63;
+    double s = 0.0;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) s += red[ww * 64 * NC + c * 64 + l];
+    out[i] = s;
+  }
+  __syncthreads();
+}
+
+// A 64-bit value of another lane of the same 16-lane row through DPP (no LDS round trip, unlike
+// __shfl_xor's ds_bpermute): 0xB1 / 0x4E = quad_perm [1,0,3,2] / [2,3,0,1], 0x141 = row_half_mirror,
+// 0x140 = row_mirror. Applied in that order to a SYMMETRIC reduction (max, or) every lane of a group of
+// 2, 4, 8, 16 lanes ends with the group's result.
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, false);
+  return ((unsigned long long)hi << 32) | lo;
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  return __longlong_as_double((long long)dpp_u64<CTRL>((unsigned long long)__double_as_longlong(v)));
+}
+
+// max is exact, associative and commutative: any reduction order gives the same bits. Four DPP steps
+// inside the rows, then the rows meet through the permlane swaps of quad_gemv.h.
+__device__ __forceinline__ double wave_max_f64(double v) {
+  v = fmax(v, dpp_f64<0xB1>(v));
+  v = fmax(v, dpp_f64<0x4E>(v));
+  v = fmax(v, dpp_f64<0x141>(v));
+  v = fmax(v, dpp_f64<0x140>(v));
+  double a = v, b = v;
+  swap16_f64(a, b);  // rows (r0, r1, r2, r3) -> a = (r0, r0, r2, r2), b = (r1, r1, r3, r3)
+  v = fmax(a, b);
+  a = v;
+  b = v;
+  swap32_f64(a, b);  // a = (m01 x 4), b = (m23 x 4)
+  return fmax(a, b);
+}
+
+// OR over each aligned group of 2^lp lanes (lp in {2, 3, 4}), the result in every lane of the group
+__device__ __forceinline__ unsigned long long group_or_u64(unsigned long long v, int lp) {
+  v |= dpp_u64<0xB1>(v);
+  v |= dpp_u64<0x4E>(v);
+  if (lp >= 3) v |= dpp_u64<0x141>(v);
+  if (lp >= 4) v |= dpp_u64<0x140>(v);
+  return v;
+}
+
+__device__ __forceinline__ double block_max_f64(double v, double* scratch) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  v = wave_max_f64(v);
+  __syncthreads();
+  if (lane == 0) scratch[wid] = v;
+  __syncthreads();
+  double t = scratch[0];
+  for (int i = 1; i < nw; ++i) t = fmax(t, scratch[i]);
+  return t;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// Graph engine: one GADMM phase with quantized publication.
+template <int NC>
+__global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
+  __shared__ __attribute__((aligned(16))) double sh_r[64 * NC];
+  __shared__ __attribute__((aligned(16))) double sh_t[64 * NC];  // the true theta of this solve
+  __shared__ __attribute__((aligned(16))) double sh_q[64 * NC];
+  __shared__ __attribute__((aligned(16))) double sh_h[64 * NC];  // the new public model th_hat
+  __shared__ __attribute__((aligned(16))) double red[NW * 64 * NC];
+  __shared__ unsigned sh_c[64 * NC];                             // the codes
+  __shared__ double scratch[NW];
+  __shared__ int flag_lds;
+  ChainCtl* ctl = a.ctl;
+  if (ctl->done) return;
+  const int it = ctl->iter;
+  const int pending = ctl->pending;
+  const PhaseSlot sl = a.slots[blockIdx.x];
+  const int d = a.d;
+  const double rho = a.rho;
+  double* th = a.theta;  // rows are th_hat
+  const double* thw = th + (long)sl.gid * d;
+  const double* thl = sl.left >= 0 ? th + (long)sl.left * d : nullptr;
+  const double* thr = sl.right >= 0 ? th + (long)sl.right * d : nullptr;
+  double* mu = a.mu + (long)sl.li * d;
+  const double* b = a.b + (long)sl.li * d;
+  const int deg = (thl != nullptr) + (thr != nullptr);
+
+  for (int j = threadIdx.x; j < d; j += NT) {
+    double m = mu[j];
+    if ((a.flags & PH_PRE_DUAL) && pending) {
+      if (thl) m = m - rho * (thl[j] - thw[j]);
+      if (thr) m = m + rho * (thw[j] - thr[j]);
+      mu[j] = m;
+    }
+    double r = b[j] - m;
+    if (thl) r = r + rho * thl[j];
+    if (thr) r = r + rho * thr[j];
+    sh_r[j] = r;
+  }
+  __syncthreads();
+  const double* Mi = a.Minv + ((long)sl.li * a.nvar + a.deg_to_var[deg]) * (long)d * d;
+  symv_cols_q<NC>(Mi, sh_r, sh_t, red, d);
+
+  // -- quantize stage: R = max |theta - th_hat|, then per coordinate draw, code and th_hat update
+  const int bits = a.q_bits;
+  const double L = (double)((1u << bits) - 1u);
+  double dmax = 0.0;
+  for (int j = threadIdx.x; j < d; j += NT) dmax = fmax(dmax, fabs(sh_t[j] - thw[j]));
+  const double R = block_max_f64(dmax, scratch);
+  for (int j = threadIdx.x; j < d; j += NT) {
+    const double hat = thw[j];
+    const unsigned q = q_code(sh_t[j] - hat, R, L, q_u01(a.q_seed, it, a.n_total, sl.gid, d, j));
+    sh_c[j] = q;
+    sh_h[j] = q_apply(hat, R, L, q);
+  }
+  __syncthreads();
+  if (a.q_msg) {  // the message as it would travel: the bits of R, then 64 / bits codes per word
+    const int lp = q_log2_per(bits), nw = q_words(d, bits);
+    unsigned long long* msg = a.q_msg + (long)sl.gid * (nw + 1);
+    if (threadIdx.x == 0) msg[0] = (unsigned long long)__double_as_longlong(R);
+    for (int k = threadIdx.x; k < nw; k += NT) {
+      unsigned long long wv = 0ull;
+      for (int e = 0; e < (1 << lp); ++e) {
+        const int i = (k << lp) + e;
+        if (i < d) wv |= (unsigned long long)sh_c[i] << (bits * e);
+      }
+      msg[1 + k] = wv;
+    }
+  }
+  double* thw_out = th + (long)sl.gid * d;
+  double rpart = 0.0;
+  for (int j = threadIdx.x; j < d; j += NT) {
+    const double t = sh_h[j];
+    thw_out[j] = t;
+    if (a.q_true) a.q_true[(long)sl.li * d + j] = sh_t[j];
+    if (a.flags & PH_POST_DUAL) {
+      double m = mu[j];
+      if (thl) m = m - rho * (thl[j] - t);
+      if (thr) m = m + rho * (t - thr[j]);
+      mu[j] = m;
+      if (a.rres) {  // K4 primal residual of the tail's two edges (public models)
+        if (thl) rpart = fma(thl[j] - t, thl[j] - t, rpart);
+        if (thr) rpart = fma(t - thr[j], t - thr[j], rpart);
+      }
+    }
+  }
+  if (a.rres && (a.flags & PH_POST_DUAL)) {
+    const double rs = block_sum_f64(rpart, scratch);
+    if (threadIdx.x == 0 && it - 1 < a.max_iter) a.rres[(long)(it - 1) * a.n_total + sl.gid] = rs;
+    __syncthreads();  // scratch is reused by the objective's block sum
+  }
+  if (a.flags & PH_OBJ) {  // the objective of the TRUE theta, still in LDS
+    symv_cols_q<NC>(a.A + (long)sl.li * d * d, sh_t, sh_q, red, d);
+    double part = 0.0;
+    for (int j = threadIdx.x; j < d; j += NT) part += (0.5 * sh_q[j] - b[j]) * sh_t[j];
+    const double f = block_sum_f64(part, scratch) + 0.5 * a.yy[sl.li];
+    if (threadIdx.x == 0) a.objw[sl.li] = f;
+  }
+  if (a.flags & PH_FINISH) {
+    if (phase_arrive(ctl, a.n_slots, &flag_lds)) finish_iteration(a, it);
+  }
+}
+
+extern "C" int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st) {
+  const PhaseArgs& a = *args;
+  if (a.n_slots <= 0) return 0;
+  if (a.model != MODEL_LINEAR || a.d > 256 || a.d < 1) {
+    gadmm_set_error("chain_phase (quantized): the linear model with d <= 256 only (model %d, d=%d)", a.model, a.d);
+    return -1;
+  }
+  if (a.q_bits != 4 && a.q_bits != 8 && a.q_bits != 16) {
+    gadmm_set_error("chain_phase (quantized): q_bits must be 4, 8 or 16, got %d", a.q_bits);
+    return -1;
+  }
+  const int nc = (a.d + 63) / 64;
+  switch (nc) {
+    case 1: hipLaunchKernelGGL(chain_phase_linear_q<1>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(chain_phase_linear_q<2>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+    default: hipLaunchKernelGGL(chain_phase_linear_q<4>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+  }
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Persistent single-launch Q-GADMM: static chain, one GPU, d <= 64, one wave per worker (+ the
+// monitor workgroup). Schedule, lagged stop rule, deadlines (done = 4) and XCD packing are those of
+// chain_persistent_kernel (REG variant); inverse and Gram sit in VGPRs in the quad layout.
+//
+// Hand-off: worker w publishes iteration `it` as G = ceil(d bits / 64) + 1 tagged 16-byte granules
+// in row w of the message table qg: granule 0 the bits of R, granule 1 + k code word k (64 / bits
+// codes, coordinate i at bit bits (i mod 64/bits) of word i / (64/bits)). Payloads travel as raw bits.
+// A receiver keeps th_hat of both neighbours in registers: lane i loads granule 0 and the granule of
+// its code and applies q_apply, the function the sender applied to its own th_hat.
+//
+// The table has ONE slot per worker although a message is a DIFFERENCE that must be consumed exactly
+// once: with a static chain a producer cannot publish iteration it + 1 before it has read the
+// consumer's next message (a tail needs its heads' theta^{it+1}, a head its tails' theta^{it}), and a
+// consumer publishes that message only after it has left the wait in which it read -- and kept in
+// registers -- the producer's message `it`. The granules are applied once, after the wait (a poll
+// that sees one neighbour's message early reloads it unchanged).
+__device__ __forceinline__ void put_raw(bool local, __amdgpu_buffer_rsrc_t rs, int byte_off, unsigned tag,
+                                        unsigned long long bits) {
+  u32x4 g = {tag, (unsigned)(bits & 0xffffffffull), tag, (unsigned)(bits >> 32)};
+  if (local) __builtin_amdgcn_raw_buffer_store_b128(g, rs, byte_off, 0, 0);
+  else __builtin_amdgcn_raw_buffer_store_b128(g, rs, byte_off, 0, 16 /* sc1 */);
+}
+__device__ __forceinline__ unsigned long long raw_bits(const u32x4& g) {
+  return ((unsigned long long)g.w << 32) | g.y;
+}
+
+template <int QT>
+__global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  __shared__ int abort_lds;
+  __shared__ int stop_lds;
+  __shared__ int xcd_lds;
+  const int d = a.d, n = a.n;
+  const int lane = threadIdx.x;
+  const __amdgpu_buffer_rsrc_t rq = rsrc_of(a.qg);
+  const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
+  const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
+  const bool packed = a.xcd > 0;            // XCD packing (PersistArgs::xcd)
+  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
+  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  if (lane == 0) {
+    abort_lds = 0;
+    stop_lds = 0;
+  }
+  lds_barrier();
+  bool local = false;  // publish with plain stores (every block verified on this XCD)
+  if (a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + 1, deadline, &xcd_lds, (unsigned)a.xtag);
+  if (bid == 0 && lane == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
+
+  if (bid == a.n_local) {
+    // ---------------------------------------------------------------- monitor workgroup
+    double* vals = lds;  // [n]
+    for (int it = a.start_iter;; ++it) {
+      const unsigned tag = make_tag(a.epoch, it);
+      const int slot = it % a.ring;
+      for (int w = lane; w < n; w += 64) {
+        double v = 0.0;
+        for (;;) {
+          if (load_granule<false>(rob, (slot * n + w) * 16, tag, &v)) break;
+          if (now_ticks() > deadline) {
+            abort_lds = 1;
+            break;
+          }
+          GADMM_POLL_PAUSE();
+        }
+        vals[w] = v;
+      }
+      lds_barrier();
+      if (lane == 0) {
+        unsigned code = 0;
+        if (abort_lds) {
+          code = 4;
+        } else {
+          double s = 0.0;
+          for (int w = 0; w < n; ++w) s += vals[w];  // fixed order: deterministic, == the graph engine's finish
+          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
+          if (!(s == s) || isinf(s)) code = 3;
+          else if (fabs(s - a.obj0) < a.tol) code = 1;
+          else if (it >= a.max_iter) code = 2;
+          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
+        }
+        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
+        store_dec<false>(a.decg + slot, dv);
+        if (code) stop_lds = 1;
+      }
+      lds_barrier();
+      if (stop_lds) return;
+    }
+  }
+
+  // ------------------------------------------------------------------ worker workgroup (one wave)
+  const PhaseSlot sl = a.slots[bid];
+  const int pos = a.pos[bid];
+  const int li = sl.li, w = sl.gid;
+  const int left = sl.left, right = sl.right;
+  const bool head = (pos % 2) == 0;
+  const int deg = (left >= 0) + (right >= 0);
+  const double rho = a.rho;
+  const int bits = a.q_bits, lp = q_log2_per(bits);
+  const int G = q_words(d, bits) + 1;
+  const double L = (double)((1u << bits) - 1u);
+  const unsigned qmask = (1u << bits) - 1u;
+  const int my_g = 1 + (lane >> lp);                 // the granule that holds this lane's code
+  const int my_sh = bits * (lane & ((1 << lp) - 1));  // ... at this bit
+  const bool in = lane < d;
+  double* st = lds;  // quad GEMV staging (QSTAGE doubles)
+
+  double Mq[4][QT], Aq[4][QT];
+  quad_load<QT>(Mq, a.Minv + ((long)li * a.nvar + a.deg_to_var[deg]) * (long)d * d, d, true);
+  quad_load<QT>(Aq, a.A + (long)li * d * d, d, true);
+  // lane i owns coordinate i: the true theta, the worker's own public model and its copies of the
+  // neighbours' (the theta table holds public models)
+  double th = in ? a.theta[(long)w * d + lane] : 0.0;
+  double hat = th;
+  double mu = in ? a.mu[(long)li * d + lane] : 0.0;
+  const double bb = in ? a.b[(long)li * d + lane] : 0.0;
+  double hl = (in && left >= 0) ? a.theta[(long)left * d + lane] : 0.0;
+  double hr = (in && right >= 0) ? a.theta[(long)right * d + lane] : 0.0;
+  const double half_yy = 0.5 * a.yy[li];
+  int pending = (a.pending_in && head) ? 1 : 0;
+  int stop_code = 0, stop_iter = 0;
+  lds_barrier();
+
+  int it = a.start_iter;
+  int rs = a.start_iter % a.ring;
+  for (;; ++it, rs = rs + 1 == a.ring ? 0 : rs + 1) {
+    if (it > a.max_iter + a.lag) break;
+    const double u = q_u01(a.q_seed, it, n, w, d, lane);  // this iteration's draw: ready before the wait ends
+    // -- stop rule: the decision of iteration it - lag, polled in the same loop as the neighbours'
+    // messages; a stop decision abandons the wait (a neighbour that saw it publishes no more)
+    const bool check = it - a.start_iter >= a.lag;
+    const int jdec = it - a.lag;
+    const bool need_nb = head ? it > a.start_iter : true;
+    const int jnb = head ? it - 1 : it;
+    const unsigned tnb = make_tag(a.epoch, jnb);
+    const int ra = need_nb ? left : -1, rb = need_nb ? right : -1;
+    int dslot = rs - a.lag;  // == jdec % ring
+    if (dslot < 0) dslot += a.ring;
+    const unsigned tj = make_tag(a.epoch, jdec);
+    bool decided = !check;
+    unsigned long long dv = 0;
+    int outcome = 0;  // 1 go, 2 stop, 3 timeout
+    u32x4 gRa = {0u, 0u, 0u, 0u}, gWa = gRa, gRb = gRa, gWb = gRa;
+    for (int spin = 0;; ++spin) {
+      bool nb = true;
+      if (in) {
+        if (ra >= 0) {
+          gRa = load_raw<false>(rq, (ra * G) * 16);
+          gWa = load_raw<false>(rq, (ra * G + my_g) * 16);
+          nb &= granule_ok(gRa, tnb) && granule_ok(gWa, tnb);
+        }
+        if (rb >= 0) {
+          gRb = load_raw<false>(rq, (rb * G) * 16);
+          gWb = load_raw<false>(rq, (rb * G + my_g) * 16);
+          nb &= granule_ok(gRb, tnb) && granule_ok(gWb, tnb);
+        }
+      }
+      if (!decided) {
+        dv = __shfl(load_dec<false>(&a.decg[dslot]), 0, 64);
+        decided = (unsigned)(dv >> 32) == tj;
+      }
+      if (decided && (unsigned)(dv & 0xffffffffu) != 0u) { outcome = 2; break; }
+      if (decided && __all(nb)) { outcome = 1; break; }
+      if ((spin & 7) == 7 && now_ticks() > deadline) { outcome = 3; break; }
+      GADMM_POLL_PAUSE();
+    }
+    if (lane == 0) {
+      if (outcome == 3) abort_lds = 1;
+      if (outcome == 2) {
+        stop_lds = 1;
+        stop_code = (int)(unsigned)(dv & 0xffffffffu);
+        stop_iter = jdec;
+      }
+    }
+    lds_barrier();
+    if (abort_lds || stop_lds) break;
+    // -- the neighbours' messages, consumed once: their public models move by the dequantized step
+    if (in && ra >= 0)
+      hl = q_apply(hl, __longlong_as_double((long long)raw_bits(gRa)), L, (unsigned)(raw_bits(gWa) >> my_sh) & qmask);
+    if (in && rb >= 0)
+      hr = q_apply(hr, __longlong_as_double((long long)raw_bits(gRb)), L, (unsigned)(raw_bits(gWb) >> my_sh) & qmask);
+    if (head && pending) {  // lazy end-of-iteration dual (reference order), on public models
+      double m = mu;
+      if (left >= 0) m = m - rho * (hl - hat);
+      if (right >= 0) m = m + rho * (hat - hr);
+      mu = m;
+    }
+    double r = bb - mu;
+    if (left >= 0) r = r + rho * hl;
+    if (right >= 0) r = r + rho * hr;
+    const double rv = in ? r : 0.0;
+
+    // -- solve theta = (A + deg rho I)^{-1} r
+    const double tn = quad_gemv<QT>(Mq, rv, st);
+
+    // -- quantize theta - th_hat and publish the packed message
+    const double diff = in ? tn - hat : 0.0;
+    const double R = wave_max_f64(fabs(diff));
+    const unsigned q = in ? q_code(diff, R, L, u) : 0u;
+    const double hat_new = in ? q_apply(hat, R, L, q) : 0.0;
+    const unsigned long long word = group_or_u64((unsigned long long)q << my_sh, lp);  // the word of this lane's group
+    const unsigned tag = make_tag(a.epoch, it);
+    if (in && (lane & ((1 << lp) - 1)) == 0) put_raw(local, rq, (w * G + my_g) * 16, tag, word);
+    if (lane == 0) put_raw(local, rq, (w * G) * 16, tag, (unsigned long long)__double_as_longlong(R));
+    if (!head) {  // tails: both neighbours are this iteration's heads -> dual update now
+      double m = mu;
+      if (left >= 0) m = m - rho * (hl - hat_new);
+      if (right >= 0) m = m + rho * (hat_new - hr);
+      mu = m;
+      if (a.rres) {  // K4 primal residual of the tail's two edges (public models)
+        double rp = 0.0;
+        if (in && left >= 0) rp = fma(hl - hat_new, hl - hat_new, rp);
+        if (in && right >= 0) rp = fma(hat_new - hr, hat_new - hr, rp);
+        const double rsum = wave_sum_f64(rp);
+        if (lane == 0 && it - 1 < a.max_iter) a.rres[(long)(it - 1) * n + w] = rsum;
+      }
+    } else {
+      pending = 1;
+    }
+    // -- objective of the TRUE theta: 1/2 th^T A th - b^T th + 1/2 y^T y
+    const double qa = quad_gemv<QT>(Aq, in ? tn : 0.0, st);
+    const double part = in ? (0.5 * qa - bb) * tn : 0.0;
+    const double f = wave_sum_f64(part) + half_yy;
+    if (lane == 0) put_granule<false>(local, rob, (rs * n + w) * 16, tag, f);
+    th = tn;
+    hat = hat_new;
+  }
+
+  // write back the final state (plain stores; visible to the host after the kernel)
+  if (in) {
+    a.theta[(long)w * d + lane] = hat;
+    a.mu[(long)li * d + lane] = mu;
+    if (a.q_true) a.q_true[(long)li * d + lane] = th;
+  }
+  if (lane == 0) {
+    if (abort_lds) {
+      a.ctl->done = 4;
+    } else if (bid == 0 && stop_code) {
+      a.ctl->done = stop_code;
+      a.ctl->conv_iter = stop_iter;
+      a.ctl->iter = it;
+      a.ctl->pending = 1;
+      a.ctl->monitored = stop_iter;
+    }
+  }
+}
+
+extern "C" {
+
+long gadmm_resident_capacity(const void* fn, int threads, size_t shm);
+int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total);
+unsigned gadmm_next_xtag();
+
+}  // extern "C"
+
+namespace {
+
+struct QVariant {
+  const void* fn = nullptr;
+  size_t shm = 0;
+};
+
+QVariant pick_q_variant(const PersistArgs& a) {
+  QVariant v;
+  if (a.d < 1 || a.d > 64) return v;
+  // register kernel: QT = 13 covers d <= 52, 16 covers d <= 64 (as chain_persistent_kernel)
+  v.fn = a.d <= 52 ? (const void*)chain_persistent_q_kernel<13> : (const void*)chain_persistent_q_kernel<16>;
+  const size_t mon = (size_t)a.n * 8, stg = (size_t)QSTAGE * 8;
+  v.shm = mon > stg ? mon : stg;
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ABI self-description of the Q-GADMM fields appended to PhaseArgs / PersistArgs (ctypes mirrors in
+// gadmm_amd/ops/native.py; gadmm_abi_layout covers the rest of both structs).
+int gadmm_quant_abi_layout(long long* out, int n) {
+  long long v[] = {(long long)offsetof(PhaseArgs, q_true), (long long)offsetof(PhaseArgs, q_msg),
+                   (long long)offsetof(PhaseArgs, q_bits), (long long)offsetof(PhaseArgs, q_seed),
+                   (long long)sizeof(PhaseArgs),           (long long)offsetof(PersistArgs, qg),
+                   (long long)offsetof(PersistArgs, q_true), (long long)offsetof(PersistArgs, q_bits),
+                   (long long)offsetof(PersistArgs, q_seed), (long long)sizeof(PersistArgs)};
+  const int k = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < k; ++i) out[i] = v[i];
+  return k;
+}
+
+// Workgroups the persistent Q kernel for `args` can keep resident (0: shape not eligible).
+long gadmm_chain_persistent_q_capacity(const PersistArgs* args) {
+  const QVariant v = pick_q_variant(*args);
+  if (!v.fn || v.shm > 65536) return 0;
+  return gadmm_resident_capacity(v.fn, 64, v.shm);
+}
+
+int gadmm_chain_persistent_q_launch(const PersistArgs* args, hipStream_t st) {
+  const PersistArgs& a = *args;
+  const QVariant v = pick_q_variant(a);
+  if (!v.fn || v.shm > 65536) {
+    gadmm_set_error("persistent Q kernel: d=%d, n=%d not eligible (d <= 64)", a.d, a.n);
+    return -1;
+  }
+  if (a.q_bits != 4 && a.q_bits != 8 && a.q_bits != 16) {
+    gadmm_set_error("persistent Q kernel: q_bits must be 4, 8 or 16, got %d", a.q_bits);
+    return -1;
+  }
+  if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.theta || !a.mu || !a.Minv || !a.A || !a.ctl) {
+    gadmm_set_error("persistent Q kernel: a required buffer is null");
+    return -1;
+  }
+  if (a.n_epochs > 0 || a.nranks > 1 || a.sys_scope || a.push || a.n_local != a.n || !a.has_monitor ||
+      a.hard_stop != 0 || a.cont) {
+    gadmm_set_error("persistent Q kernel: one GPU, every worker local, a static chain, one launch per solve");
+    return -1;
+  }
+  const int blocks = a.n_local + 1;
+  const long cap = gadmm_resident_capacity(v.fn, 64, v.shm);
+  if (blocks > cap) {
+    gadmm_set_error("persistent Q kernel: %d workgroups but only %ld can be resident", blocks, cap);
+    return -2;
+  }
+  if (a.ring <= a.lag + 1) {
+    gadmm_set_error("persistent Q kernel: ring must exceed lag + 1");
+    return -1;
+  }
+  if (a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+    gadmm_set_error("persistent Q kernel: iteration tags limited to 2^20");
+    return -1;
+  }
+  PersistArgs ka = a;
+  ka.xcd = gadmm_xcd_mode(&a, blocks, cap);
+  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
+  void* kargs[] = {&ka};
+  GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(64), kargs, v.shm, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

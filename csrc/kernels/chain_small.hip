@@ -658,10 +658,12 @@ extern "C" {
 
 int gadmm_chain_phase_big(const PhaseArgs* args, hipStream_t st);
 int gadmm_chain_phase_newton(const PhaseArgs* args, hipStream_t st);
+int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st);
 
 int gadmm_chain_phase(const PhaseArgs* args, hipStream_t st) {
   const PhaseArgs& a = *args;
   if (a.n_slots <= 0) return 0;
+  if (a.q_bits > 0) return gadmm_chain_phase_quant(args, st);  // Q-GADMM (chain_quant.hip)
   if (a.model == MODEL_LOGISTIC && a.solver == 1) return gadmm_chain_phase_newton(args, st);
   if (a.d > 256) {
     if (a.model != MODEL_LINEAR) {

@@ -49,7 +49,7 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
                inner_tol: float = 1e-4, cost_quirk: bool = True, backend: str = "auto",
                name: str = "GADMM", record_theta: bool = False, engine_opts: Optional[dict] = None,
                state=None, check_exchange: Optional[bool] = None,
-               failures: Optional[dict] = None) -> RunResult:
+               failures: Optional[dict] = None, quantize: Optional[Sequence] = None) -> RunResult:
     """Run one chain-ADMM solve on this rank. ``model`` holds this rank's shards (local order =
     ``local_ids``). ``schedule`` (D-GADMM) overrides ``path``; ``cost_quirk`` reproduces the
     reference's per-head-worker accumulation of ``sum(pathCost)`` (dynamic_group_ADMM_closedForm.m:51-55).
@@ -61,9 +61,17 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
     the workers drop out, the chain re-forms over the survivors, each failed worker's aggregated
     dual is handed to a surviving chain neighbour (keeping sum(mu) = 0, the consensus-dual
     invariant) and the stopping target becomes the survivors' optimum (linear models; natively on
-    one rank with a static chain, ``_chain_admm_native_elastic``; torch path otherwise)."""
+    one rank with a static chain, ``_chain_admm_native_elastic``; torch path otherwise).
+    ``quantize``: ``(bits, seed)`` - Q-GADMM (algorithms/quantize.py): every worker publishes a
+    stochastically quantized difference to its last transmitted model, ``bits`` in {4, 8, 16} per
+    coordinate; the chain runs on those public models, the objective and the stop rule on the true
+    iterates (``_chain_admm_quantized`` documents the dispatch). None: every path as without it."""
 
     comm = comm if comm is not None else LocalComm()
+    if quantize is not None:
+        return _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, path,
+                                     schedule, local_solver, step, max_inner, inner_tol, cost_quirk, backend, name,
+                                     record_theta, engine_opts, state, check_exchange, failures, quantize)
     if check_exchange is None:
         check_exchange = getenv("GADMM_CHECK_EXCHANGE", "0") == "1"
     placement = placement if placement is not None else Placement.contiguous(n_total, comm.nranks)
@@ -235,7 +243,7 @@ def chain_admm_sweep(model, local_ids: Sequence[int], n_total: int, rhos: Sequen
 
 def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
                       local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
-                      check_exchange=False, failures=None):
+                      check_exchange=False, failures=None, quantize=None):
     rank = comm.rank
     checker = None
     if check_exchange:
@@ -254,6 +262,16 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
         theta = torch.zeros((n_total, d), dtype=torch.float64, device=dev)
         mu = torch.zeros((len(local_ids), d), dtype=torch.float64, device=dev)
         start = 1
+    q_bits = q_seed = 0
+    th_true = None
+    min_margin = float("inf")
+    if quantize is not None:
+        # Q-GADMM: the table every worker reads and exchanges holds the PUBLIC models th_hat; the true
+        # iterates of the local workers stay beside it for the objective (a closed-form solve never
+        # reads its own previous theta, so nothing else changes)
+        from . import quantize as Q
+        q_bits, q_seed = Q.check_bits(quantize[0]), int(quantize[1])
+        th_true = theta.index_select(0, torch.tensor(local_ids, dtype=torch.long, device=dev)).clone()
     stop = Stopper(obj0, tol, max_iter)
     snap = comm.stats.snapshot()
     alive = np.ones(n_total, dtype=bool)
@@ -306,7 +324,14 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
                     new = model.newton_prox(li, thw, m_li, quad, center)
                 else:
                     raise ValueError("unknown local solver %r" % local_solver)
-                theta[torch.tensor(gid, dtype=torch.long, device=dev)] = new
+                gix = torch.tensor(gid, dtype=torch.long, device=dev)
+                if q_bits:
+                    th_true[li] = new
+                    _, _, hat, mg = Q.quantize_rows(new.cpu().numpy(), theta.index_select(0, gix).cpu().numpy(),
+                                                    q_bits, Q.u01(q_seed, it, n_total, gid, d))
+                    min_margin = min(min_margin, mg)
+                    new = torch.from_numpy(hat).to(dev)
+                theta[gix] = new
             comm.exchange_rows(theta, xchg)
             if checker is not None:
                 checker.verify(theta, [r for _, r, s in xchg if not s], it,
@@ -323,7 +348,7 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
             m = m - rho * (thl - thw) * ml.unsqueeze(-1)
             m = m + rho * (thw - thr) * mr.unsqueeze(-1)
             mu[li] = m
-        th_loc = theta.index_select(0, torch.tensor(local_ids, dtype=torch.long, device=dev))
+        th_loc = th_true if q_bits else theta.index_select(0, torch.tensor(local_ids, dtype=torch.long, device=dev))
         f = model.objective(th_loc)
         if not alive.all():
             f = f * torch.as_tensor(alive[local_ids], dtype=f.dtype, device=dev)
@@ -351,8 +376,147 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
                            "monitor_bytes": int(comm.stats.delta(snap)["monitor_bytes"])},
                     primal_res=np.asarray(primal))
     res.extra["state"] = (theta, mu, (iters if converged else start - 1 + n_it) + 1)
+    if q_bits:
+        _quant_accounting(res, q_bits, q_seed, n_total, d, start)
+        res.extra["min_flip_margin"] = min_margin
+        res.extra["theta_true"] = th_true
     if record_theta:
         res.theta = theta.cpu().numpy()
+    return res
+
+
+def _quant_accounting(res: RunResult, bits: int, seed: int, n_total: int, d: int, start: int = 1) -> None:
+    """Q-GADMM communication of a result: ``comm_units`` in equivalent full-precision transmissions
+    (a message is ``bits * d + 64`` payload bits instead of ``64 * d``) and the totals in ``extra``."""
+    from .quantize import payload_bits
+    pb = payload_bits(d, bits)
+    n_it = len(res.obj)
+    res.comm_units = np.arange(start, start + n_it, dtype=np.float64) * n_total * pb / (64.0 * d)
+    res.extra.update(q_bits=int(bits), q_seed=int(seed), payload_bits=int(res.iters) * n_total * pb)
+
+
+def _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, path, schedule,
+                          local_solver, step, max_inner, inner_tol, cost_quirk, backend, name, record_theta,
+                          engine_opts, state, check_exchange, failures, quantize) -> RunResult:
+    """Q-GADMM dispatch. Native (HIP device, ``backend`` auto / native): one rank, a static chain,
+    the linear model with closed-form solves and every worker local -- the persistent Q kernel at
+    d <= 64 (one launch; a residency refusal or a hand-off timeout falls back to the graph engine),
+    the graph engine's Q phase kernel at d <= 256. Everything else -- ``state``, ``failures``, the
+    exchange checker, a dynamic schedule, several ranks, logistic models, d > 256, CPU tensors -- runs
+    the torch path, with the reason in ``extra['quant_fallback']``. Both compute the specification of
+    algorithms/quantize.py; they differ in how the local solve rounds, which a quantizer can amplify
+    once a flip margin (``extra['min_flip_margin']`` of the torch path) is down at that level."""
+    from . import quantize as Q
+    if len(quantize) != 2:
+        raise ValueError("quantize: (bits, seed)")
+    bits, seed = Q.check_bits(quantize[0]), int(quantize[1])
+    if check_exchange is None:
+        check_exchange = getenv("GADMM_CHECK_EXCHANGE", "0") == "1"
+    placement = placement if placement is not None else Placement.contiguous(n_total, comm.nranks)
+    if schedule is None:
+        p0 = list(path) if path is not None else list(range(n_total))
+        schedule = PathSchedule(n_total, p0, np.zeros(max(n_total - 1, 0)), coherence=0)
+    if local_solver is None:
+        local_solver = "closed" if model.kind == "linear" else "gd"
+    why = None
+    if backend == "torch":
+        why = "torch backend"
+    elif model.device.type != "cuda":
+        why = "cpu tensors"
+    elif state is not None:
+        why = "state= (resume)"
+    elif failures:
+        why = "failures= (elastic recovery)"
+    elif check_exchange:
+        why = "exchange checker"
+    elif comm.nranks > 1:
+        why = "several ranks"
+    elif not _static_schedule(schedule, max_iter):
+        why = "dynamic schedule"
+    elif model.kind != "linear" or local_solver != "closed":
+        why = "not the linear closed-form model"
+    elif model.d > 256:
+        why = "d > 256"
+    elif sorted(int(w) for w in local_ids) != list(range(n_total)):
+        why = "not every worker local"
+    elif (engine_opts or {}).get("fabric") is not None:
+        why = "xgmi fabric"
+    if why is None:
+        from ..ops import native
+        if native.available():
+            with roctx_range("%s native-Q N=%d b=%d" % (name, n_total, bits)):
+                return _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter, placement,
+                                                schedule, cost_quirk, name, engine_opts or {}, bits, seed)
+        if backend == "native":
+            raise RuntimeError("native backend requested but unavailable for this comm/device")
+        why = "native library unavailable"
+    elif backend == "native":
+        raise RuntimeError("Q-GADMM: the native backend does not cover this case (%s)" % why)
+    res = _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
+                            local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
+                            check_exchange, failures, quantize=(bits, seed))
+    res.extra["quant_fallback"] = why
+    return res
+
+
+def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter, placement, schedule, cost_quirk,
+                             name, opts, bits, seed) -> RunResult:
+    """Q-GADMM on the native chain engine (one rank, static chain, linear closed form, d <= 256).
+    ``opts``: ``persistent`` (auto/True/False), ``graph``, ``cache``, ``block``, ``xcd``."""
+    from ..engine.chain_engine import NativeChainEngine, ResidencyError, HandoffTimeout
+    from . import quantize as Q
+
+    d = model.d
+    block = int(opts.get("block", 32))
+    key = ("quant", n_total, tuple(map(int, local_ids)), float(rho), int(max_iter), block, bits, seed,
+           int(opts.get("xcd", 2)))
+    cache = getattr(model, "_chain_engines", None)
+    eng = cache.get(key) if cache is not None else None
+    if eng is None:
+        eng = NativeChainEngine(model.X, model.y, local_ids, n_total, "linear", rho=rho, obj0=obj0, tol=tol,
+                                max_iter=max_iter, block=block, precomputed=(model.A, model.b, model.yy),
+                                xcd=int(opts.get("xcd", 2)), quant=(bits, seed))
+        if opts.get("cache", True):
+            if cache is None:
+                cache = {}
+                model._chain_engines = cache
+            cache[key] = eng
+    else:
+        eng.set_targets(obj0, tol)
+    eng.set_path(schedule.path, placement, 0)
+    eng.reset()
+    torch.cuda.synchronize(model.device)
+    t0 = time.perf_counter()
+    r = None
+    kernel = None
+    engine_kind = None
+    if opts.get("persistent", "auto") in (True, "auto") and eng.persistent_q_eligible():
+        try:
+            r = eng.run_persistent(fetch_trace=True)
+            engine_kind, kernel = "persistent", eng.last_kernel
+        except (ResidencyError, HandoffTimeout) as e:
+            eng.reset()
+            engine_kind = "graph(fallback: %s)" % type(e).__name__
+    if r is None:
+        r = eng.run(use_graph=opts.get("graph", True))
+        kernel = "graph-Q"
+        if engine_kind is None:
+            engine_kind = "graph" if eng.graph_ok() else "eager"
+        eng.stream.synchronize()
+    wall = time.perf_counter() - t0
+    iters, done = int(r.iters), int(r.done)
+    tr, tt = eng.traces(iters)
+    per = float(np.sum(schedule.cost)) * ((n_total + 1) // 2 if cost_quirk else 1)
+    G = Q.granules_per_row(d, bits)
+    res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(done == 1), wall_s=wall,
+                    time_trace=tt, comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
+                    com_cost=np.arange(1, iters + 1) * per, bytes_sent=0, bytes_total=0, primal_res=None,
+                    extra={"backend": "native", "engine": engine_kind, "kernel": kernel, "rank": 0, "nranks": 1,
+                           "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0, "transport": "local",
+                           "obj_mode": eng.obj_mode_name, "engine_obj": eng, "q_granules": G,
+                           "q_wire_bytes": iters * n_total * G * 16,
+                           "placed": int(getattr(eng, "last_placed", 0)) if engine_kind == "persistent" else 0})
+    _quant_accounting(res, bits, seed, n_total, d)
     return res
 
 
@@ -951,6 +1115,15 @@ def _is_rechain(it: int, coherence) -> bool:
 
 
 # Convenience wrappers named after the reference functions -----------------------------------------
+
+def quantized_group_admm(model, rho, obj0, acc, max_iter, bits, seed=1234, **kw) -> RunResult:
+    """Q-GADMM (arXiv:1910.10453) on a static chain: GADMM whose workers exchange ``bits``-bit
+    stochastically quantized model differences (``chain_admm(..., quantize=(bits, seed))``)."""
+    n_total = kw.pop("n_total", model.n_local)
+    local_ids = kw.pop("local_ids", list(range(model.n_local)))
+    kw.setdefault("name", "Q-GADMM(b=%d)" % int(bits))
+    return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, quantize=(bits, seed), **kw)
+
 
 def group_admm_closed_form(model, rho, obj0, acc, max_iter, **kw) -> RunResult:
     """``group_ADMM_closedForm`` (A1) on all local workers (single rank unless comm given)."""

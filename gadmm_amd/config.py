@@ -48,6 +48,10 @@ class ExperimentConfig:
     # same field: 'concurrent' = up to eight coherences side by side, in rounds of epoch-chunk
     # launches (algorithms.dynamic_group_admm_sweep)
     sweep: str = "sequential"
+    # Q-GADMM runs next to the GADMM rho sweep of the linear entries (E1, E2): one
+    # ``Q-GADMM_b{bits}_rho{rho}`` run per (bits, rho), bits in {4, 8, 16}; empty = none
+    quant_bits: List[float] = field(default_factory=list)
+    quant_seed: int = 1234
 
     def override(self, **kw) -> "ExperimentConfig":
         if kw.get("sweep", "sequential") not in ("sequential", "concurrent"):

@@ -137,7 +137,8 @@ class NativeChainEngine:
                  max_iter: int = 1000, lam: float = 0.0, step: float = 0.0, max_inner: int = 100,
                  inner_tol: float = 1e-4, comm=None, block: int = 16, stream: Optional[torch.cuda.Stream] = None,
                  precomputed=None, force_monitor: bool = False, obj_mode: str = "auto", local_solver: str = "gd",
-                 chord: Optional[float] = None, residual: bool = False, xcd: int = 2, inverses=None):
+                 chord: Optional[float] = None, residual: bool = False, xcd: int = 2, inverses=None,
+                 quant: Optional[Sequence[int]] = None):
         """``local_solver`` (logistic): "gd" = the reference's inexact inner GD (logReg_GD.m, step /
         max_inner / inner_tol), "newton" = exact local solves (group_ADMM_logistic.m semantics,
         csrc/kernels/chain_newton.hip; d, m <= 64). ``chord`` (newton): a worker reuses its last
@@ -156,7 +157,12 @@ class NativeChainEngine:
         (PersistArgs::xcd; speed only, results are bit-identical). ``inverses`` (linear, with
         ``precomputed``): ``(Minv (N, nvar, d, d), nvar, deg_to_var)`` -- the engine reads its cached
         inverses out of a table it shares with other engines (engine/chain_sweep.py builds one table for
-        a whole rho sweep in one launch) and leaves ``refresh`` / ``set_rho`` to the table's owner."""
+        a whole rho sweep in one launch) and leaves ``refresh`` / ``set_rho`` to the table's owner.
+        ``quant``: ``(bits, seed)`` -- Q-GADMM (csrc/kernels/chain_quant.hip; linear, one rank, d <= 256):
+        the theta table holds the public models th_hat, ``theta_true`` the true iterates of the last
+        phases, ``q_msg`` (n_total, 1 + words) the last message of each worker (the bits of R, then the
+        packed code words). ``run()`` uses the graph engine's Q phase kernel, ``run_persistent()`` the
+        persistent Q kernel (``persistent_q_eligible``); the blocked plan is never used."""
         if not X_loc.is_cuda:
             raise ValueError("NativeChainEngine runs on a HIP device; use the torch algorithms on CPU")
         # the kernels read raw f64 pointers: anything else (e.g. float32 labels from torch.where) would be
@@ -177,6 +183,13 @@ class NativeChainEngine:
         self.xport = getattr(comm, "xport", None) if comm is not None else None
         if local_solver not in ("gd", "newton"):
             raise ValueError("unknown local solver %r" % local_solver)
+        self.quant = None
+        if quant is not None:
+            from ..algorithms.quantize import check_bits, words_per_row
+            self.quant = (check_bits(quant[0]), int(quant[1]) & ((1 << 64) - 1))
+            if model != "linear" or self.d > 256 or comm is not None:
+                raise ValueError("native Q-GADMM: the linear model on one rank with d <= 256")
+            self.q_words = words_per_row(self.d, self.quant[0])
         if local_solver == "newton" and (model != "logistic" or self.d > 64 or self.m > 64):
             raise ValueError("native Newton local solves need the logistic model with d, m <= 64")
         self.local_solver = local_solver
@@ -229,6 +242,10 @@ class NativeChainEngine:
             self.xcd = int(xcd)
             # K4 primal residual: per (iteration, worker) contributions of the tails (owned rows only)
             self.rres = torch.zeros((self.max_iter * self.n_total,), dtype=f64, device=dev) if residual else None
+            self.theta_true = self.q_msg = None
+            if self.quant is not None:
+                self.theta_true = torch.zeros((nl, d), dtype=f64, device=dev)
+                self.q_msg = torch.zeros((self.n_total, 1 + self.q_words), dtype=torch.int64, device=dev)
             if d > 256:
                 stride = int(native.require().gadmm_chain_big_rbuf_stride(d))
                 self.rbuf = torch.zeros((max(nl, 1) * stride,), dtype=f64, device=dev)
@@ -291,6 +308,9 @@ class NativeChainEngine:
         args.lgid = self.lgid.data_ptr()
         args.tstamp = self.tstamp.data_ptr()
         args.rres = native.ptr(self.rres)
+        if self.quant is not None:
+            args.q_bits, args.q_seed = self.quant
+            args.q_true, args.q_msg = self.theta_true.data_ptr(), self.q_msg.data_ptr()
         desc = native.EngineDesc()
         desc.base = args
         desc.d_slots = self.slots.data_ptr()
@@ -548,9 +568,56 @@ class NativeChainEngine:
         g.scratch = self.newton_img.data_ptr() if self.newton_img is not None else None
         return g
 
+    def persistent_q_eligible(self) -> bool:
+        """The persistent Q kernel takes this engine: one rank, every worker local, d <= 64 and all
+        n + 1 workgroups resident at once (``GADMM_CU_BUDGET`` shrinks the CU count)."""
+        if self.quant is None or self.plan is None or self.path is None or self.model != "linear":
+            return False
+        if self.nranks != 1 or self.n_local != self.n_total or self.d > 64:
+            return False
+        key = ("q", getenv("GADMM_CU_BUDGET"))
+        memo = self.__dict__.setdefault("_cap_memo", {})
+        if key not in memo:
+            pa = native.PersistArgs()
+            pa.d, pa.n = self.d, self.n_total
+            memo[key] = int(self.lib.gadmm_chain_persistent_q_capacity(ctypes.byref(pa)))
+        return self.n_local + 1 <= memo[key]
+
+    def _run_persistent_q(self, lag: int, timeout_s: float, start_iter: int, fetch_trace: bool) -> EngineRun:
+        """Q-GADMM, the whole solve in one launch of chain_persistent_q_kernel."""
+        import time as _time
+        if not self.persistent_q_eligible():
+            raise RuntimeError("persistent Q kernel not eligible for this engine/config")
+        if start_iter != 1:
+            raise ValueError("persistent Q kernel: a fresh solve only (start_iter 1)")
+        ring = lag + 4
+        pa, slots, pos, _ = self._persist_args(lag, ring, timeout_s, start_iter, 0, None, False, 0, False)
+        G = self.q_words + 1
+        if getattr(self, "_qg", None) is None:
+            with torch.cuda.stream(self.stream):  # zeroed once, ordered before the kernel; tags are salted per solve
+                self._qg = torch.zeros((self.n_total * G * 4,), dtype=torch.int32, device=self.device)
+        pa.obj_mode = 0
+        pa.qg, pa.q_true = self._qg.data_ptr(), self.theta_true.data_ptr()
+        pa.q_bits, pa.q_seed = self.quant
+        self.last_kernel = "persistent-Q(b=%d,G=%d)" % (self.quant[0], G)
+        t0 = _time.perf_counter()
+        rc = int(self.lib.gadmm_chain_persistent_q_launch(ctypes.byref(pa), self.stream.cuda_stream))
+        if rc == -2:
+            raise ResidencyError(self.lib.gadmm_last_error().decode())
+        native.check(rc, "chain_persistent_q_launch")
+        fetch = self._queue_readback(fetch_trace)
+        self.stream.synchronize()
+        self._tr_valid = fetch
+        t1 = _time.perf_counter()
+        self.last_timeline = self.last_timeline_slots = None
+        done, conv, nxt = self._decode_ctl("persistent Q kernel")
+        return EngineRun(conv, done, nxt - start_iter, 1, (t1 - t0) * 1e3, 0, 0, 0, 0)
+
     def persistent_eligible(self, fabric=None) -> bool:
         if self.plan is None or self.path is None:
             return False
+        if self.quant is not None:
+            return fabric is None and self.persistent_q_eligible()
         if self.nranks != 1 and fabric is None:
             return False
         if self.model == "logistic":
@@ -612,7 +679,7 @@ class NativeChainEngine:
     def dynamic_eligible(self, fabric=None) -> bool:
         """One-launch D-GADMM (per-epoch chains in device tables): linear, every degree's inverse
         resident; several ranks need an xGMI fabric whose theta tables hold a ring of iteration slots."""
-        if self.model != "linear":
+        if self.model != "linear" or self.quant is not None:
             return False
         if self.nranks != 1 and (fabric is None or getattr(fabric, "table_slots", 1) < 2):
             return False
@@ -626,7 +693,8 @@ class NativeChainEngine:
         """(k, L, W, pw) of the temporally blocked kernel for this engine, or None (multi-GPU, d > 64,
         GADMM_BLOCKED=0). pw = positions per wave: 1 = the 12-wave kernel (default, also the only
         instrumented one, so ``timeline`` selects it), 2 = the paired 8-wave kernel (GADMM_BLOCK_PW=2)."""
-        if fabric is not None or self.nranks > 1 or self.d > 64 or getenv("GADMM_BLOCKED", "1") == "0":
+        if fabric is not None or self.nranks > 1 or self.d > 64 or getenv("GADMM_BLOCKED", "1") == "0" \
+                or self.quant is not None:
             return None
         # memoised per (timeline, the env switches the planner reads)
         key = (bool(timeline), getenv("GADMM_BLOCK_K"), getenv("GADMM_BLOCK_L"),
@@ -920,6 +988,10 @@ class NativeChainEngine:
         before the stream is synchronised -- host work of the caller that does not need the outcome
         (e.g. D-GADMM's per-epoch cost arrays) overlaps the kernel instead of following it."""
         _timing.host_stamp("rp:start")
+        if self.quant is not None:
+            if fabric is not None or epochs is not None or pending_in or hard_stop or cont or timeline_iters:
+                raise RuntimeError("persistent Q kernel: a static chain on one GPU, one launch per solve")
+            return self._run_persistent_q(lag, timeout_s, start_iter, fetch_trace)
         if epochs is not None:
             if not self.dynamic_eligible(fabric):
                 raise RuntimeError("dynamic persistent kernel not eligible for this engine/config")

@@ -335,6 +335,19 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
                             need_state=(state_rho is not None and rho == state_rho))
         r.extra.pop("engine_obj", None)
         out["GADMM_rho%g" % rho] = attach_modelled_clock(r, prob.model, rho, sess)
+    if cfg.quant_bits and cfg.model != "linear":
+        raise ValueError("quant_bits: Q-GADMM runs on the linear entries (closed-form local solves)")
+    for bits in cfg.quant_bits:  # Q-GADMM next to the sweep; comm_units counts equivalent full-precision messages
+        from ..algorithms import chain_admm
+
+        for rho in cfg.rhos:
+            with roctx_range("qgadmm b=%g rho=%g" % (bits, rho)):
+                r = chain_admm(prob.model, prob.local_ids, prob.n_total, rho, prob.obj0, cfg.acc, cfg.gadmm_iters,
+                               comm=sess.comm, placement=prob.placement, backend=backend,
+                               name="Q-GADMM(b=%d,rho=%g)" % (int(bits), rho), quantize=(int(bits), cfg.quant_seed))
+            for k in ("engine_obj", "theta_true", "state"):
+                r.extra.pop(k, None)
+            out["Q-GADMM_b%d_rho%g" % (int(bits), rho)] = attach_modelled_clock(r, prob.model, rho, sess)
     if cfg.model == "logistic":
         for rho in cfg.exact_rhos:  # exact local solves (D2 semantics), to the tighter exact_acc gap
             with roctx_range("gadmm_exact rho=%g" % rho):
