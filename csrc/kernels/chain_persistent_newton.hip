@@ -1501,6 +1501,13 @@ long gadmm_chain_persistent_newton_capacity(const PersistArgs* args, const LogiA
   return fn ? gadmm_resident_capacity(fn, newton_threads(*g), newton_shm(*args, *g)) : 0;
 }
 
+// Which kernel a launch with these arguments (and the environment as it is now) would take:
+// 0 none (newton_variant refuses them), 1 the one-wave solver kernel, 2 the pipeline kernel.
+int gadmm_chain_persistent_newton_kernel(const PersistArgs* args, const LogiArgs* g) {
+  if (!newton_variant(*args, *g)) return 0;
+  return newton_rec(*g) ? 2 : 1;
+}
+
 int gadmm_chain_persistent_newton_launch(const PersistArgs* args, const LogiArgs* gargs, hipStream_t st) {
   const PersistArgs& a = *args;
   const LogiArgs& g = *gargs;

@@ -1119,7 +1119,9 @@ class NativeChainEngine:
                 raise RuntimeError("persistent logistic kernel: static chains only")
             self._logi = self._logi_args()
             if self.local_solver == "newton":
-                self.last_kernel = "per-worker-newton"
+                # which of the launcher's two kernels this launch takes (GADMM_NEWTON_REC is read per launch)
+                which = int(self.lib.gadmm_chain_persistent_newton_kernel(ctypes.byref(pa), ctypes.byref(self._logi)))
+                self.last_kernel = "per-worker-newton" + {1: "(one-wave)", 2: "(pipeline)"}.get(which, "")
                 launch = self.lib.gadmm_chain_persistent_newton_launch
             else:
                 self.last_kernel = "per-worker-logistic"

@@ -195,6 +195,7 @@ def _declare(lib: ctypes.CDLL) -> None:
                                                            c_void_p]),
         "gadmm_logi_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
         "gadmm_chain_persistent_newton_capacity": (c_long, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
+        "gadmm_chain_persistent_newton_kernel": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
         "gadmm_newton_rec_scratch_doubles": (c_long, []),
         "gadmm_chain_persistent_newton_launch": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs),
                                                          c_void_p]),

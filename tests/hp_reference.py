@@ -10,7 +10,11 @@ specification), in the form the kernels evaluate them:
   it); NumPy has no long-double solve, so the long-double inverse is the float64 one refined by
   three Newton-Schulz steps ``X <- X (2 I - M X)`` (quadratic: 1e-13 -> 1e-26 -> below 2^-63);
 * the linear objective is the Gram form ``1/2 th'A th - b'th + 1/2 y'y``;
-* chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form).
+* chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form);
+* the exact logistic prox (``gadmm_logistic_newton``) has no oracle counterpart: it follows the header
+  of csrc/kernels/chain_newton.hip and is held against the torch path (models/logistic.py:newton_prox)
+  by tests/test_hp_reference_cpu.py. Its long-double run is the converged prox (stop tolerance 1e-17);
+  the float64 run stops as the kernels do (1e-13), optionally under their chord rule.
 
 This is a helper module, not a conftest: test modules import it as ``import hp_reference``.
 """
@@ -177,6 +181,103 @@ def gadmm_logistic_gd(X, y, rho, lam, step, K, max_inner, inner_tol, dtype=LD):
     return thetas, mu, obj, inner, margin[0]
 
 
+NEWTON_MAX = 50      # step cap of a local Newton solve (chain_newton.hip NEWTON_MAX, newton_prox iters)
+NEWTON_TOL = 1e-13   # the kernels' stop tolerance (NEWTON_TOL / NTOL)
+NEWTON_TOL_LD = 1e-17  # the long-double reference's: the converged prox
+
+
+def _newton_run(X, y, rho, lam, K, dtype, tol, chord):
+    """The recurrence of ``gadmm_logistic_newton`` with the duals of EVERY iteration (K, N, d): a run
+    to iteration k is a prefix of a longer one, so one run serves every ``k <= K``."""
+    N, m, d = X.shape
+    if chord > 0 and np.dtype(dtype) != np.float64:
+        raise ValueError("the chord rule is the float64 kernels': dtype=float64 only")
+    X = np.asarray(X, dtype=dtype)
+    y = np.asarray(y, dtype=dtype)
+    rho, lam, tol = (np.asarray(v, dtype=dtype) for v in (rho, lam, tol))
+    one = np.asarray(1.0, dtype=dtype)
+    half = np.asarray(0.5, dtype=dtype)
+    eye = np.eye(d, dtype=dtype)
+    th = np.zeros((N, d), dtype=dtype)
+    mu = np.zeros((N, d), dtype=dtype)
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    mus = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    steps = np.zeros((K, N), dtype=np.int64)
+    cache = [None] * N  # chord > 0: the inverse of the worker's last refresh, kept across iterations
+
+    def solve(n, k):
+        deg = (n > 0) + (n < N - 1)
+        shift = lam + deg * rho
+        c = mu[n].copy()
+        if n > 0:
+            c = c - rho * th[n - 1]
+        if n < N - 1:
+            c = c - rho * th[n + 1]
+        A, Y = X[n], y[n]
+        x = th[n].copy()
+        Hinv = cache[n] if chord > 0 else None
+        refresh = Hinv is None
+        prev = None
+        for s in range(NEWTON_MAX):
+            p = one / (one + np.exp(Y * (A @ x)))  # sigma(-y z)
+            g = -(A.T @ (Y * p)) + shift * x + c
+            if refresh:
+                Hinv = spd_inverse((A.T * (p * (one - p))) @ A + shift * eye, dtype)
+                if chord > 0:
+                    cache[n] = Hinv
+            dx = Hinv @ g
+            x = x - dx
+            mdx = np.max(np.abs(dx))
+            steps[k, n] = s + 1
+            if mdx < tol * max(one, np.max(np.abs(x))):
+                break
+            # chord steps reuse the inverse while they contract by at least `chord` per step; the step
+            # after a refresh is always a chord step (as the kernel: its contraction is not tested)
+            refresh = bool(chord <= 0 or (not refresh and prev is not None and mdx > chord * prev))
+            prev = mdx
+        th[n] = x
+
+    for k in range(K):
+        for phase in (0, 1):
+            for n in range(phase, N, 2):
+                solve(n, k)
+        for n in range(N):
+            upd = np.zeros(d, dtype=dtype)
+            if n < N - 1:
+                upd = upd + rho * (th[n] - th[n + 1])
+            if n > 0:
+                upd = upd - rho * (th[n - 1] - th[n])
+            mu[n] = mu[n] + upd
+        thetas[k] = th
+        mus[k] = mu
+        tot = np.zeros((), dtype=dtype)
+        for n in range(N):
+            tot = tot + (lam * half * (th[n] @ th[n]) + np.sum(np.log1p(np.exp(-y[n] * (X[n] @ th[n])))))
+        obj[k] = tot
+    return thetas, mus, obj, steps
+
+
+def gadmm_logistic_newton(X, y, rho, lam, K, dtype=LD, tol=NEWTON_TOL_LD, chord=0.0):
+    """GADMM logistic regression with EXACT local solves (header of csrc/kernels/chain_newton.hip;
+    the stop rule of models/logistic.py:newton_prox): heads, tails, then every worker's ``mu``. Worker n
+    minimises ``f_n(x) + mu_n'x + rho/2 sum_nbr |x - th_nbr|^2`` by Newton steps
+
+        g = -X'(y . sigma(-y . Xx)) + (lam + deg rho) x + mu - rho (th_l + th_r)
+        H = X' diag(w) X + (lam + deg rho) I,  w = sigma (1 - sigma);   dx = H^-1 g;   x <- x - dx
+
+    from its own last iterate, at most 50 of them, and stops after the first step with
+    ``max|dx| < tol * max(1, max|x|)`` (strict). ``H^-1`` is ``spd_inverse``'s explicit inverse.
+    ``chord = c > 0`` (float64 only) is the kernels' chord rule: a worker keeps the inverse of its last
+    refresh across iterations, and a step refreshes only when none is cached or when the previous
+    step, itself a chord step, contracted by less than c (``|dx_k| > c |dx_{k-1}|``); the stop rule
+    and the fixed point are unchanged.
+    Returns ``(theta (K, N, d), mu (N, d) per-worker duals after iteration K, objectives (K,),
+    Newton step counts (K, N))``."""
+    th, mus, obj, steps = _newton_run(np.asarray(X), y, rho, lam, K, dtype, tol, chord)
+    return th, mus[-1], obj, steps
+
+
 def edge_to_worker_duals(lam_edge):
     """Per-worker aggregate ``mu_n = lam_n - lam_{n-1}`` of edge duals (N, d) whose last row is 0."""
     mu = np.array(lam_edge, copy=True)
@@ -214,10 +315,21 @@ def noise_level(ref_ld, ref_f64, scale):
     return float(np.max(diff)) if diff.size else 0.0
 
 
-def bound(e64, d, m_logistic=0):
-    """``FACTOR * max(e64, max(d, m_logistic, 16) * 2^-53)``: the float64 noise of the recurrence, with
-    the standard dot-product bound as the floor for runs that happen to round luckily."""
-    return FACTOR * max(float(e64), max(int(d), int(m_logistic), 16) * 2.0 ** -53)
+def bound(e64, d, m_logistic=0, truncation=0.0):
+    """``FACTOR * max(e64, max(d, m_logistic, 16) * 2^-53, truncation)``: the float64 noise of the
+    recurrence, with the standard dot-product bound as the floor for runs that happen to round luckily.
+    ``truncation``: what a stop rule of the kernel admits beyond rounding (``chord_truncation``)."""
+    return FACTOR * max(float(e64), max(int(d), int(m_logistic), 16) * 2.0 ** -53, float(truncation))
+
+
+def chord_truncation(chord, scale_theta):
+    """``tau(c) / max|theta|``, ``tau(c) = c / (1 - c) NEWTON_TOL max(1, max|x|)``: a chord-accepted last
+    step contracted by at most c, so the iterate it leaves can sit that far from the prox (the
+    geometric tail ``sum_{j >= 1} c^j`` of a step below the stop threshold). 0 at ``chord = 0``: exact
+    Newton converges quadratically and its stop rule leaves nothing above rounding."""
+    if chord <= 0:
+        return 0.0
+    return chord / (1.0 - chord) * NEWTON_TOL * max(1.0, scale_theta) / scale_theta
 
 
 class Reference:
@@ -227,7 +339,7 @@ class Reference:
     max |theta| over the run; ``b_theta`` / ``b_dual`` / ``b_obj``: the bounds of the three relative
     errors ``err_theta`` / ``err_dual`` / ``err_obj`` measure."""
 
-    def __init__(self, ld, f64, rho, d, m_logistic=0):
+    def __init__(self, ld, f64, rho, d, m_logistic=0, chord=0.0):
         self.theta, self.dual, self.obj = ld[0], ld[1], ld[2]
         self.extra = ld[3:]
         self.rho = float(rho)
@@ -235,9 +347,10 @@ class Reference:
         self.e_theta = noise_level(self.theta, f64[0], self.scale_theta)
         self.e_dual = noise_level(self.dual, f64[1], self.rho * self.scale_theta)
         self.e_obj = noise_level(self.obj, f64[2], np.abs(self.obj))
-        self.b_theta = bound(self.e_theta, d, m_logistic)
-        self.b_dual = bound(self.e_dual, d, m_logistic)
-        self.b_obj = bound(self.e_obj, d, m_logistic)
+        self.truncation = chord_truncation(chord, self.scale_theta)  # Newton cases with a chord rule only
+        self.b_theta = bound(self.e_theta, d, m_logistic, self.truncation)
+        self.b_dual = bound(self.e_dual, d, m_logistic, self.truncation)
+        self.b_obj = bound(self.e_obj, d, m_logistic, self.truncation)
 
     def err_theta(self, theta, k=None):
         """``theta`` (N, d) against the reference after iteration ``k`` (1-based; None: the last)."""
@@ -312,3 +425,45 @@ def logistic_case(n, m, d, K=K_ITERS, max_inner=MAX_INNER, inner_tol=0.0):
         f64 = gadmm_logistic_gd(X, y, rho, lam, step, K, max_inner, inner_tol, np.float64)
         return X, y, rho, lam, step, Reference(ld, f64, rho, d, m)
     return _cached(("log", n, m, d, K, max_inner, inner_tol), build)
+
+
+# The shapes of tests/test_gpu_newton_classes.py (the edge each one sits on is written there).
+NEWTON_GRAPH_SHAPES = [(2, 1, 1), (3, 5, 3), (3, 7, 5), (4, 17, 16), (3, 15, 17), (5, 36, 34), (3, 52, 52),
+                       (3, 40, 53), (3, 53, 40), (4, 7, 61), (2, 3, 64), (3, 63, 63), (3, 64, 64)]
+NEWTON_PERSISTENT_SHAPES = [(2, 1, 1), (3, 5, 3), (3, 7, 5), (4, 17, 16), (3, 15, 17), (5, 36, 34), (4, 12, 49),
+                            (3, 40, 52), (3, 52, 20), (3, 52, 52)]
+NEWTON_SHAPES = NEWTON_GRAPH_SHAPES + [s for s in NEWTON_PERSISTENT_SHAPES if s not in NEWTON_GRAPH_SHAPES]
+NEWTON_CHORDS = (0.0, 0.02, 0.3)  # exact Newton, the graph engine's default, the persistent kernels'
+PERSISTENT_OVERRUN = 16           # a persistent kernel stops at most this many iterations past K
+
+
+def _newton_history(n, m, d, K, dtype, tol, chord):
+    """One run of the recurrence per (case, arithmetic), long enough for every iteration count the
+    tests ask for: K_ITERS for the graph engine and the CPU tests, up to PERSISTENT_OVERRUN more for
+    the iteration a persistent kernel happens to stop at."""
+    run = K_ITERS if K <= K_ITERS else max(K, K_ITERS + PERSISTENT_OVERRUN)
+
+    def build():
+        X, y, rho, lam, _ = make_logistic(n, m, d, seed_of(n, m, d))
+        out = _newton_run(X, y, rho, lam, run, dtype, tol, chord)
+        _freeze(X, y, *out)
+        return (X, y, rho, lam) + out
+    return _cached(("newton-run", n, m, d, run, np.dtype(dtype).name, tol, chord), build)
+
+
+def newton_case(n, m, d, K=K_ITERS, chord=0.0):
+    """The ``Reference`` of ``gadmm_logistic_newton`` on ``make_logistic(n, m, d, seed_of(n, m, d))``
+    (the data of ``logistic_case``; ``step`` is not used). The reference is the long-double run with
+    ``tol = 1e-17`` and no chord rule, the converged prox; its noise ``e_*`` is the distance of the
+    float64 run with the kernels' ``tol = 1e-13`` and the chord threshold ``chord`` (e64 at 0, e_chord
+    above), and at ``chord > 0`` the bounds also admit ``chord_truncation``. Beside the fields of
+    ``Reference``: ``X``, ``y``, ``lam``, ``chord``; ``extra[0]`` the long-double run's Newton step
+    counts (K, N) and ``steps64`` the float64 run's."""
+    def build():
+        X, y, rho, lam, th, mus, obj, steps = _newton_history(n, m, d, K, LD, NEWTON_TOL_LD, 0.0)
+        _, _, _, _, th64, mus64, obj64, steps64 = _newton_history(n, m, d, K, np.float64, NEWTON_TOL, float(chord))
+        ref = Reference((th[:K], mus[K - 1], obj[:K], steps[:K]), (th64[:K], mus64[K - 1], obj64[:K]), rho, d, m,
+                        chord=float(chord))
+        ref.X, ref.y, ref.lam, ref.chord, ref.steps64 = X, y, lam, float(chord), steps64[:K]
+        return ref
+    return _cached(("newton", n, m, d, K, float(chord)), build)

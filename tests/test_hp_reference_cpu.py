@@ -1,8 +1,10 @@
-"""CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py.
+"""CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py
+and tests/test_gpu_newton_classes.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
-kernel stands there, held to the same bound ``8 * max(e64, max(d, m, 16) * 2^-53)``."""
+kernel stands there, held to the same bound ``8 * max(e64, max(d, m, 16) * 2^-53)``. The exact-prox
+recurrence, which the oracle does not have, is held against the torch Newton path instead."""
 import numpy as np
 import pytest
 
@@ -89,6 +91,84 @@ def test_fixtures_reproduce_oracle(lin24, log24):
     assert ld[4] > 1e-6 and np.array_equal(ld[3], f64[3])
     o = R.gadmm_logistic_gd(X, y, 2e-4, 30, 0.0, 1e-5, 0.0, 2.2)
     _check("log24", ref, o.theta, H.edge_to_worker_duals(o.dual), o.obj)
+
+
+# ------------------------------------------------------------------------------------------------
+# Exact local solves (tests/test_gpu_newton_classes.py). The oracle has no exact-prox variant
+# (gadmm_amd/oracle/reference.py: inner gradient descent only), so the project's own torch path
+# stands where a kernel stands: it solves H dx = g by LU where the reference applies an explicit
+# inverse, and batches a phase's workers (all of them step until the slowest has converged).
+@pytest.mark.parametrize("n,m,d", H.NEWTON_SHAPES)
+def test_gadmm_logistic_newton_reproduces_torch_path(n, m, d):
+    import torch
+    from gadmm_amd.algorithms import chain_admm
+    from gadmm_amd.models import LogisticRegression
+    ref = H.newton_case(n, m, d)
+    model = LogisticRegression(torch.from_numpy(np.array(ref.X)), torch.from_numpy(np.array(ref.y)), lam=ref.lam)
+    a = chain_admm(model, list(range(n)), n, ref.rho, 0.0, 1e-300, K, local_solver="newton", backend="torch")
+    assert a.extra["backend"] == "torch" and a.iters == K and len(a.obj) == K
+    theta, mu, nxt = a.extra["state"]
+    assert nxt == K + 1
+    _check("newton %s" % ((n, m, d),), ref, theta.numpy(), mu.numpy(), a.obj)
+
+
+@pytest.mark.parametrize("n,m,d", H.NEWTON_SHAPES)
+def test_newton_reference_noise_and_steps(n, m, d):
+    """The bound means something only while the noise under it is small: e64 of every quantity stays
+    below 64 * 2^-53 * max(d, m, 16) (measured 1.5e-16 .. 1.1e-15, profiles/newton_classes). Exact
+    Newton from the worker's last iterate takes 3 .. 7 steps; no solve, at any tested chord threshold,
+    comes near the cap of 50, where the kernels would report inner_fail."""
+    ref = H.newton_case(n, m, d)
+    lim = 64 * 2.0 ** -53 * max(d, m, 16)
+    print("newton %s: e64 theta %.2e dual %.2e objective %.2e (limit %.2e), steps %d..%d (float64 %d..%d)"
+          % ((n, m, d), ref.e_theta, ref.e_dual, ref.e_obj, lim, ref.extra[0].min(), ref.extra[0].max(),
+             ref.steps64.min(), ref.steps64.max()))
+    assert ref.e_theta <= lim and ref.e_dual <= lim and ref.e_obj <= lim
+    assert ref.truncation == 0.0 and ref.b_theta == H.bound(ref.e_theta, d, m)
+    for steps in (ref.extra[0], ref.steps64):
+        assert steps.shape == (K, n) and 2 <= steps.min() and steps.max() <= 12
+    for c in H.NEWTON_CHORDS[1:]:
+        rc = H.newton_case(n, m, d, chord=c)
+        print("  chord %.2f: e_chord theta %.2e dual %.2e objective %.2e, truncation %.2e, steps %d..%d"
+              % (c, rc.e_theta, rc.e_dual, rc.e_obj, rc.truncation, rc.steps64.min(), rc.steps64.max()))
+        assert rc.steps64.min() >= 1 and rc.steps64.max() < H.NEWTON_MAX
+        assert rc.theta is ref.theta or np.array_equal(rc.theta, ref.theta)  # one long-double run serves all
+        assert rc.truncation >= c / (1 - c) * H.NEWTON_TOL and rc.b_theta >= 8 * rc.truncation
+        assert max(rc.b_theta, rc.b_dual, rc.b_obj) < 1e-12  # still ten orders below an indexing mistake
+
+
+@pytest.mark.parametrize("n,m,d", [(2, 1, 1), (5, 36, 34), (3, 64, 64)])
+def test_newton_bound_catches_one_wrong_coordinate(n, m, d):
+    """One coordinate of one worker's theta off by 1e-9 of max|theta| lands above the chord-0 bound,
+    off by 1e-10 above the (wider) bound at chord 0.3; the float64 runs themselves, correct by
+    construction, land below 1/8 of it."""
+    X, y, rho, lam, _ = H.make_logistic(n, m, d, H.seed_of(n, m, d))
+    for c, off in ((0.0, 1e-9), (0.3, 1e-10)):
+        ref = H.newton_case(n, m, d, chord=c)
+        th64 = H.gadmm_logistic_newton(X, y, rho, lam, K, np.float64, H.NEWTON_TOL, c)[0][-1]
+        assert ref.err_theta(th64) <= ref.b_theta / 8
+        bad = np.array(th64)
+        bad[n - 1, d - 1] += off * ref.scale_theta
+        ratio = ref.err_theta(bad) / ref.b_theta
+        print("newton %s chord %.1f: one coordinate off by %.0e -> err / bound %.1f" % ((n, m, d), c, off, ratio))
+        assert ratio > 1.0
+
+
+def test_newton_reference_api():
+    X, y, rho, lam, _ = H.make_logistic(3, 5, 3, 1)
+    th, mu, ob, steps = H.gadmm_logistic_newton(X, y, rho, lam, 4)
+    assert th.dtype == mu.dtype == ob.dtype == H.LD and th.shape == (4, 3, 3) and mu.shape == (3, 3)
+    assert ob.shape == (4,) and steps.shape == (4, 3)
+    assert np.max(np.abs(mu.sum(axis=0))) < 1e-17 * float(np.max(np.abs(mu)) + 1)  # the duals sum to zero
+    with pytest.raises(ValueError):
+        H.gadmm_logistic_newton(X, y, rho, lam, 2, H.LD, 1e-17, 0.3)
+    # a run to iteration k is a prefix of a longer one: what newton_case(K = last) relies on
+    a, b = H.newton_case(3, 5, 3, K + 3), H.newton_case(3, 5, 3)
+    assert np.array_equal(a.theta[:K], b.theta) and np.array_equal(a.obj[:K], b.obj) and a.theta.shape[0] == K + 3
+    th2, mu2, _, _ = H.gadmm_logistic_newton(b.X, b.y, b.rho, b.lam, K)
+    assert np.array_equal(th2, b.theta) and np.array_equal(mu2, b.dual)
+    assert H.bound(0.0, 3, 5, 1e-14) == 8e-14 and H.chord_truncation(0.0, 2.0) == 0.0
+    assert abs(H.chord_truncation(0.3, 0.5) - 0.3 / 0.7 * 1e-13 / 0.5) < 1e-28
 
 
 @pytest.mark.parametrize("d", [1, 64, 256])
