@@ -68,7 +68,9 @@ __host__ __device__ __forceinline__ bool is_server_alg(int alg) {
 }
 
 // LDS layout (doubles) shared by host sizing (gadmm_fo_lds) and the kernel. `cache`: the replicated
-// server table (n rows of d, server algorithms only).
+// server table (n rows of d, server algorithms only). `red` is the scratch of every gemv_t_lds call:
+// NWV * C * 64 doubles for C lane chunks, and the logistic z = X theta runs with C = mc chunks of m
+// (mc > nc when d <= 64 < m), so it is sized by max(nc, mc), not by the d class alone.
 struct FoLds {
   int mat, xs, aux, red, wred, dl, cache, total;
   __host__ __device__ FoLds(int model, int alg, int n, int d, int m, int nc, int mc) {
@@ -78,7 +80,7 @@ struct FoLds {
     xs = (msz + 1) & ~1;
     aux = xs + 64 * nc;
     red = aux + 64 * nc;
-    wred = red + NWV * nc * 64;
+    wred = red + NWV * (nc > mc ? nc : mc) * 64;
     dl = wred + 8;
     cache = dl + 16;
     total = cache + (is_server_alg(alg) ? n * d : 0);
@@ -678,10 +680,13 @@ extern "C" int gadmm_xcd_pick(int want, int multi, int blocks, long cap_total, c
 extern "C" {
 
 static int fo_mc(int model, int m) { return model == FO_LINEAR ? 0 : (m <= 64 ? 1 : (m <= 128 ? 2 : 0)); }
+static int fo_nci(int d) { return d <= 64 ? 0 : 1; }
+
+// The instantiation gadmm_fo_launch picks, as nci * 3 + mc: fo_persistent_kernel<nci + 1, mc, .>.
+int gadmm_fo_kernel_class(int model, int d, int m) { return fo_nci(d) * 3 + fo_mc(model, m); }
 
 long gadmm_fo_lds(int model, int alg, int n, int d, int m) {
-  const int nc = d <= 64 ? 1 : 2;
-  const FoLds L(model, alg, n, d, m, nc, fo_mc(model, m));
+  const FoLds L(model, alg, n, d, m, fo_nci(d) + 1, fo_mc(model, m));
   long b = (long)L.total * 8;
   if (b < 16L * n + 64) b = 16L * n + 64;  // the monitor stages 2 doubles per worker
   return b;
@@ -729,7 +734,7 @@ int gadmm_fo_launch(const FoArgs* a, void* stream) {
         (const void*)fo_persistent_kernel<1, 2, true>},
        {(const void*)fo_persistent_kernel<2, 0, true>, (const void*)fo_persistent_kernel<2, 1, true>,
         (const void*)fo_persistent_kernel<2, 2, true>}}};
-  const int nci = a->d <= 64 ? 0 : 1;
+  const int nci = fo_nci(a->d);
   const void* fn = fns[multi ? 1 : 0][nci][mc];
   const int blocks = a->n_local + (a->has_monitor ? 1 : 0);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, (size_t)lds) != hipSuccess) return -4;

@@ -266,6 +266,8 @@ class FirstOrderEngine:
         ctl = native.FoCtl.from_buffer_copy(raw)
         pc = self.pushc.sum(0).cpu().numpy()
         rows, flags = float(pc[0]), float(pc[1])
+        kc = int(self.lib.gadmm_fo_kernel_class(a.model, self.d, self.m))  # the launcher's own choice
+        kern = "fo<%d,%d>" % (kc // 3 + 1, kc % 3)
         if not multi:
             if ctl.status == 4:
                 raise RuntimeError("first-order engine timed out (alg=%s, iters=%d)" % (alg, ctl.iters))
@@ -273,7 +275,7 @@ class FirstOrderEngine:
             return {"obj": obj[:k].cpu().numpy(), "cnt": cnt[:k].cpu().numpy(),
                     "times": tms[:k].cpu().numpy().astype(np.float64) / TICKS_PER_S, "iters": k,
                     "converged": ctl.status == 1, "uploads": float(ctl.uploads), "theta": self.theta.clone(),
-                    "rows_pushed": 0, "flags_pushed": 0, "payload_bytes": 0, "wire_bytes": 0}
+                    "rows_pushed": 0, "flags_pushed": 0, "payload_bytes": 0, "wire_bytes": 0, "kernel": kern}
         # several ranks: agree on failure, then every rank takes the monitor's (rank 0's) result
         grp = _group(self.comm)
         bad = torch.tensor([1.0 if ctl.status == 4 else 0.0, rows, flags], dtype=torch.float64)
@@ -291,7 +293,7 @@ class FirstOrderEngine:
         return {"obj": body[0].numpy().copy(), "cnt": body[1].numpy().copy(), "times": body[2].numpy() / TICKS_PER_S,
                 "iters": k, "converged": int(hdr[1]) == 1, "uploads": float(hdr[2]), "theta": self.theta.clone(),
                 "rows_pushed": rows_all, "flags_pushed": flags_all, "payload_bytes": rows_all * self.d * 8,
-                "wire_bytes": rows_all * self.d * 16 + flags_all * 16}
+                "wire_bytes": rows_all * self.d * 16 + flags_all * 16, "kernel": kern}
 
     def close(self):
         if self.fab is not None:

@@ -239,6 +239,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_chain_blocked_dyn_sweep_launch": (c_int, [ctypes.POINTER(PersistArgs), c_int, c_void_p, c_void_p,
                                                          c_void_p]),
         "gadmm_fo_lds": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+        "gadmm_fo_kernel_class": (c_int, [c_int, c_int, c_int]),
         "gadmm_fo_tab_granules": (c_long, [c_int, c_int, c_int]),
         "gadmm_fo_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
         "gadmm_fo_launch": (c_int, [ctypes.POINTER(FoArgs), c_void_p]),

@@ -14,7 +14,10 @@ specification), in the form the kernels evaluate them:
 * the exact logistic prox (``gadmm_logistic_newton``) has no oracle counterpart: it follows the header
   of csrc/kernels/chain_newton.hip and is held against the torch path (models/logistic.py:newton_prox)
   by tests/test_hp_reference_cpu.py. Its long-double run is the converged prox (stop tolerance 1e-17);
-  the float64 run stops as the kernels do (1e-13), optionally under their chord rule.
+  the float64 run stops as the kernels do (1e-13), optionally under their chord rule;
+* the first-order baselines (``first_order``) follow the torch path (algorithms/baselines.py,
+  dual_averaging.py), quirks included, with the scalar inputs (step, Hmax_n^2, LAG's threshold factor,
+  IAG's schedule) computed once in float64 and shared with the engines.
 
 This is a helper module, not a conftest: test modules import it as ``import hp_reference``.
 """
@@ -315,11 +318,12 @@ def noise_level(ref_ld, ref_f64, scale):
     return float(np.max(diff)) if diff.size else 0.0
 
 
-def bound(e64, d, m_logistic=0, truncation=0.0):
-    """``FACTOR * max(e64, max(d, m_logistic, 16) * 2^-53, truncation)``: the float64 noise of the
+def bound(e64, d, m_logistic=0, truncation=0.0, n=0):
+    """``FACTOR * max(e64, max(d, m_logistic, n, 16) * 2^-53, truncation)``: the float64 noise of the
     recurrence, with the standard dot-product bound as the floor for runs that happen to round luckily.
-    ``truncation``: what a stop rule of the kernel admits beyond rounding (``chord_truncation``)."""
-    return FACTOR * max(float(e64), max(int(d), int(m_logistic), 16) * 2.0 ** -53, float(truncation))
+    ``truncation``: what a stop rule of the kernel admits beyond rounding (``chord_truncation``); ``n``:
+    the worker count where a step sums n rows (the first-order server step), 0 elsewhere."""
+    return FACTOR * max(float(e64), max(int(d), int(m_logistic), int(n), 16) * 2.0 ** -53, float(truncation))
 
 
 def chord_truncation(chord, scale_theta):
@@ -467,3 +471,307 @@ def newton_case(n, m, d, K=K_ITERS, chord=0.0):
         ref.X, ref.y, ref.lam, ref.chord, ref.steps64 = X, y, lam, float(chord), steps64[:K]
         return ref
     return _cached(("newton", n, m, d, K, float(chord)), build)
+
+
+# ------------------------------------------------------------------------------------------------
+# First-order baselines (tests/test_gpu_first_order_classes.py): GD, DGD, LAG-PS, LAG-WK, IAG and dual
+# averaging as gadmm_amd/algorithms/baselines.py and dual_averaging.py run them (the torch path, which
+# follows GD_DGD_LAG.m and dual_averaging.m), every operation in ``dtype``.
+FO_K = 80  # > ring + 3 = 67 IAG table slots and > 64 objective-ring slots; LAG decides from iteration 11
+FO_ALGS = ("GD", "DGD", "LAG-PS", "LAG-WK", "cIAG", "R-IAG", "DualAvg", "DualAvg-J")
+FO_TRIGGERSLOT = 10
+
+
+def _fo_eval(kind, X, y, lam, dtype):
+    """``ev(TH) -> (f (N,), g (N, d))``: every worker's objective and gradient at its row of ``TH``.
+    Linear: the Gram form, Gram formed in ``dtype``; logistic: softplus / sigmoid on the shard."""
+    half = np.asarray(0.5, dtype=dtype)
+    if kind == "linear":
+        A, b, yy = _gram(X, y, dtype)
+
+        def ev(TH):
+            At = np.einsum("nij,nj->ni", A, TH)
+            return half * np.sum(At * TH, axis=1) - np.sum(b * TH, axis=1) + half * yy, At - b
+        return ev
+    X = np.asarray(X, dtype=dtype)
+    y = np.asarray(y, dtype=dtype)
+    lam = np.asarray(lam, dtype=dtype)
+    one = np.asarray(1.0, dtype=dtype)
+
+    def ev(TH):
+        z = np.einsum("nmd,nd->nm", X, TH)
+        f = np.sum(np.log1p(np.exp(-y * z)), axis=1) + lam * half * np.sum(TH * TH, axis=1)
+        return f, -np.einsum("nmd,nm->nd", X, y / (one + np.exp(y * z))) + lam * TH
+    return ev
+
+
+def first_order(alg, X, y, K, step, kind="linear", lam=0.0, thrd=0.0, hsq=None, sched=None, jacobi=False,
+                faithful=True, dtype=LD, scale_history=None, ev=None):
+    """``K`` iterations of ``alg`` in GD, DGD, LAG-PS, LAG-WK, IAG, DualAvg from theta = 0. ``step`` is
+    the step the update applies (what ``engine.run`` takes: alpha, alpha / 100 for DGD, alpha / N for
+    IAG); ``thrd`` / ``hsq`` LAG's threshold factor and Hmax_n^2; ``sched`` IAG's refreshing worker per
+    iteration. The quirks of the torch path: the server table (and DGD's gradients when ``faithful``)
+    start as ones; ``faithful`` GD's first step is ones (linear) or worker 0's gradient (logistic);
+    ``faithful`` LAG-PS refreshes worker 0 every iteration > 1 without counting an upload; LAG decides
+    nothing before iteration 11. ``scale_history = (it, c)`` multiplies LAG's recorded
+    ``|theta^it - theta^{it-1}|^2`` by c (a wrong entry of the kernels' step ring). ``ev``: a prebuilt
+    ``_fo_eval`` of the same data and dtype.
+    Returns a dict: ``obj`` (K,), ``theta`` after iteration K ((d,) server algorithms, (N, d) DGD and
+    dual averaging), ``scale`` = max |theta| over the run, and for LAG ``cnt`` (K,) uploads per
+    iteration, ``mask`` (K, N), ``margin`` = the smallest ``|lhs - rhs| / max(|lhs|, |rhs|)`` of any
+    trigger decision (0 / 0 skipped)."""
+    N, m, d = np.shape(X)
+    if ev is None:
+        ev = _fo_eval(kind, X, y, lam, dtype)
+    step = np.asarray(step, dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    out = {"obj": obj}
+    scale = 0.0
+    ones_t = np.ones((N, d), dtype=dtype)
+
+    def rows(theta):
+        return np.broadcast_to(theta, (N, d))
+
+    if alg == "GD":
+        theta = np.zeros(d, dtype=dtype)
+        for it in range(1, K + 1):
+            f, G = ev(rows(theta))
+            if it == 1 and faithful:
+                g = np.ones(d, dtype=dtype) if kind == "linear" else G[0]
+            else:
+                g = np.sum(G, axis=0)
+            obj[it - 1] = np.sum(f)
+            theta = theta - step * g
+            scale = max(scale, float(np.max(np.abs(theta))))
+    elif alg == "DGD":
+        theta = np.zeros((N, d), dtype=dtype)
+        G = ones_t.copy() if faithful else np.zeros((N, d), dtype=dtype)
+        half, third = np.asarray(0.5, dtype=dtype), np.asarray(1.0, dtype=dtype) / np.asarray(3.0, dtype=dtype)
+        for it in range(1, K + 1):
+            f, g = ev(theta)
+            if it > 1 or not faithful:
+                G = g
+            obj[it - 1] = np.sum(f)
+            new = np.empty_like(theta)
+            for w in range(N):
+                if N == 1:
+                    new[w] = theta[w] - step * G[w]
+                elif w == 0:
+                    new[w] = theta[w] - half * step * (G[w] + G[w + 1])
+                elif w == N - 1:
+                    new[w] = theta[w] - half * step * (G[w] + G[w - 1])
+                else:
+                    new[w] = theta[w] - third * step * (G[w] + G[w + 1] + G[w - 1])
+            theta = new
+            scale = max(scale, float(np.max(np.abs(theta))))
+    elif alg in ("LAG-PS", "LAG-WK"):
+        ps = alg == "LAG-PS"
+        thrd = np.asarray(thrd, dtype=dtype)
+        hloc = np.asarray(hsq, dtype=dtype)
+        table, G = ones_t.copy(), ones_t.copy()
+        theta_hat = np.zeros((N, d), dtype=dtype)
+        theta = np.zeros(d, dtype=dtype)
+        dl = {}  # |theta^k - theta^{k-1}|^2, k = 1 .. (the kernels' ring of the last ten)
+        cnt = np.zeros((K,), dtype=np.float64)
+        masks = np.zeros((K, N), dtype=bool)
+        margin = np.inf
+        for it in range(1, K + 1):
+            f, g = ev(rows(theta))
+            mask = np.zeros(N, dtype=bool)
+            if it > FO_TRIGGERSLOT:
+                trig = np.zeros((), dtype=dtype)
+                for k in range(1, FO_TRIGGERSLOT + 1):
+                    trig = trig + dl[it - k]
+                lhs = hloc * np.sum((theta_hat - theta) ** 2, axis=1) if ps else np.sum((g - G) ** 2, axis=1)
+                rhs = thrd * trig
+                mask = lhs > rhs
+                big = np.maximum(np.abs(lhs), np.abs(rhs))
+                live = big > 0
+                if np.any(live):
+                    margin = min(margin, float(np.min(np.abs(lhs - rhs)[live] / big[live])))
+            G[mask] = g[mask]
+            if ps:
+                theta_hat[mask] = theta
+            upd = mask.copy()
+            if ps and faithful and it > 1:  # the forced refresh of worker 0: no upload counted
+                G[0] = g[0]
+                upd[0] = True
+            table[upd] = G[upd]
+            cnt[it - 1] = int(mask.sum())
+            masks[it - 1] = mask
+            obj[it - 1] = np.sum(f)
+            new = theta - step * np.sum(table, axis=0)
+            dl[it] = np.sum((new - theta) ** 2)
+            if scale_history is not None and scale_history[0] == it:
+                dl[it] = dl[it] * np.asarray(scale_history[1], dtype=dtype)
+            theta = new
+            scale = max(scale, float(np.max(np.abs(theta))))
+        out.update(cnt=cnt, mask=masks, margin=margin)
+    elif alg == "IAG":
+        table = ones_t.copy()
+        theta = np.zeros(d, dtype=dtype)
+        for it in range(1, K + 1):
+            f, g = ev(rows(theta))
+            w = int(sched[it - 1])
+            if it > 1:
+                table[w] = g[w]
+            obj[it - 1] = np.sum(f)
+            theta = theta - step * np.sum(table, axis=0)
+            scale = max(scale, float(np.max(np.abs(theta))))
+    elif alg == "DualAvg":
+        theta = np.zeros((N, d), dtype=dtype)
+        Z = np.zeros((N, d), dtype=dtype)
+        half = np.asarray(0.5, dtype=dtype)
+        for it in range(1, K + 1):
+            _, g = ev(theta)
+            Zp = Z.copy()
+            for w in range(N):
+                left = None if w == 0 else (Zp[w - 1] if jacobi else Z[w - 1])
+                right = None if w == N - 1 else Zp[w + 1]
+                if left is None and right is None:
+                    zn = g[w].copy()
+                elif left is None:
+                    zn = right + g[w]
+                elif right is None:
+                    zn = left + g[w]
+                else:
+                    zn = half * right + half * left + g[w]
+                Z[w] = zn
+            theta = -step * Z
+            obj[it - 1] = np.sum(ev(theta)[0])
+            scale = max(scale, float(np.max(np.abs(theta))))
+    else:
+        raise ValueError("first_order: unknown algorithm %r" % (alg,))
+    out.update(theta=theta, scale=scale)
+    return out
+
+
+def fo_constants(kind, X, y, lam):
+    """The scalar inputs of a first-order run, once, in float64 (``baselines.global_constants`` /
+    ``model.hmax``): ``(step = 1 / Hmax_all, hmax (N,))``. The very same values go to the reference and
+    to the engines, which take them as arguments: no eigenvalue solver stands between the two."""
+    G = np.einsum("nmi,nmj->nij", X, X)
+    ev_all = float(np.linalg.eigvalsh(G.sum(0))[-1])
+    ev_loc = np.array([float(np.linalg.eigvalsh(G[i])[-1]) for i in range(G.shape[0])])
+    if kind == "linear":
+        return 1.0 / ev_all, ev_loc
+    return 1.0 / (0.25 * ev_all + lam), 0.25 * np.abs(ev_loc) + lam
+
+
+def fo_run_args(alg, n, K, step, hmax):
+    """``(engine algorithm, keyword arguments)`` of variant ``alg`` (one of ``FO_ALGS``) for both
+    ``first_order`` and ``engine.run``: the step as the update applies it, LAG's ``thrd`` (as
+    ``baselines.lag``) and ``hsq``, IAG's schedule (``baselines.iag_schedule``, seed 7), ``jacobi``."""
+    if alg == "GD":
+        return "GD", {"step": step}
+    if alg == "DGD":
+        return "DGD", {"step": step / 100.0}
+    if alg in ("LAG-PS", "LAG-WK"):
+        thrd = (10.0 if alg == "LAG-PS" else 1.0) / (step ** 2 * n ** 2) / FO_TRIGGERSLOT
+        return alg, {"step": step, "thrd": thrd, "hsq": hmax ** 2}
+    if alg in ("cIAG", "R-IAG"):
+        import torch
+        from gadmm_amd.algorithms.baselines import iag_schedule
+        sched = iag_schedule(n, K, "cyclic" if alg == "cIAG" else "random", torch.from_numpy(np.array(hmax)), 7)
+        return "IAG", {"step": step / n, "sched": sched}
+    if alg in ("DualAvg", "DualAvg-J"):
+        return "DualAvg", {"step": step, "jacobi": alg == "DualAvg-J"}
+    raise ValueError(alg)
+
+
+def _fo_data(kind, n, m, d, seed_offset):
+    """Data, constants and the two ``_fo_eval`` closures of a shape, shared by its eight algorithms."""
+    def build():
+        seed = seed_of(n, m, d) + seed_offset
+        if kind == "linear":
+            X, y, _ = make_linear(n, m, d, seed)
+            lam = 0.0
+        else:
+            X, y, _, lam, _ = make_logistic(n, m, d, seed)
+        _freeze(X, y)
+        step, hmax = fo_constants(kind, X, y, lam)
+        _freeze(hmax)
+        return X, y, lam, step, hmax, _fo_eval(kind, X, y, lam, LD), _fo_eval(kind, X, y, lam, np.float64)
+    return _cached(("fo-data", kind, n, m, d, seed_offset), build)
+
+
+class FoCase:
+    """One first-order case: the data, the run arguments, the long-double run (``ld``), the float64
+    run of the same recurrence (``f64``) and the bounds from them. ``theta`` / ``obj`` / ``cnt`` /
+    ``mask`` / ``margin`` are the long-double run's; ``e_obj`` (relative per trace entry) and
+    ``e_theta`` (over ``scale_theta`` = max |theta| of the run) the float64 noise; ``b_obj`` /
+    ``b_theta`` = ``bound(e64, d, m_logistic, n=n)``."""
+
+    def __init__(self, kind, alg, n, m, d, K, faithful, seed_offset):
+        X, y, lam, step, hmax, ev_ld, ev_64 = _fo_data(kind, n, m, d, seed_offset)
+        self.kind, self.variant, self.n, self.m, self.d, self.K, self.faithful = kind, alg, n, m, d, K, faithful
+        self.X, self.y, self.lam, self.step0, self.hmax = X, y, lam, step, hmax
+        self.alg, self.args = fo_run_args(alg, n, K, step, hmax)
+        kw = dict(self.args, kind=kind, lam=lam, faithful=faithful)
+        self.ld = first_order(self.alg, X, y, K, dtype=LD, ev=ev_ld, **kw)
+        self.f64 = first_order(self.alg, X, y, K, dtype=np.float64, ev=ev_64, **kw)
+        for r in (self.ld, self.f64):
+            _freeze(*[v for v in r.values() if isinstance(v, np.ndarray)])
+        self.obj, self.theta, self.scale_theta = self.ld["obj"], self.ld["theta"], self.ld["scale"]
+        self.cnt, self.mask, self.margin = self.ld.get("cnt"), self.ld.get("mask"), self.ld.get("margin")
+        self.uploads = None if self.cnt is None else float(self.cnt.sum())
+        self.e_obj = noise_level(self.obj, self.f64["obj"], np.abs(self.obj))
+        self.e_theta = noise_level(self.theta, self.f64["theta"], self.scale_theta)
+        ml = m if kind == "logistic" else 0
+        self.b_obj, self.b_theta = bound(self.e_obj, d, ml, n=n), bound(self.e_theta, d, ml, n=n)
+
+    def err_obj(self, obj):
+        obj = np.asarray(obj)
+        return noise_level(self.obj[:len(obj)], obj, np.abs(self.obj[:len(obj)]))
+
+    def err_theta(self, theta):
+        """``theta`` (d,) or (N, d) (a server algorithm's replicated rows: each against the one
+        reference row) over ``scale_theta``."""
+        return noise_level(np.broadcast_to(self.theta, np.shape(theta)), theta, self.scale_theta)
+
+
+# Per-shape seed offsets, changed only when a case misses the noise cap or a LAG condition of
+# tests/test_hp_reference_cpu.py (none widened; every change is recorded here with its reason).
+FO_SEED_OFFSET = {}
+
+
+def first_order_case(kind, alg, n, m, d, K=FO_K, faithful=True):
+    """The cached ``FoCase`` of variant ``alg`` (one of ``FO_ALGS``) on ``make_linear`` /
+    ``make_logistic(n, m, d, seed_of(n, m, d))`` (``lam = 1e-3`` as ``make_logistic`` returns it)."""
+    off = FO_SEED_OFFSET.get((kind, n, m, d), 0)
+    return _cached(("fo", kind, alg, n, m, d, K, bool(faithful), off),
+                   lambda: FoCase(kind, alg, n, m, d, K, bool(faithful), off))
+
+
+# The shapes of tests/test_gpu_first_order_classes.py (why each is there is written next to that
+# file's parameter lists).
+FO_LINEAR_SHAPES = [(2, 3, 1), (3, 7, 3), (5, 70, 64), (4, 80, 65), (3, 150, 128), (1, 5, 3), (33, 8, 4), (65, 6, 3),
+                    (253, 4, 2), (256, 4, 2)]
+FO_LINEAR_WIDE = (257, 4, 2)  # DGD and dual averaging only: the server algorithms stop at n = 256
+FO_LOGISTIC_SHAPES = [(3, 5, 3), (3, 64, 20), (3, 65, 20), (3, 128, 64), (4, 70, 60), (3, 129, 20), (2, 60, 65),
+                      (2, 66, 128), (2, 130, 70), (33, 6, 3)]
+FO_BIG_SHAPES = [(1, 140, 129), (3, 140, 129), (3, 270, 256), (3, 270, 257), (3, 60, 50)]
+FO_LIVE_STOP_AT = 40
+# (variant, n, m, d, faithful) of the live stop rule: the persistent engine's monitor at (3, 7, 3) and
+# the large-d engine's device stop rule at d = 129. GD and DGD run with faithful=False: the faithful
+# first step along ones moves AWAY from the optimum, and the stop rule's gaps must decrease from the
+# start (dual averaging has no such quirk).
+FO_LIVE_STOP = [("GD", 3, 7, 3, False), ("DGD", 3, 7, 3, False), ("DualAvg", 3, 7, 3, True),
+                ("GD", 3, 140, 129, False)]
+
+
+def fo_algs(n):
+    """The variants run at worker count ``n``. LAG-WK is left out at n = 1: its trigger compares a
+    gradient change of the one worker with its own step history, the run is a feedback loop on a single
+    comparison and its float64 noise (theta: 2.8e-9 at linear (1, 5, 3)) is far above the 1e-12 cap.
+    At n >= 65 the randomized schedule stands for IAG: in 80 iterations the cyclic one never reaches a
+    row beyond 80."""
+    return [a for a in FO_ALGS if not (n == 1 and a == "LAG-WK") and not (n >= 65 and a == "cIAG")]
+
+
+def fo_live_stop(case):
+    """``(obj0, tol, gaps)`` of a live stop rule on ``case``: ``obj0`` the long-double objective after
+    the last iteration, ``tol`` the midpoint of the gaps ``|obj_k - obj0|`` at iterations 39 and 40."""
+    gaps = np.abs(case.obj - case.obj[-1])
+    k = FO_LIVE_STOP_AT
+    return float(case.obj[-1]), float((gaps[k - 2] + gaps[k - 1]) / 2), gaps

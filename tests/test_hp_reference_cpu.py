@@ -1,5 +1,5 @@
-"""CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py
-and tests/test_gpu_newton_classes.py.
+"""CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py,
+tests/test_gpu_newton_classes.py and tests/test_gpu_first_order_classes.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
@@ -216,3 +216,156 @@ def test_bound_catches_what_a_wrong_kernel_does(n, m, d):
     Xb[0, :, d - 1] *= 1.0 + 1e-9  # the last column of worker 0's shard, nine digits in
     thb, mub, obb = H.gadmm_linear(Xb, y, rho, K, np.float64)
     assert ref.err_theta(thb[-1]) > ref.b_theta and ref.err_dual(mub) > ref.b_dual and ref.err_obj(obb) > ref.b_obj
+
+
+# ------------------------------------------------------------------------------------------------
+# First-order baselines (tests/test_gpu_first_order_classes.py). The references follow the torch path
+# (gadmm_amd/algorithms/baselines.py, dual_averaging.py), so the torch path on the CPU stands where a
+# kernel stands; dual averaging is also held against the oracle. Then the conditions on the inputs
+# that entitle the GPU tests to what they assert: LAG decisions far from a tie and of every kind,
+# float64 noise small enough for the bound to reject anything, and bounds that do reject.
+FO_CASES = [("linear",) + s for s in H.FO_LINEAR_SHAPES + [H.FO_LINEAR_WIDE] + H.FO_BIG_SHAPES] + \
+           [("logistic",) + s for s in H.FO_LOGISTIC_SHAPES]
+FO_UNFAITHFUL = [("linear", 3, 7, 3), ("logistic", 3, 5, 3)]
+FO_ALL = [c + (True,) for c in FO_CASES] + [c + (False,) for c in FO_UNFAITHFUL]
+FO_NOISE_CAP = 1e-12
+FO_MARGIN = 1e-9
+
+
+def _fo_torch(case):
+    """The torch path on the CPU with the case's own constants: ``(objective trace, per-iteration
+    upload counts or None, uploads or None)``."""
+    import torch
+    from gadmm_amd.algorithms import gradient_descent, decentralized_gd, lag, iag, dual_averaging
+    from gadmm_amd.models import LinearRegression, LogisticRegression
+    X, y = torch.from_numpy(np.array(case.X)), torch.from_numpy(np.array(case.y))
+    model = LinearRegression(X, y) if case.kind == "linear" else LogisticRegression(X, y, lam=case.lam)
+    n, K, s, f = case.n, case.K, case.step0, case.faithful
+    ids, hmax, v = list(range(n)), torch.from_numpy(np.array(case.hmax)), case.variant
+    if v == "GD":
+        r = gradient_descent(model, ids, n, K, 0.0, s, faithful=f, backend="torch")
+    elif v == "DGD":
+        r = decentralized_gd(model, ids, n, K, 0.0, s, faithful=f, backend="torch")
+    elif v.startswith("LAG"):
+        r = lag(model, ids, n, K, 0.0, s, hmax, v[4:], faithful=f, backend="torch")
+        comm = r.comm_units - np.arange(1, K + 1)  # 1 + the running upload count (no quiet unit: K < 1000)
+        return r.obj, np.diff(np.concatenate([[1.0], comm])), r.extra["uploads"]
+    elif v.endswith("IAG"):
+        r = iag(model, ids, n, K, 0.0, s, "cyclic" if v == "cIAG" else "random", hmax, 7, faithful=f, backend="torch")
+    else:
+        r = dual_averaging(model, ids, n, s, 0.0, 0.0, K, jacobi=v.endswith("-J"), backend="torch")
+    return r.obj, None, None
+
+
+@pytest.mark.parametrize("kind,n,m,d,faithful", FO_ALL)
+def test_first_order_reproduces_torch_path(kind, n, m, d, faithful):
+    for alg in H.fo_algs(n):
+        c = H.first_order_case(kind, alg, n, m, d, faithful=faithful)
+        obj, cnt, uploads = _fo_torch(c)
+        assert len(obj) == c.K == H.FO_K
+        r_ld = c.err_obj(obj) / c.b_obj
+        r_64 = H.noise_level(c.f64["obj"], obj, np.abs(c.obj)) / c.b_obj
+        print("%s %s %s faithful=%d: torch path err/bound objective %.3f (float64 run %.3f)"
+              % (kind, (n, m, d), alg, faithful, r_ld, r_64))
+        assert r_ld <= 1.0 and r_64 <= 1.0, (alg, r_ld, r_64)
+        if cnt is not None:
+            assert np.array_equal(cnt, c.f64["cnt"]) and np.array_equal(cnt, c.cnt), alg
+            assert uploads == c.uploads == float(c.f64["cnt"].sum()), alg
+    if n >= 2:  # the oracle's sweep reads Z[1]: no n = 1
+        c = H.first_order_case(kind, "DualAvg", n, m, d, faithful=faithful)
+        o = R.dual_averaging(np.array(c.X), np.array(c.y), c.K, 0.0, 0.0, c.step0,
+                             logistic_eta=c.lam if kind == "logistic" else None)
+        ro, rt = c.err_obj(np.asarray(o.obj)) / c.b_obj, c.err_theta(o.theta) / c.b_theta
+        print("%s %s DualAvg: oracle err/bound objective %.3f theta %.3f" % (kind, (n, m, d), ro, rt))
+        assert len(o.obj) == c.K and ro <= 1.0 and rt <= 1.0, (ro, rt)
+
+
+@pytest.mark.parametrize("kind,n,m,d,faithful", FO_ALL)
+def test_first_order_inputs_entitle_the_assertions(kind, n, m, d, faithful):
+    """Conditions on the inputs, not measurements. Every case: the float64 noise of every quantity is at
+    most 1e-12 (above that a bound rejects nothing; LAG-WK at n = 1 is left out for this, see
+    ``hp_reference.fo_algs``). Every LAG case: (a) the long-double and the float64 run take identical
+    masks, (b) no decision of the long-double run comes within 1e-9 (relative) of its threshold, so a
+    correct float64 kernel takes the same decisions and the GPU test may ask for equal counts, (c) after
+    iteration 10 some iteration uploads nothing and some uploads, (d) at n >= 33 some iteration uploads a
+    proper subset of the workers. A case that fails gets another seed offset
+    (``hp_reference.FO_SEED_OFFSET``), nothing is widened."""
+    for alg in H.fo_algs(n):
+        c = H.first_order_case(kind, alg, n, m, d, faithful=faithful)
+        print("%s %s %s faithful=%d: e64 objective %.2e theta %.2e%s"
+              % (kind, (n, m, d), alg, faithful, c.e_obj, c.e_theta,
+                 "" if c.cnt is None else ", margin %.2e, uploads %d" % (c.margin, c.uploads)))
+        assert c.e_obj <= FO_NOISE_CAP and c.e_theta <= FO_NOISE_CAP, (alg, c.e_obj, c.e_theta)
+        assert c.obj.dtype == H.LD and c.theta.dtype == H.LD and c.f64["obj"].dtype == np.float64
+        assert c.theta.shape == ((n, d) if alg in ("DGD", "DualAvg", "DualAvg-J") else (d,))
+        if c.cnt is None:
+            continue
+        assert np.array_equal(c.mask, c.f64["mask"]), alg                         # (a)
+        assert c.margin >= FO_MARGIN, (alg, c.margin)                              # (b)
+        assert np.all(c.cnt[:10] == 0)
+        late = c.cnt[10:]
+        assert np.any(late == 0) and np.any(late > 0), alg                         # (c)
+        if n >= 33:
+            assert np.any((late > 0) & (late < n)), alg                            # (d)
+
+
+def test_first_order_lag_wk_single_worker_is_left_out():
+    """Linear (1, 5, 3) LAG-WK misses the noise cap by orders of magnitude: it is not in ``fo_algs(1)``."""
+    assert "LAG-WK" not in H.fo_algs(1) and "LAG-WK" in H.fo_algs(2) and len(H.fo_algs(2)) == 8
+    assert "cIAG" not in H.fo_algs(65) and "R-IAG" in H.fo_algs(65) and "cIAG" in H.fo_algs(33)
+    c = H.first_order_case("linear", "LAG-WK", 1, 5, 3)
+    print("linear (1, 5, 3) LAG-WK: e64 objective %.2e theta %.2e" % (c.e_obj, c.e_theta))
+    assert max(c.e_obj, c.e_theta) > FO_NOISE_CAP
+
+
+@pytest.mark.parametrize("kind,alg,n,m,d", [("linear", "GD", 5, 70, 64), ("logistic", "LAG-WK", 4, 70, 60),
+                                            ("linear", "DualAvg", 3, 150, 128)])
+def test_first_order_bounds_reject_a_wrong_kernel(kind, alg, n, m, d):
+    """The float64 run, correct by construction, sits below 1/8 of the bounds; one coordinate of the
+    final theta, or one trace entry, off by 1e-9 relative lands above them; a step-history entry of LAG
+    off by a factor 2 (a stale or overwritten slot of the kernels' ring) changes the upload counts."""
+    c = H.first_order_case(kind, alg, n, m, d)
+    th, obj = np.array(c.f64["theta"]), np.array(c.f64["obj"])
+    assert c.err_theta(th) <= c.b_theta / 8 and c.err_obj(obj) <= c.b_obj / 8
+    th.reshape(-1)[-1] += 1e-9 * c.scale_theta
+    obj[c.K // 2] *= 1.0 + 1e-9
+    rt, ro = c.err_theta(th) / c.b_theta, c.err_obj(obj) / c.b_obj
+    print("%s %s %s: off by 1e-9 -> err/bound theta %.1f objective %.1f" % (kind, (n, m, d), alg, rt, ro))
+    assert rt > 1.0 and ro > 1.0
+    if c.cnt is not None:
+        bad = H.first_order(c.alg, c.X, c.y, c.K, kind=kind, lam=c.lam, dtype=np.float64, scale_history=(20, 2.0),
+                            **c.args)
+        assert np.array_equal(bad["cnt"][:20], c.cnt[:20]) and not np.array_equal(bad["cnt"], c.cnt)
+
+
+@pytest.mark.parametrize("alg,n,m,d,faithful", H.FO_LIVE_STOP)
+def test_first_order_live_stop_is_decided(alg, n, m, d, faithful):
+    """The live stop rule of the GPU tests (``fo_live_stop``): the gaps to the last objective decrease
+    strictly up to iteration 40, the two gaps around the tolerance differ by more than 1e-6 relative, and
+    the tolerance sits further from both than the objective bound reaches, so ``|obj - obj0| < tol`` first
+    holds at iteration 40 in any run within the bound. (GD and DGD run with ``faithful=False``: the
+    faithful first step along ones moves away from the optimum, the gap of iteration 2 is above that of 1.)"""
+    c = H.first_order_case("linear", alg, n, m, d, faithful=faithful)
+    obj0, tol, gaps = H.fo_live_stop(c)
+    k = H.FO_LIVE_STOP_AT
+    assert np.all(np.diff(gaps[:k]) < 0)
+    assert gaps[k - 1] < tol < gaps[k - 2] and (gaps[k - 2] - gaps[k - 1]) / gaps[k - 2] > 1e-6
+    reach = 2 * c.b_obj * float(np.max(np.abs(c.obj[k - 2:k])))  # err_obj is relative per trace entry
+    assert min(gaps[k - 2] - tol, tol - gaps[k - 1]) > reach
+    g64 = np.abs(c.f64["obj"] - obj0)
+    assert int(np.nonzero(g64 < tol)[0][0]) + 1 == k
+
+
+def test_first_order_reference_api():
+    assert H.bound(0.0, 3, n=256) == 8 * 256 * 2.0 ** -53 and H.bound(0.0, 3, n=5) == H.bound(0.0, 3)
+    assert H.bound(1e-13, 2, 0, 0.0, 256) == 8e-13 and H.bound(0.0, 40, 250, n=33) == 8 * 250 * 2.0 ** -53
+    c = H.first_order_case("logistic", "LAG-PS", 3, 5, 3)
+    assert c is H.first_order_case("logistic", "LAG-PS", 3, 5, 3) and c.lam == 1e-3 and c.alg == "LAG-PS"
+    assert c.args["thrd"] == 10.0 / (c.step0 ** 2 * 9) / 10 and np.array_equal(c.args["hsq"], c.hmax ** 2)
+    assert c.mask.shape == (H.FO_K, 3) and np.array_equal(c.mask.sum(1), c.cnt)
+    u = H.first_order_case("logistic", "LAG-PS", 3, 5, 3, faithful=False)
+    assert not np.array_equal(u.obj, c.obj)  # the forced refresh of worker 0 is a quirk of faithful runs
+    i = H.first_order_case("linear", "cIAG", 3, 7, 3)
+    assert i.alg == "IAG" and np.array_equal(i.args["sched"][:4], [1, 2, 0, 1]) and i.args["step"] == i.step0 / 3
+    with pytest.raises(ValueError):
+        H.first_order("SGD", i.X, i.y, 2, 0.1)
