@@ -11,11 +11,20 @@
 // while the row panel is W_Kj = sgn_j C_j^T (sgn = -1 for processed j < k0, +1 for j > K). Step K:
 //   1. C (d x nb) gathered from the lower triangle; P = W_KK; Pi = P^-1 (nb = 64: the in-register small
 //      inverse of spd_inverse.hip; nb = 128: this routine recursively with 64-blocks)
-//   2. Lc = C Pi                                                             [MFMA GEMM, d x nb x nb]
-//   3. lower tiles I >= J off K:  W_IJ -= sgn_J Lc_I C_J^T                   [MFMA rank-nb update]
+//   2. Lc0 = C Pi;  R0 = C - Lc0 P;  Lc = Lc0 + R0 Pi;  R = C - Lc P        [4 MFMA GEMMs, d x nb x nb]
+//   3. lower tiles I >= J off K:  W_IJ -= sgn_J (Lc_I C_J^T + R_I Lc_J^T)    [MFMA rank-2nb update]
 //   4. the K cross: W_iK = -Lc_i (i > K),  W_Kj = -Lc_j^T (j < k0),  W_KK = Pi
-// then the lower triangle is mirrored. Half the tiles of the full-matrix form, and at nb = 128 the
-// update does 16 flops per byte of W it streams.
+// then the lower triangle is mirrored. Half the tiles of the full-matrix form.
+//
+// Steps 2 and 3 are what keeps the blocked form as accurate as the unblocked one when a pivot block is
+// ill-conditioned (a Gram of m < d rows plus a small shift: the rank runs out inside a block). An explicit
+// inverse is not a backward-stable solve: Lc0 = C Pi carries an error dL that is not tied to C, and the
+// plain update Lc0 C^T puts dL C^T, about kappa^2 eps relative, into a trailing block that is itself only
+// 1 / kappa of W's scale. The residual-corrected panel brings dL down to kappa eps, and the symmetric form
+//   Lc C^T + (C - Lc P) Lc^T = C P^-1 C^T - dL P dL^T
+// has no first-order term in dL at all. Measured on rank-deficient Grams with 1e6 <= kappa <= 1e8 at
+// d = 129 .. 257 (profiles/setup_kernels): 1e-4 .. 1e-2 relative before, 1e-10 .. 4e-7 after, the level of
+// the unblocked kernel; well-conditioned inverses are unchanged to rounding. The update's K doubles.
 //
 // GEMM tile: 256 threads (4 waves, 2 x 2), a 64 x 64 output tile per workgroup, each wave 32 x 32 as
 // 2 x 2 v_mfma_f64_16x16x4_f64 tiles; K staged through LDS in chunks of 16 (A as [k][i], B as [k][j],
@@ -34,7 +43,7 @@ constexpr int GK = 16;        // K chunk
 constexpr int GLD = GT + 4;   // LDS row stride (doubles)
 constexpr int GNT = 256;
 
-// MODE 0: C (M x N) = A (M x K) B (K x N), row-major with leading dimensions.
+// MODE 0: C (M x N) = A (M x K) B (K x N), row-major with leading dimensions; s0 = +1 / -1: C += / -= A B.
 // MODE 1 (the Gauss-Jordan update, square M = N = d): B is read TRANSPOSED (B[j][k], ldb), only tiles
 // on or below the diagonal and off the pivot block [s0, s1) are touched: C -= sgn_J A B^T with
 // sgn_J = -1 for column tiles left of s0.
@@ -121,7 +130,8 @@ __global__ void __launch_bounds__(GNT) gemm_f64_kernel(int M, int N, int K, cons
         const int c = col0 + wc * 32 + y * 16 + (lane & 15);
         if (r >= M || c >= N) continue;
         double* cp = C + (long)r * ldc + c;
-        *cp = MODE == 0 ? acc[x][y][reg] : fma(-sg, acc[x][y][reg], *cp);
+        if (MODE == 0) *cp = s0 == 0 ? acc[x][y][reg] : fma(s0 > 0 ? 1.0 : -1.0, acc[x][y][reg], *cp);
+        else *cp = fma(-sg, acc[x][y][reg], *cp);
       }
 }
 
@@ -134,9 +144,10 @@ __global__ void shift_copy_kernel(const double* __restrict__ A, double s, int d,
   }
 }
 
-// P = W_KK from the lower triangle (nb x nb, contiguous, symmetric); C = the column panel
+// P = W_KK from the lower triangle (nb x nb, contiguous, symmetric); the column panel C into the left
+// half of CL = [C | Lc] and into the right half of LR = [Lc | R] (the residual starts as C); rows 2 nb long
 __global__ void panel_kernel(const double* __restrict__ W, int d, int k0, int nb, double* __restrict__ P,
-                             double* __restrict__ C) {
+                             double* __restrict__ CL, double* __restrict__ LR) {
   const long n = (long)d * nb;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
     const int i = (int)(e / nb), q = (int)(e - (long)i * nb);
@@ -147,18 +158,31 @@ __global__ void panel_kernel(const double* __restrict__ W, int d, int k0, int nb
       const int r = i - k0, hi = r > q ? r : q, lo = r > q ? q : r;
       P[r * nb + q] = W[(long)(k0 + hi) * d + k0 + lo];
     }
-    C[e] = v;
+    CL[(long)i * 2 * nb + q] = v;
+    LR[(long)i * 2 * nb + nb + q] = v;
   }
 }
 
-// the K cross: W_iK = -Lc_i (i > K), W_Kj = -Lc_j^T (j < k0), W_KK = Pi
-__global__ void cross_kernel(double* __restrict__ W, int d, int k0, int nb, const double* __restrict__ Lc,
+// after the refined panel: CL's right half = Lc (LR's left half), LR's right half = C again (the final
+// residual R = C - Lc P is formed in place there)
+__global__ void panel_swap_kernel(int d, int nb, double* __restrict__ CL, double* __restrict__ LR) {
+  const long n = (long)d * nb;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    const long i = e / nb, q = e - i * nb;
+    CL[i * 2 * nb + nb + q] = LR[i * 2 * nb + q];
+    LR[i * 2 * nb + nb + q] = CL[i * 2 * nb + q];
+  }
+}
+
+// the K cross: W_iK = -Lc_i (i > K), W_Kj = -Lc_j^T (j < k0), W_KK = Pi; Lc = the left half of LR (rows 2 nb)
+__global__ void cross_kernel(double* __restrict__ W, int d, int k0, int nb, const double* __restrict__ LR,
                              const double* __restrict__ Pi) {
   const long n = (long)d * nb;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
     const int i = (int)(e / nb), q = (int)(e - (long)i * nb);
-    if (i < k0) W[(long)(k0 + q) * d + i] = -Lc[e];
-    else if (i >= k0 + nb) W[(long)i * d + k0 + q] = -Lc[e];
+    const double lc = LR[(long)i * 2 * nb + q];
+    if (i < k0) W[(long)(k0 + q) * d + i] = -lc;
+    else if (i >= k0 + nb) W[(long)i * d + k0 + q] = -lc;
     else W[(long)i * d + k0 + q] = Pi[(i - k0) * nb + q];
   }
 }
@@ -184,23 +208,24 @@ int gemm_launch(int mode, int M, int N, int K, const double* A, int lda, const d
 inline int grid_for(long n) { return (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536); }
 
 long ws_doubles(int d, int nb) {
-  const long own = 2L * nb * nb + 2L * d * nb + 8;
+  const long own = 2L * nb * nb + 4L * d * nb + 8;
   return nb > 64 ? own + ws_doubles(nb, 64) : own;
 }
 
 // In place: W (d x d, full) -> W^-1 (full, symmetric). ws: ws_doubles(d, nb), ws[zero] = 0.
 int blocked_inplace(double* W, int d, int nb, double* ws, int* status, hipStream_t st) {
-  // layout: [zero(8) | P | Pi | C | Lc | inner level]; the zero slot (the small inverse's shift) sits at
-  // a fixed offset no call ever writes: C / Lc extents depend on the (recursive) call's d
+  // layout: [zero(8) | P | Pi | CL | LR | inner level]; the zero slot (the small inverse's shift) sits at
+  // a fixed offset no call ever writes: the CL / LR extents depend on the (recursive) call's d.
+  // CL = [C | Lc] and LR = [Lc | R], d rows of 2 b (b <= nb: the step's block width)
   double* zero = ws;
   double* P = zero + 8;
   double* Pi = P + (long)nb * nb;
-  double* C = Pi + (long)nb * nb;
-  double* Lc = C + (long)d * nb;
-  double* inner = Lc + (long)d * nb;
+  double* CL = Pi + (long)nb * nb;
+  double* LR = CL + 2L * d * nb;
+  double* inner = LR + 2L * d * nb;
   for (int k0 = 0; k0 < d; k0 += nb) {
     const int b = d - k0 < nb ? d - k0 : nb;
-    hipLaunchKernelGGL(panel_kernel, dim3(grid_for((long)d * b)), dim3(256), 0, st, W, d, k0, b, P, C);
+    hipLaunchKernelGGL(panel_kernel, dim3(grid_for((long)d * b)), dim3(256), 0, st, W, d, k0, b, P, CL, LR);
     GADMM_CHECK(hipGetLastError());
     int rc;
     if (b <= 64) {
@@ -209,9 +234,17 @@ int blocked_inplace(double* W, int d, int nb, double* ws, int* status, hipStream
       GADMM_CHECK(hipMemcpyAsync(Pi, P, sizeof(double) * b * b, hipMemcpyDeviceToDevice, st));
       if ((rc = blocked_inplace(Pi, b, 64, inner, status, st))) return rc;
     }
-    if ((rc = gemm_launch(0, d, b, b, C, b, Pi, b, Lc, b, 0, 0, st))) return rc;            // Lc = C Pi
-    if ((rc = gemm_launch(1, d, d, b, Lc, b, C, b, W, d, k0, k0 + b, st))) return rc;       // lower update
-    hipLaunchKernelGGL(cross_kernel, dim3(grid_for((long)d * b)), dim3(256), 0, st, W, d, k0, b, Lc, Pi);
+    const int b2 = 2 * b;
+    double* Lc = LR;      // left half of LR
+    double* R = LR + b;   // right half
+    if ((rc = gemm_launch(0, d, b, b, CL, b2, Pi, b, Lc, b2, 0, 0, st))) return rc;         // Lc0 = C Pi
+    if ((rc = gemm_launch(0, d, b, b, Lc, b2, P, b, R, b2, -1, 0, st))) return rc;          // R0 = C - Lc0 P
+    if ((rc = gemm_launch(0, d, b, b, R, b2, Pi, b, Lc, b2, 1, 0, st))) return rc;          // Lc = Lc0 + R0 Pi
+    hipLaunchKernelGGL(panel_swap_kernel, dim3(grid_for((long)d * b)), dim3(256), 0, st, d, b, CL, LR);
+    GADMM_CHECK(hipGetLastError());
+    if ((rc = gemm_launch(0, d, b, b, Lc, b2, P, b, R, b2, -1, 0, st))) return rc;          // R = C - Lc P
+    if ((rc = gemm_launch(1, d, d, b2, LR, b2, CL, b2, W, d, k0, k0 + b, st))) return rc;   // lower update
+    hipLaunchKernelGGL(cross_kernel, dim3(grid_for((long)d * b)), dim3(256), 0, st, W, d, k0, b, LR, Pi);
     GADMM_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(mirror_kernel, dim3(grid_for((long)d * d)), dim3(256), 0, st, W, d);

@@ -146,7 +146,7 @@ def _spd_solve(M: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
     real-shaped oracle, inside the timed set-up of the 10M x 10k config): Jacobi-preconditioned CG to a
     1e-13 relative residual when the Gram is well conditioned (a tall Gaussian shard: ~20 GEMVs of the
     d x d matrix, a few ms at d = 10k), else the native blocked Gauss-Jordan inverse (f64 MFMA,
-    csrc/kernels/spd_inverse_blocked.hip, ~50 ms at d = 10k) and one GEMV. rocSOLVER's potrf / trsv
+    csrc/kernels/spd_inverse_blocked.hip, ~70 ms at d = 10k) and one GEMV. rocSOLVER's potrf / trsv
     spent ~0.3 s there, mostly first-call library loading between their kernels, and was not
     deterministic with ranks sharing a GPU (profiles/r04_real10m)."""
     native_ok = getenv("GADMM_OPT_SOLVER", "native") != "rocsolver"

@@ -233,7 +233,8 @@ def spd_inverse(A: torch.Tensor, shifts: torch.Tensor, out: Optional[torch.Tenso
 def spd_inverse_blocked(A: torch.Tensor, shifts: torch.Tensor, out: Optional[torch.Tensor] = None, nb: int = 128,
                         check_status: bool = True, status: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Large-d ``(N, V, d, d)`` inverses of ``A_n + shifts[n, v] I`` on the device: blocked in-place
-    Gauss-Jordan, f64-MFMA rank-``nb`` updates (csrc/kernels/spd_inverse_blocked.hip)."""
+    Gauss-Jordan, residual-corrected panels and f64-MFMA rank-``2 nb`` updates (accurate to
+    ``kappa eps`` also when a pivot block is ill-conditioned; csrc/kernels/spd_inverse_blocked.hip)."""
     lib = native.require()
     shifts = torch.as_tensor(shifts, dtype=torch.float64)
     if shifts.dim() == 1:

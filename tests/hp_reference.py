@@ -17,7 +17,10 @@ specification), in the form the kernels evaluate them:
   the float64 run stops as the kernels do (1e-13), optionally under their chord rule;
 * the first-order baselines (``first_order``) follow the torch path (algorithms/baselines.py,
   dual_averaging.py), quirks included, with the scalar inputs (step, Hmax_n^2, LAG's threshold factor,
-  IAG's schedule) computed once in float64 and shared with the engines.
+  IAG's schedule) computed once in float64 and shared with the engines;
+* the set-up kernels (Grams, inverses) have exact references at the end of this file: integer data whose
+  Gram is known exactly (``exact_gram``, ``image_gram``) and the long-double inverse, with the kernels'
+  Gauss-Jordan recurrences in float64 (``gauss_jordan_inverse``) as the noise measure.
 
 This is a helper module, not a conftest: test modules import it as ``import hp_reference``.
 """
@@ -775,3 +778,396 @@ def fo_live_stop(case):
     gaps = np.abs(case.obj - case.obj[-1])
     k = FO_LIVE_STOP_AT
     return float(case.obj[-1]), float((gaps[k - 2] + gaps[k - 1]) / 2), gaps
+
+
+# ------------------------------------------------------------------------------------------------
+# Set-up kernels (tests/test_gpu_setup_kernels.py): the three Grams (csrc/kernels/gram.hip,
+# gram_ozaki.hip, gram_crt.hip) against EXACT integer Grams, the inverses (spd_inverse.hip,
+# spd_inverse_blocked.hip) against the long-double inverse with the float64 Gauss-Jordan recurrence of
+# the kernels as the noise measure.
+CRT_NMOD = 16   # moduli of gram_crt.hip: Garner's Horner evaluation rounds at most once per modulus
+IMAGE_BITS = 49  # bits of the int8 schemes' integer images (gram_crt.hip KB; 7 digits of 7 bits)
+
+
+def column_exponents(cols):
+    """The int8 Grams' documented column-exponent rule on the augmented columns ``cols`` (..., m, D):
+    the smallest e with ``max|x| <= 127/128 * 2^e`` (``frexp``, incremented when the fraction is above
+    127/128), and 0 for an all-zero column. Returns int64 (..., D)."""
+    mx = np.max(np.abs(np.asarray(cols, dtype=np.float64)), axis=-2)
+    f, e = np.frexp(mx)
+    e = np.where(f > 127.0 / 128.0, e + 1, e)
+    return np.where(mx > 0, e, 0).astype(np.int64)
+
+
+def _int_gram(N):
+    """``sum_i N_ia N_ib`` of int64 ``N`` (shards, m, D) as Python integers (object array): the values are
+    split into halves of at most 25 bits so that every int64 partial Gram is exact (asserted)."""
+    N = np.asarray(N, dtype=np.int64)
+    hi = (N + (1 << 24)) >> 25  # nearest: N = hi 2^25 + lo, |lo| <= 2^24
+    lo = N - (hi << 25)
+    big = max(int(np.max(np.abs(hi))), int(np.max(np.abs(lo))), 1)
+    assert N.shape[1] * big * big < 2 ** 63
+    g = lambda a, b: np.einsum("nmi,nmj->nij", a, b).astype(object)  # noqa: E731
+    return g(hi, hi) * (1 << 50) + (g(hi, lo) + g(lo, hi)) * (1 << 25) + g(lo, lo)
+
+
+class ExactGram:
+    """``X`` (shards, m, d), ``y`` (shards, m) float64; ``G`` the exact augmented Gram as Python integers
+    (object, shards x D x D); ``shift`` (shards, D) with ``x_ij = N_ij 2^shift_j``; ``image`` the float64
+    image ``G_ab 2^(shift_a + shift_b)`` (exact when every ``|G_ab| < 2^53``, else None); ``A``, ``b``,
+    ``yy`` its blocks; ``e`` the column exponents the int8 kernels must derive; ``N`` the integers."""
+
+    def __init__(self, N, shift, need_image):
+        N = np.asarray(N, dtype=np.int64)
+        shift = np.broadcast_to(np.asarray(shift, dtype=np.int64), (N.shape[0], N.shape[2]))
+        aug = np.ldexp(N.astype(np.float64), shift[:, None, :])   # exact: |N| < 2^53, a power-of-two scale
+        self.N, self.shift = N, np.array(shift)
+        self.X, self.y = np.ascontiguousarray(aug[:, :, :-1]), np.ascontiguousarray(aug[:, :, -1])
+        self.m, self.d = N.shape[1], N.shape[2] - 1
+        self.G = _int_gram(N)
+        self.e = column_exponents(aug)
+        self.pair_shift = self.shift[:, :, None] + self.shift[:, None, :]
+        self.image = self.A = self.b = self.yy = None
+        if need_image:
+            assert max(abs(int(v)) for v in self.G.reshape(-1)) < 2 ** 53   # the float64 image is exact
+            self.image = np.ldexp(self.G.astype(np.float64), self.pair_shift)
+            d = self.d
+            self.A, self.b, self.yy = self.image[:, :d, :d], self.image[:, d, :d], self.image[:, d, d]
+            _freeze(self.image)
+        _freeze(self.N, self.shift, self.X, self.y, self.e, self.pair_shift)
+
+    def unscale(self, A, b, yy):
+        """Kernel outputs (shards, d, d), (shards, d), (shards,) as the augmented (shards, D, D) matrix in
+        units of the integer Gram (an exact power-of-two scaling of every entry)."""
+        n, d = self.N.shape[0], self.d
+        out = np.empty((n, d + 1, d + 1), dtype=np.float64)
+        out[:, :d, :d], out[:, d, :d], out[:, :d, d], out[:, d, d] = A, b, b, yy
+        return np.ldexp(out, -self.pair_shift)
+
+
+def exact_gram(N_int, s):
+    """Integer data ``N_int`` (shards, m, d + 1; the last column is y) with per-column power-of-two
+    exponents ``s`` ((d + 1,) or (shards, d + 1)): ``X = N_int 2^s`` and the exact Gram with its float64
+    image, which is exact because every ``|G_ab| < 2^53`` (asserted). See ``ExactGram``."""
+    return ExactGram(N_int, s, True)
+
+
+def image_gram(N49, e):
+    """Full 49-bit images ``|N| < 2^49``, ``x = N 2^(e_j - 49)``: the exact integer Gram (Python integers)
+    and the column exponents the kernels derive from the data, which must be the intended ``e`` (the
+    generator pins each column's maximum; asserted). See ``ExactGram`` (``image`` is None)."""
+    N49 = np.asarray(N49, dtype=np.int64)
+    assert int(np.max(np.abs(N49))) < 2 ** IMAGE_BITS
+    e = np.broadcast_to(np.asarray(e, dtype=np.int64), (N49.shape[0], N49.shape[2]))
+    g = ExactGram(N49, e - IMAGE_BITS, False)
+    assert np.array_equal(g.e, e), "a column's maximum does not pin the intended exponent"
+    return g
+
+
+def gram_errors(g, A, b, yy, lower_only=False):
+    """Entrywise ``|out - exact| / (2^-53 |exact|)`` of kernel outputs against the exact integer Gram, in
+    exact rational arithmetic: ``(largest ratio over the entries with exact != 0, number of entries
+    with exact == 0 and out != 0)``. Integer-valued outputs compare as Python integers."""
+    U = g.unscale(A, b, yy)
+    worst, nonzero_at_zero = 0.0, 0
+    from fractions import Fraction
+    for n in range(U.shape[0]):
+        Un, Gn = U[n], g.G[n]
+        whole = Un == np.rint(Un)
+        for a in range(Un.shape[0]):
+            for c in range(a + 1 if lower_only else Un.shape[1]):
+                ex = Gn[a, c]
+                v = float(Un[a, c])
+                if ex == 0:
+                    nonzero_at_zero += v != 0.0
+                    continue
+                if not np.isfinite(v):
+                    return float("inf"), nonzero_at_zero
+                err = abs(int(v) - ex) if whole[a, c] else abs(Fraction(v) - ex)
+                worst = max(worst, float(Fraction(err * 2 ** 53, abs(ex))))
+    return worst, int(nonzero_at_zero)
+
+
+def range_statistic(g):
+    """``max_j colmax_j / sqrt(G_jj / m)`` per shard over the augmented columns with ``G_jj > 0`` (the
+    accuracy gate's statistic, linalg.gram), in long double from the exact Gram."""
+    out = np.zeros(g.N.shape[0], dtype=LD)
+    aug = np.abs(np.concatenate([g.X, g.y[:, :, None]], axis=2)).max(axis=1)
+    for n in range(g.N.shape[0]):
+        for j in range(g.d + 1):
+            gjj = int(g.G[n, j, j])
+            if gjj > 0:
+                ajj = np.ldexp(LD(gjj), int(2 * g.shift[n, j]))   # exact: G_jj < 2^53
+                out[n] = max(out[n], LD(aug[n, j]) / np.sqrt(ajj / LD(g.m)))
+    return out
+
+
+def integer_gram_case(shards, m, d, amp, seed=0):
+    """The integer-exact data family, cached: ``N_int`` uniform in ``[-amp, amp]`` with, as far as the
+    d + 1 columns allow (D >= 6: all; D = 4: the first four; D = 2: the first two), in this order
+
+    * a column whose largest magnitude is exactly ``127 2^k`` (the exponent rule's edge: not
+      incremented), the extreme NEGATIVE;
+    * one at ``255 2^k`` (incremented);
+    * an all-zero column;
+    * one at ``2^k``;
+    * two orthogonal columns, ``v = (u_1, -u_0, u_3, -u_2, ...)`` (a last odd row: 0): products that
+      cancel to an exact 0;
+
+    on the columns 0, D - 1 (y), D - 2 (the last feature), 1, 2, D - 3, rotated by the shard index, so
+    that the second shard of a call has them elsewhere (a stale exponent or maximum of the previous
+    shard shows). Column scales ``2^s``, s uniform in [-30, 30] per shard and column. ``k`` is the
+    largest with ``255 2^k <= amp``. ``m amp^2 < 2^53``: every partial sum in any order is exact."""
+    def build():
+        assert amp >= 255 and m * amp * amp < 2 ** 53 and amp <= 2 ** 20
+        rng = np.random.default_rng([seed, shards, m, d, amp])
+        D = d + 1
+        N = rng.integers(-amp, amp + 1, size=(shards, m, D), dtype=np.int64)
+        N[:, 0, :] = np.where(N[:, 0, :] == 0, 1, N[:, 0, :])   # no accidental all-zero column at m = 1
+        s = rng.integers(-30, 31, size=(shards, D), dtype=np.int64)
+        k = int(np.floor(np.log2(amp / 255.0)))
+        pos = [0, D - 1, D - 2, 1, 2, D - 3] if D >= 6 else list(range(D))
+        kinds = ["e127", "e255", "zero", "pow2", "orth"] if D >= 6 else ["e127", "e255", "zero", "pow2"][:D]
+        for n in range(shards):
+            p = pos[n % len(pos):] + pos[:n % len(pos)]
+            row = int(rng.integers(0, m))
+            for kind, c in zip(kinds, p):
+                if kind == "zero":
+                    N[n, :, c] = 0
+                elif kind == "orth":
+                    u = N[n, :, p[5]].copy()
+                    v = np.zeros_like(u)
+                    h = m // 2 * 2
+                    v[0:h:2], v[1:h:2] = u[1:h:2], -u[0:h:2]
+                    N[n, :, c] = v
+                else:
+                    top = {"e127": 127, "e255": 255, "pow2": 1}[kind] << k
+                    N[n, :, c] = np.clip(N[n, :, c], -top + 1, top - 1)
+                    N[n, row, c] = -top if kind == "e127" else top
+        return exact_gram(N, s)
+    return _cached(("int-gram", shards, m, d, amp, seed), build)
+
+
+def image_case(shards, m, d, seed=0):
+    """Full 49-bit images, cached: column j has the intended exponent ``e_j`` uniform in [-20, 20] and
+    holds ``+T``, ``-T`` (the largest image the exponent rule admits at that exponent, ``T = 127 2^42``:
+    ``max|x| = 127/128 2^e`` exactly, where the rule does not increment) and 0 when m >= 3, the rest
+    uniform in ``[-T, T]``."""
+    def build():
+        assert m >= 3
+        rng = np.random.default_rng([seed, shards, m, d, 49])
+        T = 127 << 42
+        D = d + 1
+        N = rng.integers(-T, T + 1, size=(shards, m, D), dtype=np.int64)
+        e = rng.integers(-20, 21, size=(shards, D), dtype=np.int64)
+        for n in range(shards):
+            for j in range(D):
+                r = rng.choice(m, size=3, replace=False)
+                N[n, r[0], j], N[n, r[1], j], N[n, r[2], j] = T, -T, 0
+        return image_gram(N, e)
+    return _cached(("image-gram", shards, m, d, seed), build)
+
+
+def _gj_plain(W):
+    """In place: Gauss-Jordan without pivoting in the kernels' operation order (spd_inverse.hip):
+    ``p = 1 / m_kk``; row k scaled; rank-1 update off row and column k; column k = ``-a_ik p``."""
+    d = W.shape[0]
+    for k in range(d):
+        p = 1.0 / W[k, k]
+        row = W[k, :] * p
+        col = W[:, k].copy()
+        row[k] = 0.0
+        col[k] = 0.0
+        W -= np.outer(col, row)
+        W[k, :] = row
+        W[:, k] = -col * p
+        W[k, k] = p
+    return W
+
+
+def _gj_blocked(W, nb):
+    """In place on the lower triangle, the scheme in the header of spd_inverse_blocked.hip: per pivot
+    block K the panel C (``W_iK`` below, ``-W_Ki'`` left of it), ``Pi = W_KK^-1`` (a block wider than 64
+    recurses with 64-blocks), the residual-corrected ``Lc0 = C Pi``, ``R0 = C - Lc0 P``,
+    ``Lc = Lc0 + R0 Pi``, ``R = C - Lc P``, the signed lower update
+    ``W_IJ -= sgn_J (Lc_I C_J' + R_I Lc_J')`` as one product of ``[Lc | R]`` and ``[C | Lc]``, the cross; then
+    the mirror."""
+    d = W.shape[0]
+    for k0 in range(0, d, nb):
+        b = min(nb, d - k0)
+        k1 = k0 + b
+        C = np.zeros((d, b))
+        C[:k0] = -W[k0:k1, :k0].T
+        C[k1:] = W[k1:, k0:k1]
+        P = np.tril(W[k0:k1, k0:k1])
+        P = P + np.tril(P, -1).T
+        Pi = gauss_jordan_inverse(P) if b <= 64 else _gj_blocked(P.copy(), 64)
+        Lc = C @ Pi
+        Lc = Lc + (C - Lc @ P) @ Pi
+        R = C - Lc @ P
+        sgn = np.where(np.arange(d) < k0, -1.0, 1.0)
+        W -= (np.hstack([Lc, R]) @ np.hstack([C, Lc]).T) * sgn[None, :]   # rows and columns of K: C is 0 there
+        W[k1:, k0:k1] = -Lc[k1:]
+        W[k0:k1, :k0] = -Lc[:k0].T
+        W[k0:k1, k0:k1] = Pi
+    L = np.tril(W)
+    W[:] = L + np.tril(L, -1).T
+    return W
+
+
+def gauss_jordan_inverse(M, nb=None):
+    """float64 NumPy inverse of the symmetric ``M`` by the kernels' recurrence: the noise measure of the
+    inverse tests, never their reference. ``nb = None``: spd_inverse.hip (plain Gauss-Jordan, then
+    ``0.5 (W + W')``); ``nb`` 64 or 128: spd_inverse_blocked.hip."""
+    W = np.array(M, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if nb is None:
+            _gj_plain(W)
+            return 0.5 * (W + W.T)
+        assert nb in (64, 128)
+        return _gj_blocked(W, nb)
+
+
+INVERSE_KINDS = ("well", "ill")
+_WELL_SHIFTS = (0.05, 0.11, 0.23, 0.4, 0.7, 1.3)   # times d: distinct per (worker, variant)
+_ILL_KAPPA = (3e6, 6e6, 1e7, 1.7e7, 3e7, 5e7)      # target condition numbers, distinct likewise
+
+
+class InverseMatrix:
+    """One shifted Gram ``M = fl(A + s I)`` (what the kernels form), its long-double inverse ``ref``,
+    ``kappa`` (2-norm, ``eigvalsh``), and per recurrence (``nb`` None / 64 / 128) the float64 noise
+    ``e64(nb) = max|gauss_jordan_inverse(M, nb) - ref| / max|ref|`` and the bound
+    ``FACTOR * max(e64, d 2^-53 kappa)``: the project's factor over the noise of the same recurrence,
+    floored by the forward error of a backward-stable inversion."""
+
+    def __init__(self, A, s):
+        d = A.shape[0]
+        self.d, self.A, self.s = d, A, float(s)
+        self.M = A + self.s * np.eye(d)
+        ev = np.linalg.eigvalsh(self.M)
+        assert ev[0] > 0
+        self.kappa = float(ev[-1] / ev[0])
+        self.ref = spd_inverse(self.M, LD)
+        self.scale = float(np.max(np.abs(self.ref)))
+        self._e64 = {}
+        _freeze(self.M, self.ref)
+
+    def err(self, X):
+        return noise_level(self.ref, X, self.scale)
+
+    def e64(self, nb=None):
+        if nb not in self._e64:
+            self._e64[nb] = self.err(gauss_jordan_inverse(self.M, nb))
+        return self._e64[nb]
+
+    def bound(self, nb=None):
+        return FACTOR * max(self.e64(nb), self.d * 2.0 ** -53 * self.kappa)
+
+    def self_error(self):
+        """The reference's own first-order error estimate ``max|X (M X - I)| / max|X|`` (long double)."""
+        X, M = self.ref, self.M.astype(LD)
+        return float(np.max(np.abs(X @ (M @ X - np.eye(self.d, dtype=LD)))) / LD(self.scale))
+
+
+def _inverse_gram(kind, d, seed, n):
+    def build():
+        rng = np.random.default_rng([seed, d, n, INVERSE_KINDS.index(kind)])
+        Z = rng.standard_normal((2 * d if kind == "well" else d // 2, d))
+        A = Z.T @ Z
+        A = 0.5 * (A + A.T)
+        _freeze(A)
+        return A, (float(np.linalg.eigvalsh(A)[-1]) if Z.shape[0] else 0.0)
+    return _cached(("inv-gram", kind, d, seed, n), build)
+
+
+def inverse_matrix(kind, d, seed, n, v, variants):
+    """The cached ``InverseMatrix`` of worker ``n``, variant ``v``. ``well``: ``Z'Z`` of 2d Gaussian rows
+    plus ``d * _WELL_SHIFTS[n variants + v]`` (kappa <= 100). ``ill``: the Gram of d // 2 rows, singular,
+    plus ``lambda_max / _ILL_KAPPA[...]``, so 1e6 <= kappa_2 <= 1e8 (asserted; d >= 2: a 1 x 1 matrix
+    has kappa 1)."""
+    def build():
+        A, lmax = _inverse_gram(kind, d, seed, n)
+        i = (n * variants + v) % len(_WELL_SHIFTS)
+        if kind == "well":
+            c = InverseMatrix(A, d * _WELL_SHIFTS[i])
+            assert c.kappa <= 100
+        else:
+            assert d >= 2
+            c = InverseMatrix(A, lmax / _ILL_KAPPA[i])
+            assert 1e6 <= c.kappa <= 1e8, c.kappa
+        return c
+    return _cached(("inv", kind, d, seed, n, v, variants), build)
+
+
+class InverseCase:
+    """``A`` (workers, d, d), ``shifts`` (workers, variants), ``mats[n][v]`` the ``InverseMatrix``."""
+
+    def __init__(self, kind, d, seed, workers, variants):
+        self.kind, self.d = kind, d
+        self.mats = [[inverse_matrix(kind, d, seed, n, v, variants) for v in range(variants)] for n in range(workers)]
+        self.A = np.stack([row[0].A for row in self.mats])
+        self.shifts = np.array([[c.s for c in row] for row in self.mats])
+
+    def ratios(self, out, nb=None, skip=()):
+        """``err / bound`` of every matrix of ``out`` (workers, variants, d, d) not in ``skip``."""
+        return {"n%dv%d" % (n, v): c.err(out[n, v]) / c.bound(nb)
+                for n, row in enumerate(self.mats) for v, c in enumerate(row) if (n, v) not in skip}
+
+
+def inverse_case(kind, d, seed=0, workers=3, variants=2):
+    """The cached inverse case of family ``kind`` (``well`` / ``ill``) at size ``d``: ``workers`` Grams
+    with ``variants`` distinct shifts each. A smaller case shares its matrices with a larger one of the
+    same ``variants`` (the long-double inverse is computed once per matrix)."""
+    return _cached(("inv-case", kind, d, seed, workers, variants),
+                   lambda: InverseCase(kind, d, seed, workers, variants))
+
+
+def non_spd_matrix(d, bad, seed=0, nan=False):
+    """A symmetric ``L D L'`` (unit lower-triangular L with small entries, D = 1 .. 2 except
+    ``D[bad] = -1``): the pivots of Gauss-Jordan without pivoting are D's entries (up to rounding, all
+    far from 0), so the first non-positive one is at index ``bad``. ``nan``: instead a well-conditioned
+    SPD matrix whose entry (bad, bad) is NaN."""
+    rng = np.random.default_rng([seed, d, bad, int(nan)])
+    L = np.tril(rng.uniform(-1, 1, (d, d)) / (2 * d), -1) + np.eye(d)
+    D = rng.uniform(1, 2, d)
+    if not nan:
+        D[bad] = -1.0
+    M = (L * D) @ L.T
+    M = 0.5 * (M + M.T)
+    if nan:
+        M[bad, bad] = np.nan
+    return M
+
+
+# The shapes of tests/test_gpu_setup_kernels.py (the edge each one sits on is written there).
+GRAM_AMP = 2 ** 20 - 1   # m amp^2 < 2^53 up to m = 8191; at most 3 non-zero base-128 digits per value
+GRAM_AMP_LONG = 1000     # the cases of more than one chunk
+GRAM_F64_D = (1, 62, 63, 64, 126, 127, 128, 129, 255)
+GRAM_F64_M = (1, 15, 16, 17, 33)
+GRAM_F64_SPLIT = ((40, 3), (33, 4), (512, 2), (513, 2))   # (m, ksplit)
+GRAM_F64_SPLIT_D = (3, 70)                                # both tile sizes
+GRAM_F64_AUTO = (2, 1025, 70)
+GRAM_OZ_D = (1, 62, 63, 64, 129)
+GRAM_OZ_M = (1, 31, 32, 33)
+GRAM_OZ_LONG = (8191, 8192, 8193, 16385)    # d = 3, 2 shards, amp 1000
+GRAM_CRT_D = (1, 254, 255, 256)
+GRAM_CRT_M = (1, 33, 64, 65, 128, 129, 192, 193, 256, 257, 320, 321)
+GRAM_CRT_LONG = (32768, 32769, 65537)       # d = 3, 2 shards, amp 1000
+GRAM_IMAGE = ((300, 5), (65, 255), (257, 256))
+INV_SMALL_D = (1, 2, 7, 8, 9, 63, 64)
+INV_GENERAL_D = (32, 33, 65, 90, 91, 127, 128)
+INV_BLOCKED_D = (129, 192, 193, 257)
+
+
+def gram_int_case(m, d):
+    """The integer case of shape (m, d) shared by the three kernels' tests: 2 shards; amplitude
+    ``GRAM_AMP`` while ``m amp^2 < 2^53``, else ``GRAM_AMP_LONG``."""
+    return integer_gram_case(2, m, d, GRAM_AMP if m * GRAM_AMP ** 2 < 2 ** 53 else GRAM_AMP_LONG)
+
+
+def gram_int_shapes():
+    """Every (m, d) at which tests/test_gpu_setup_kernels.py runs an integer case."""
+    out = {(m, d) for d in GRAM_F64_D for m in GRAM_F64_M} | {(m, d) for d in GRAM_F64_SPLIT_D for m, _ in GRAM_F64_SPLIT}
+    out |= {GRAM_F64_AUTO[1:]} | {(m, d) for d in GRAM_OZ_D for m in GRAM_OZ_M} | {(m, 3) for m in GRAM_OZ_LONG}
+    out |= {(m, d) for d in GRAM_CRT_D for m in GRAM_CRT_M} | {(m, 3) for m in GRAM_CRT_LONG}
+    return sorted(out)

@@ -1,5 +1,5 @@
 """CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py,
-tests/test_gpu_newton_classes.py and tests/test_gpu_first_order_classes.py.
+tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py and tests/test_gpu_setup_kernels.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
@@ -369,3 +369,292 @@ def test_first_order_reference_api():
     assert i.alg == "IAG" and np.array_equal(i.args["sched"][:4], [1, 2, 0, 1]) and i.args["step"] == i.step0 / 3
     with pytest.raises(ValueError):
         H.first_order("SGD", i.X, i.y, 2, 0.1)
+
+
+# ------------------------------------------------------------------------------------------------
+# Set-up kernels (tests/test_gpu_setup_kernels.py): the exact Grams and the inverse references, checked
+# here without a device, so that a failure there is the kernel's.
+import math  # noqa: E402
+from fractions import Fraction  # noqa: E402
+
+import test_gram_crt_math as CRT  # noqa: E402  (the slicer / Garner emulation; not copied)
+
+OZ_SL, OZ_KC = 7, 8192          # gram_ozaki.hip: digits per value, samples per chunk
+CRT_KC = 32768                  # gram_crt.hip: samples per chunk
+NMOD = H.CRT_NMOD
+
+
+def test_kernel_constants_match_the_sources():
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "csrc", "kernels")
+    oz, crt = open(os.path.join(src, "gram_ozaki.hip")).read(), open(os.path.join(src, "gram_crt.hip")).read()
+    assert int(re.search(r"constexpr int SL = (\d+);", oz).group(1)) == OZ_SL
+    assert int(re.search(r"constexpr int KC = (\d+);", oz).group(1)) == OZ_KC
+    assert int(re.search(r"constexpr int KC = (\d+);", crt).group(1)) == CRT_KC
+    assert int(re.search(r"constexpr int NMOD = (\d+);", crt).group(1)) == NMOD == len(CRT._tables()[0])
+    assert int(re.search(r"constexpr int KB = (\d+);", crt).group(1)) == H.IMAGE_BITS == 7 * OZ_SL
+
+
+@pytest.mark.parametrize("m,d", H.gram_int_shapes())
+def test_exact_gram_agrees_with_long_double_and_torch(m, d):
+    """The exact image equals the long-double Gram bit for bit (every sum is below 2^53, nothing
+    rounds), and, where the rows are few, the torch float64 Gram too. The family's edge columns are
+    where the docstring of ``integer_gram_case`` puts them."""
+    import torch
+    from gadmm_amd.ops import linalg
+    g = H.gram_int_case(m, d)
+    assert g.X.shape == (2, m, d) and g.image.shape == (2, d + 1, d + 1) and np.abs(g.shift).max() <= 30
+    A, b, yy = H._gram(g.X, g.y, H.LD)
+    assert np.array_equal(A, g.A.astype(H.LD)) and np.array_equal(b, g.b.astype(H.LD))
+    assert np.array_equal(yy, g.yy.astype(H.LD))
+    if m <= 64:
+        At, bt, yyt = linalg.gram_torch(torch.from_numpy(np.array(g.X)), torch.from_numpy(np.array(g.y)))
+        assert np.array_equal(At.numpy(), g.A) and np.array_equal(bt.numpy(), g.b) and np.array_equal(yyt.numpy(), g.yy)
+    assert np.array_equal(g.image, g.image.transpose(0, 2, 1)) and not np.array_equal(g.N[0], g.N[1])
+    if d + 1 >= 6:
+        D, k = d + 1, int(np.floor(np.log2(np.abs(g.N).max() / 255.0)))
+        pos = [0, D - 1, D - 2, 1, 2, D - 3]
+        for n in range(2):
+            e127, e255, zero, pow2, orth, u = pos[n:] + pos[:n]
+            top = np.abs(g.N[n]).max(axis=0)
+            assert top[e127] == 127 << k and g.N[n, :, e127].min() == -(127 << k)   # a negative extreme
+            assert top[e255] == 255 << k and top[zero] == 0 and top[pow2] == 1 << k
+            assert g.e[n, e127] == k + 7 + g.shift[n, e127]        # 127 2^k = 127/128 2^(k + 7): the edge
+            assert g.e[n, e255] == k + 9 + g.shift[n, e255]        # 255/256 > 127/128: incremented
+            assert g.e[n, pow2] == k + 1 + g.shift[n, pow2] and g.e[n, zero] == 0
+            assert g.G[n, orth, u] == 0 and g.image[n, orth, u] == 0.0
+            assert m < 2 or np.count_nonzero(g.N[n, :, orth] * g.N[n, :, u]) >= 2   # products that cancel
+
+
+def _digit_gram(g):
+    """gram_ozaki.hip on the CPU: the round-to-nearest base-128 digits of ``x 2^-e`` (the residual after
+    7 digits must be 0 on this family), the exact int32 level sums of the digit pairs with p + q <= 8 per
+    chunk, the recombination ``v = fma(level, 2^(-7 (L + 2)), v)`` smallest level first (the product is
+    a power-of-two scaling, so the fma is one rounded addition), ``C += ldexp(v, e_a + e_b)`` per
+    chunk. Integer arithmetic on integers (int64 NumPy, bounds asserted), floats where the kernel has floats."""
+    aug = np.concatenate([g.X, g.y[:, :, None]], axis=2)
+    out = np.zeros_like(g.image)
+    digits_used = 0
+    for n in range(aug.shape[0]):
+        v = np.ldexp(aug[n], -g.e[n][None, :])
+        assert np.abs(v).max() <= 127.0 / 128.0
+        dig = np.zeros((OZ_SL,) + v.shape, dtype=np.int64)
+        for p in range(OZ_SL):
+            v = v * 128.0
+            q = np.rint(v)
+            v = v - q
+            dig[p] = q.astype(np.int64)
+            assert np.abs(q).max() <= (127 if p == 0 else 64)
+            if np.any(q != 0):
+                digits_used = max(digits_used, p + 1)
+        assert not np.any(v), "a value of the integer family has more than 7 digits"
+        for c0 in range(0, g.m, OZ_KC):
+            chunk = dig[:, c0:c0 + OZ_KC]
+            lev = np.zeros((OZ_SL,) + g.image.shape[1:], dtype=np.int64)
+            for p in range(OZ_SL):
+                for q in range(OZ_SL - p):
+                    lev[p + q] += chunk[p].T @ chunk[q]
+            assert np.abs(lev).max() < 2 ** 31
+            acc = np.zeros(g.image.shape[1:])
+            for L in range(OZ_SL - 1, -1, -1):
+                acc = lev[L].astype(np.float64) * math.ldexp(1.0, -7 * (L + 2)) + acc
+            out[n] += np.ldexp(acc, g.e[n][:, None] + g.e[n][None, :])
+    return out, digits_used
+
+
+@pytest.mark.parametrize("m,d", [(m, d) for d in H.GRAM_OZ_D for m in H.GRAM_OZ_M] + [(m, 3) for m in H.GRAM_OZ_LONG])
+def test_digit_scheme_emulation_is_bit_exact_on_the_integer_family(m, d):
+    """What entitles the GPU test to ``torch.equal``: on this family the scheme's own arithmetic, done
+    correctly, reproduces the exact image bit for bit (at most 3 non-zero digits per value: no digit
+    pair is dropped and every partial sum is exact)."""
+    g = H.gram_int_case(m, d)
+    out, used = _digit_gram(g)
+    print("digits (m %d, d %d): %d digits used, %d mismatches" % (m, d, used, int(np.sum(out != g.image))))
+    assert used <= 3 and np.array_equal(out, g.image)
+
+
+def _crt_entry(Na, Nb, mods, inv, chunk):
+    """One Gram entry by gram_crt.hip's arithmetic (tests/test_gram_crt_math.py): int8 residues, chunk
+    sums reduced mod p into the balanced range, Garner, Horner in doubles."""
+    res = []
+    for p in mods:
+        ra = [CRT._residue(float(v), p) for v in Na]
+        rb = ra if Nb is Na else [CRT._residue(float(v), p) for v in Nb]
+        acc = 0
+        for c0 in range(0, len(ra), chunk):
+            acc = int(math.fmod(acc + sum(x * y for x, y in zip(ra[c0:c0 + chunk], rb[c0:c0 + chunk])), p))
+            hm = p >> 1
+            acc = acc - p if acc > hm else acc + p if acc < -hm else acc
+        res.append(acc)
+    return CRT._garner(res, mods, inv)[0]
+
+
+def _crt_emulation(g, rows=24, cols=6):
+    """The emulation on a subsample of ``g``: the rows that hold each column's extremes first, then the
+    leading ones, at most ``rows``; the family's edge columns, at most ``cols``. Per entry
+    ``(|val - exact| / (2^-53 |exact|), val != 0 at exact == 0)`` against the subsample's own exact Gram."""
+    mods, inv, kb, _ = CRT._tables()
+    D = g.d + 1
+    cs = sorted(set([0, D - 1, D - 2, 1, 2, D - 3][:cols]) & set(range(D)))
+    worst, bad_zero = 0.0, 0
+    for n in range(g.N.shape[0]):
+        img = g.N[n].astype(object) * np.array([2 ** int(kb - (g.e[n, j] - g.shift[n, j])) for j in range(D)], dtype=object)
+        assert max(abs(int(v)) for v in img.reshape(-1)) < 2 ** kb   # integers: e - shift <= 49 on both families
+        top = list(dict.fromkeys(int(i) for i in np.argmax(np.abs(g.N[n][:, cs]), axis=0)))
+        rs = (top + [i for i in range(g.m) if i not in top])[:rows]
+        for ia, a in enumerate(cs):
+            for c in cs[:ia + 1]:
+                Na, Nb = [int(img[i, a]) for i in rs], [int(img[i, c]) for i in rs]
+                exact = sum(x * y for x, y in zip(Na, Nb))
+                val = _crt_entry(Na, Na if a == c else Nb, mods, inv, 7)
+                if exact == 0:
+                    bad_zero += val != 0.0
+                else:
+                    worst = max(worst, float(abs(Fraction(val) - exact) * 2 ** 53 / abs(exact)))
+    return worst, bad_zero
+
+
+@pytest.mark.parametrize("m,d", [(m, d) for d in H.GRAM_CRT_D for m in H.GRAM_CRT_M] + [(m, 3) for m in H.GRAM_CRT_LONG])
+def test_crt_emulation_meets_the_gpu_bound_on_the_integer_family(m, d):
+    """The CRT scheme's own arithmetic on the GPU file's data (a subsample: the emulation is Python per
+    value and modulus) stays within NMOD 2^-53 |exact| entrywise and gives exactly 0 at an exact 0."""
+    worst, bad_zero = _crt_emulation(H.gram_int_case(m, d))
+    print("crt emulation (m %d, d %d): err / (2^-53 |exact|) %.2f of %d" % (m, d, worst, NMOD))
+    assert worst <= NMOD and bad_zero == 0
+
+
+@pytest.mark.parametrize("m,d", H.GRAM_IMAGE)
+def test_image_gram_and_its_crt_emulation(m, d):
+    g = H.image_case(2, m, d)
+    T = 127 << 42
+    assert g.image is None and np.all(np.abs(g.N).max(axis=1) == T) and np.all(np.abs(g.N).min(axis=1) == 0)
+    assert np.all(g.N.max(axis=1) == T) and np.all(g.N.min(axis=1) == -T) and np.all(g.shift == g.e - H.IMAGE_BITS)
+    assert int(g.G[1, d, 0]) == sum(int(a) * int(b) for a, b in zip(g.N[1, :, d], g.N[1, :, 0]))
+    worst, bad_zero = _crt_emulation(g)
+    print("crt emulation, 49-bit images (m %d, d %d): err / (2^-53 |exact|) %.2f of %d" % (m, d, worst, NMOD))
+    assert worst <= NMOD and bad_zero == 0
+
+
+def test_column_exponent_rule():
+    cols = np.array([[0.0, 127.0, 127.5, 128.0, -255.0, 1.0, 2.0 ** -40 * 127 / 128]]).repeat(3, axis=0)
+    cols[1] *= 0.5
+    assert list(H.column_exponents(cols)) == [0, 7, 8, 8, 9, 1, -40]
+    with pytest.raises(AssertionError):   # a maximum past 127/128 2^e does not pin the intended exponent
+        H.image_gram(np.array([[[2 ** 49 - 1, 5]]]), np.array([[3, 3]]))
+    with pytest.raises(AssertionError):   # an image Gram entry of 2^53 or more has no exact float64 image
+        H.exact_gram(np.full((1, 2, 2), 2 ** 26), np.zeros(2, dtype=np.int64))
+
+
+@pytest.mark.parametrize("m,d", [(33, 64), (1, 1), (8193, 3)])
+def test_gram_bounds_reject_a_wrong_kernel(m, d):
+    """The exact comparison rejects one entry off by one unit of its last place; the CRT bound, which
+    admits NMOD roundings by construction, rejects an entry off by one unit of the INTEGER Gram (every
+    ``|G| < 2^49`` on this family: one unit is above 16 * 2^-53 relative) and a value at an exact 0; both
+    reject a dropped row. The exact image itself passes both."""
+    g = H.gram_int_case(m, d)
+    assert H.gram_errors(g, g.A, g.b, g.yy) == (0.0, 0)
+    assert max(abs(int(v)) for v in g.G.reshape(-1)) < 2 ** 49
+    A = np.array(g.A)
+    j = int(np.argmax(np.abs(A[1]).max(axis=1) > 0))
+    A[1, j, j] = np.nextafter(A[1, j, j], np.inf)
+    assert not np.array_equal(A, g.A) and 1.0 <= H.gram_errors(g, A, g.b, g.yy)[0] <= 2.0
+    A[1, j, j] = g.A[1, j, j] + np.ldexp(1.0, int(2 * g.shift[1, j]))
+    worst, _ = H.gram_errors(g, A, g.b, g.yy)
+    print("gram (m %d, d %d): one integer unit on a diagonal entry -> %.1f x 2^-53 relative" % (m, d, worst))
+    assert worst > NMOD
+    zeros = np.argwhere(g.A[0] == 0.0)
+    if len(zeros):
+        A = np.array(g.A)
+        A[0, zeros[0][0], zeros[0][1]] = 2.0 ** -300
+        assert H.gram_errors(g, A, g.b, g.yy) == (0.0, 1)
+    # one row dropped (a tail the kernel never reads)
+    Ad, bd, yyd = H._gram(g.X[:, :-1], g.y[:, :-1], np.float64)
+    assert not np.array_equal(bd, g.b) or not np.array_equal(Ad, g.A) or not np.array_equal(yyd, g.yy)
+    assert H.gram_errors(g, Ad, bd, yyd)[0] > NMOD
+    r = H.range_statistic(g)
+    assert r.dtype == H.LD and np.all(r >= 1.0)
+
+
+# The inverse cases of the GPU file: (kind, d, workers, variants, recurrences).
+INV_CASES = [(k, d, 3, 2, (None,)) for d in H.INV_SMALL_D + H.INV_GENERAL_D for k in H.INVERSE_KINDS if (k, d) != ("ill", 1)]
+INV_CASES += [(k, d, w, v, (64, 128)) for d in H.INV_BLOCKED_D for k in H.INVERSE_KINDS for w, v in ((1, 1), (2, 2))]
+INV_CASES += [("well", 9, 3, 1, (None,)), ("well", 64, 3, 1, (None,)), ("well", 200, 3, 1, (64, 128))]   # status tests
+
+
+@pytest.mark.parametrize("kind,d,workers,variants,nbs", INV_CASES)
+def test_inverse_cases_and_gauss_jordan_reference(kind, d, workers, variants, nbs):
+    """Per matrix: kappa in the family's range (asserted when the case is built) and distinct shifts;
+    ``gauss_jordan_inverse`` (plain, nb = 64 and nb = 128: all three, whatever the GPU test uses) agrees
+    with ``np.linalg.inv`` to the bound of its recurrence; the long-double reference's own first-order
+    error estimate is at most 1/64 of the smallest bound."""
+    case = H.inverse_case(kind, d, workers=workers, variants=variants)
+    assert case.A.shape == (workers, d, d) and len(set(case.shifts.reshape(-1))) == workers * variants
+    for n, row in enumerate(case.mats):
+        for v, c in enumerate(row):
+            assert np.array_equal(c.M, case.A[n] + case.shifts[n, v] * np.eye(d)) and c.ref.dtype == H.LD
+            inv = np.linalg.inv(c.M)
+            for nb in (None, 64, 128):
+                X = H.gauss_jordan_inverse(c.M, nb)
+                assert np.array_equal(X, X.T)
+                assert H.noise_level(X, inv, c.scale) <= c.bound(nb), (n, v, nb)
+            smallest = min(c.bound(nb) for nb in (None, 64, 128))
+            assert smallest >= H.FACTOR * d * 2.0 ** -53 * c.kappa
+            se = c.self_error()
+            print("inverse %s d %d n%d v%d: kappa %.3g, e64 plain %.2e nb64 %.2e nb128 %.2e, reference's own error %.2e"
+                  " (%.1e of the smallest bound)" % (kind, d, n, v, c.kappa, c.e64(None), c.e64(64), c.e64(128), se,
+                                                     se / smallest))
+            assert se <= smallest / 64
+    assert set(nbs) <= {None, 64, 128}
+
+
+def test_blocked_reference_follows_the_recursion():
+    """nb = 128 at d = 193 has a 65-wide last block, which recurses with 64-blocks: the result differs
+    in rounding from nb = 64 and from the plain recurrence, and all three invert the matrix."""
+    c = H.inverse_case("well", 193, workers=1, variants=1).mats[0][0]
+    Xp, X64, X128 = (H.gauss_jordan_inverse(c.M, nb) for nb in (None, 64, 128))
+    assert not np.array_equal(X64, X128) and not np.array_equal(Xp, X64)
+    for X in (Xp, X64, X128):
+        assert np.max(np.abs(X @ c.M - np.eye(193))) < 1e-12
+    with pytest.raises(AssertionError):
+        H.gauss_jordan_inverse(c.M, 32)
+
+
+@pytest.mark.parametrize("d,nb", [(9, None), (64, None), (128, None), (193, 128), (257, 64)])
+def test_inverse_bounds_reject_a_wrong_kernel(d, nb):
+    """A ``well`` inverse with one entry moved by 1e-9 relative, and an ``ill`` inverse with one row
+    taken from the neighbouring variant, land above the bound; the float64 recurrence lands below."""
+    well = H.inverse_case("well", d, workers=2, variants=2) if d > 128 else H.inverse_case("well", d)
+    c = well.mats[1][1]
+    X = H.gauss_jordan_inverse(c.M, nb)
+    assert c.err(X) <= c.bound(nb) / H.FACTOR
+    X[d - 1, 0] += 1e-9 * c.scale
+    assert c.err(X) > c.bound(nb)
+    ill = H.inverse_case("ill", d, workers=2, variants=2) if d > 128 else H.inverse_case("ill", d)
+    c, nbr = ill.mats[1][0], ill.mats[1][1]
+    X = H.gauss_jordan_inverse(c.M, nb)
+    X[d // 2] = H.gauss_jordan_inverse(nbr.M, nb)[d // 2]
+    print("ill d %d: one row of the neighbouring variant -> err / bound %.3g" % (d, c.err(X) / c.bound(nb)))
+    assert c.err(X) > c.bound(nb)
+    out = np.stack([[H.gauss_jordan_inverse(m.M, nb) for m in row] for row in ill.mats])
+    assert all(r <= 1.0 / H.FACTOR + 1e-12 for r in ill.ratios(out, nb).values())
+    assert set(ill.ratios(out, nb)) - set(ill.ratios(out, nb, skip={(1, 0)})) == {"n1v0"}
+
+
+@pytest.mark.parametrize("d,bad", [(9, 0), (9, 4), (9, 8), (64, 32), (200, 150)])
+def test_non_spd_matrix_first_bad_pivot(d, bad):
+    """The pivots of Gauss-Jordan without pivoting on ``non_spd_matrix(d, bad)`` are positive before
+    index ``bad`` and negative at it, far from 0 (the kernels' rounding cannot move the index)."""
+    M = d * H.non_spd_matrix(d, bad)
+    assert np.array_equal(M, M.T)
+    W = M.copy()
+    piv = []
+    for k in range(d):
+        piv.append(W[k, k])
+        W[k + 1:, k + 1:] -= np.outer(W[k + 1:, k], W[k, k + 1:]) / W[k, k]
+    piv = np.array(piv) / d
+    assert np.all(piv[:bad] > 0.9) and piv[bad] < -0.9
+    Mn = H.non_spd_matrix(d, bad, nan=True)
+    assert np.isnan(Mn[bad, bad]) and np.isnan(Mn).sum() == 1
+    Mn[bad, bad] = 1.5
+    assert np.linalg.eigvalsh(Mn)[0] > 0.5
