@@ -183,7 +183,7 @@ struct PersistArgs {
   // XCC_ID into xchk ([XCHK] granules) and, if all agree, publish granules
   // with plain stores that stay in that XCD's L2 (MI355X_MICROARCH.md price list). The env
   // GADMM_XCD overrides xcd (A/B runs). xtag: the granules' tag, fresh per launch (set by the
-  // launcher, gadmm_next_xtag), so xchk needs no memset in front of the kernel (a 4.8 us fill on the
+  // launcher, gadmm_next_xtag in persist_launch.h), so xchk needs no memset in front of the kernel (a 4.8 us fill on the
   // GPU timeline of every solve, profiles/r06_dgadmm).
   u32x4* xchk;
   int xcd, xtag;

@@ -1,7 +1,10 @@
 // Device helpers shared by the persistent (single-launch) kernels: data-is-flag granules
-// (cdna_hip_programming.md §6 Guideline 16, R2), wall-clock deadlines, LDS-resident GEMV.
+// (cdna_hip_programming.md §6 Guideline 16, R2), wall-clock deadlines, LDS-resident GEMV, and the
+// protocol every engine wraps around its worker loop: the placement prologue (place_block) and the
+// stop-rule monitor (monitor_loop). Host side of the protocol: persist_launch.h.
 #pragma once
 #include "gadmm_common.h"
+#include "stop_rule.h"
 
 // Pause between two polls of a hand-off spin (s_sleep units of 64 clocks; 0 = poll back to back).
 #ifndef GADMM_POLL_SLEEP
@@ -44,7 +47,7 @@ __device__ __forceinline__ void store_granule(__amdgpu_buffer_rsrc_t rs, int byt
 // Plain (write-back) granule store: the line stays in this XCD's L2, so a same-XCD `sc1` reader is
 // served from L2 instead of re-fetching it across the fabric (MI355X_MICROARCH.md, price list:
 // `sc1` stores DROP the line). Visible ONLY to readers on the same XCD: callers must have verified
-// the placement of every reader (chain_blocked.hip: xcd_verdict).
+// the placement of every reader (xcd_verdict below, through place_block).
 __device__ __forceinline__ void store_granule_local(__amdgpu_buffer_rsrc_t rs, int byte_off, unsigned tag, double v) {
   const unsigned long long bits = __double_as_longlong(v);
   u32x4 g = {tag, (unsigned)(bits & 0xffffffffull), tag, (unsigned)(bits >> 32)};
@@ -262,6 +265,99 @@ __device__ __forceinline__ bool xcd_verdict(u32x4* xchk, int bid, int nb, unsign
   }
   lds_barrier();
   return __builtin_amdgcn_readfirstlane(*lds_flag) != 0;
+}
+
+// Where this block stands in a launch that may be XCD-packed (`xcd`: the launch's PersistArgs::xcd /
+// StarArgs::xcd / FoArgs::xcd; packing is one-GPU only, so SYS launches are never packed).
+struct Placement {
+  bool spacer;  // packed launch, blockIdx.x % 8 != 0: the block has no work and returns at once
+  int bid;      // index among the working blocks
+  bool local;   // every working block verified on this XCD: publish with plain stores (put_granule)
+};
+
+// The opening of a persistent kernel: nb working blocks; xcd > 1 runs xcd_verdict with `tag` and
+// `lds_flag` (block-uniform outcome, ends in a workgroup barrier). ctl (nullable): block 0 records the
+// placement in ChainCtl::placed.
+template <bool SYS>
+__device__ __forceinline__ Placement place_block(int xcd, u32x4* xchk, unsigned tag, int nb,
+                                                 unsigned long long deadline, int* lds_flag, ChainCtl* ctl = nullptr) {
+  const bool packed = !SYS && xcd > 0;
+  Placement p;
+  p.spacer = packed && (blockIdx.x & 7u);  // only b % 8 == 0 work (one XCD)
+  p.bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  p.local = false;
+  if (p.spacer) return p;
+  if (!SYS && xcd > 1) p.local = xcd_verdict(xchk, p.bid, nb, deadline, lds_flag, tag);
+  if (!SYS && ctl && p.bid == 0 && threadIdx.x == 0) ctl->placed = xcd > 0 ? (p.local ? 2 : 1) : 0;
+  return p;
+}
+
+// The stop-rule monitor of every persistent engine: one workgroup per run (on the monitor rank), of
+// which wave 0 works and the others return (`wave`: the caller's wave index, wave-uniform). Per iteration it polls the tagged objective granules of
+// all n workers in ring slot it % ring, sums them in worker order (the order of the graph engine's
+// finish: the traces are bit-identical), records the trace, applies stop_code and fans {tag, code}
+// out to every rank's decision ring (dec_push[r], r < nranks). A poll that outlives the deadline
+// (tested every 8th poll) decides code 4. It returns after the first non-zero code.
+// PA: PersistArgs, a sweep slot's copy of it, or StarArgs (the fields read here have one meaning in
+// all of them); what differs between engines is passed explicitly:
+//   PAUSE       s_sleep units between two polls, 0 = back to back (each engine's measured choice)
+//   vals        LDS, n doubles
+//   start_iter  first iteration of this launch
+//   hard_stop   > 0 (epoch chunks): no iteration beyond it runs; done = 5 if none decided a stop, and a
+//               decision is also written to ctl (the workers may stop at hard_stop before they see it)
+//   wave        this wave's index in the block, as the kernel already holds it (recomputing it here cost the
+//               blocked kernels two VGPRs and the d = 52 paired kernel its zero scratch)
+//   tl          nullable: this workgroup's timeline row; iteration start_iter + k is stamped at
+//               tl[k * tl_stride] for k < timeline_iters
+template <bool SYS, int PAUSE, class PA>
+__device__ __forceinline__ void monitor_loop(const PA& a, double* vals, __amdgpu_buffer_rsrc_t rob,
+                                             unsigned long long deadline, int start_iter, int hard_stop,
+                                             long long* tl, int tl_stride, int wave) {
+  if (wave != 0) return;
+  const int lane = threadIdx.x & 63, n = a.n;
+  for (int it = start_iter;; ++it) {
+    if (hard_stop > 0 && it > hard_stop) {  // chunk exhausted without a stop decision
+      if (lane == 0) a.ctl->done = 5;
+      return;
+    }
+    const unsigned tag = make_tag(a.epoch, it);
+    const int slot = it % a.ring;
+    bool okall = true;
+    for (int w = lane; w < n; w += 64) {
+      double val = 0.0;
+      for (int spin = 0;; ++spin) {
+        if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &val)) break;
+        if ((spin & 7) == 7 && now_ticks() > deadline) {
+          okall = false;
+          break;
+        }
+        if (PAUSE > 0) __builtin_amdgcn_s_sleep(PAUSE);
+      }
+      vals[w] = val;
+    }
+    const bool ok = __all(okall);
+    unsigned code = 0;
+    if (lane == 0) {
+      if (!ok) {
+        code = 4;
+      } else {
+        double s = 0.0;
+        for (int w = 0; w < n; ++w) s += vals[w];  // worker order: deterministic, == every other engine
+        if (it - 1 < a.max_iter) a.trace[it - 1] = s;
+        code = (unsigned)stop_code(s, a.obj0, a.tol, it, a.max_iter);
+        if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
+      }
+      const unsigned long long dv = ((unsigned long long)tag << 32) | code;
+      for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
+      if (code && hard_stop > 0) {
+        a.ctl->done = (int)code;
+        a.ctl->conv_iter = it;
+      }
+      const int k = it - start_iter;
+      if (tl && k < a.timeline_iters) tl[(long)k * tl_stride] = (long long)now_ticks();
+    }
+    if (__shfl((int)code, 0, 64)) return;
+  }
 }
 
 }  // namespace persist

@@ -30,6 +30,7 @@
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include <stdlib.h>
 
 namespace {
@@ -89,61 +90,6 @@ __device__ __forceinline__ void stage_epochs(const PA& a, int q, const EpochLds&
 }  // namespace
 
 
-
-// ---- monitor workgroup (same protocol as chain_persistent): sums f_n in worker order, records the
-// trace and posts the stop decision of every iteration to every rank's decision ring
-template <bool SYS, bool TL, class PA>
-__device__ __forceinline__ void blocked_monitor(const PA& a, double* lds, int v, int lane,
-                                                unsigned long long deadline, __amdgpu_buffer_rsrc_t rob, int bid) {
-  const int n = a.n;
-  if (v != 0) return;
-  double* vals = lds;  // [n]
-  for (int it = a.start_iter;; ++it) {
-    if (a.hard_stop > 0 && it > a.hard_stop) {  // D-GADMM chunk exhausted without a stop decision
-      if (lane == 0) a.ctl->done = 5;
-      return;
-    }
-    const unsigned tag = make_tag(a.epoch, it);
-    const int slot = it % a.ring;
-    bool okall = true;
-    for (int w = lane; w < n; w += 64) {
-      double val = 0.0;
-      for (int spin = 0;; ++spin) {
-        if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &val)) break;
-        if ((spin & 7) == 7 && now_ticks() > deadline) {
-          okall = false;
-          break;
-        }
-        GADMM_POLL_PAUSE();
-      }
-      vals[w] = val;
-    }
-    const bool ok = __all(okall);
-    unsigned code = 0;
-    if (lane == 0) {
-      if (!ok) {
-        code = 4;
-      } else {
-        double s = 0.0;
-        for (int w = 0; w < n; ++w) s += vals[w];  // worker order: == the other engines
-        if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-        if (!(s == s) || isinf(s)) code = 3;
-        else if (fabs(s - a.obj0) < a.tol) code = 1;
-        else if (it >= a.max_iter) code = 2;
-        if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-      }
-      const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-      for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-      if (code && a.hard_stop > 0) {  // chunked: the workers may reach the hard stop before seeing it
-        a.ctl->done = (int)code;
-        a.ctl->conv_iter = it;
-      }
-      const int kk = it - a.start_iter;
-      if (TL && kk < a.timeline_iters) a.timeline[((long)bid * a.timeline_iters + kk) * 8] = (long long)now_ticks();
-    }
-    if (__shfl((int)code, 0, 64)) return;
-  }
-}
 
 // ---- objective workgroup: wave v evaluates f_q(theta_q^it) of owned chain position q (A_q in VGPRs,
 // quad layout) off the critical path and posts it to the monitor ring
@@ -264,7 +210,8 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
   if (!SYS && bid == 0 && threadIdx.x == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
 
   if (bid == W + Wo) {
-    blocked_monitor<SYS, TL>(a, lds, v, lane, deadline, rob, bid);
+    monitor_loop<SYS, GADMM_POLL_SLEEP>(a, lds, rob, deadline, a.start_iter, a.hard_stop,
+                                        TL ? a.timeline + (long)bid * a.timeline_iters * 8 : nullptr, 8, v);
     return;
   }
 
@@ -847,7 +794,7 @@ __global__ void __launch_bounds__(64 * PWW) chain_blocked_pair_kernel(PersistArg
   }
   lds_barrier();
   if ((int)blockIdx.x == W + Wo) {
-    blocked_monitor<SYS, false>(a, lds, v, lane, deadline, rob, (int)blockIdx.x);
+    monitor_loop<SYS, GADMM_POLL_SLEEP>(a, lds, rob, deadline, a.start_iter, a.hard_stop, nullptr, 0, v);
     return;
   }
   const long ring_base = 2L * n * 2 * d;
@@ -1203,10 +1150,6 @@ long gadmm_chain_blocked_lds(int d, int len) {
 long gadmm_chain_blocked_tab_granules(int n, int d, int ring) { return 2L * n * 2 * d + (long)ring * n * d; }
 long gadmm_chain_blocked_tab_granules_dyn(int n, int d, int ring) { return 4L * n * 2 * d + (long)ring * n * d; }
 
-long gadmm_resident_capacity(const void* fn, int threads, size_t shm);  // chain_persistent.hip
-int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total);  // chain_persistent.hip
-unsigned gadmm_next_xtag();  // chain_persistent.hip
-
 int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
   const PersistArgs& a = *args;
   const bool multi = a.nranks > 1;
@@ -1239,10 +1182,12 @@ int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
     gadmm_set_error("blocked chain kernel: unsupported configuration");
     return -1;
   }
-  if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-    gadmm_set_error("blocked chain kernel: ring/lag/tag range");
+  if (a.lag < 1) {
+    gadmm_set_error("blocked chain kernel: lag must be at least 1");
     return -1;
   }
+  PersistArgs ka = a;
+  void* kargs[] = {&ka};
   const int nseg = multi ? a.seg_hi - a.seg_lo + 1 : a.n;
   const int W = (nseg + a.blk_len - 1) / a.blk_len;
   if (a.blk_pw == 2 && a.n_epochs == 0) {  // paired-wave kernel (static chains only)
@@ -1258,16 +1203,7 @@ int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
                                                : (const void*)chain_blocked_pair_kernel<52, true>)
                                   : (a.d <= 32 ? (const void*)chain_blocked_pair_kernel<32, false>
                                                : (const void*)chain_blocked_pair_kernel<52, false>);
-    const long cap2 = gadmm_resident_capacity(fn2, 64 * PWW, (size_t)lds2);
-    if (blocks2 > cap2) {  // every workgroup must be resident together (they spin on each other)
-      gadmm_set_error("blocked chain kernel: %d workgroups but only %ld can be resident", blocks2, cap2);
-      return -2;
-    }
-    if (lds2 > 65536) GADMM_CHECK(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    void* kargs2[] = {const_cast<PersistArgs*>(&a)};
-    GADMM_CHECK(hipLaunchKernel(fn2, dim3(blocks2), dim3(64 * PWW), kargs2, (size_t)lds2, st));
-    GADMM_CHECK(hipGetLastError());
-    return 0;
+    return gadmm_persist_launch({fn2, 64 * PWW, (size_t)lds2, blocks2, "blocked chain kernel", false}, &ka, kargs, st);
   }
   const int Wo = (nseg + MAXW - 1) / MAXW;
   const int blocks = W + Wo + (a.has_monitor ? 1 : 0);
@@ -1304,25 +1240,11 @@ int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
     if (tl) fn = a.d <= 32 ? (const void*)chain_blocked_kernel<32, false, true> : (const void*)chain_blocked_kernel<52, false, true>;
     else fn = a.d <= 32 ? (const void*)chain_blocked_kernel<32, false, false> : (const void*)chain_blocked_kernel<52, false, false>;
   }
-  const long cap = gadmm_resident_capacity(fn, 64 * MAXW, (size_t)lds);
-  if (blocks > cap) {  // every workgroup must be resident together (they spin on each other)
-    gadmm_set_error("blocked chain kernel: %d workgroups but only %ld can be resident", blocks, cap);
-    return -2;
-  }
-  const int xcd = gadmm_xcd_mode(&a, blocks, cap);
-  const int grid = xcd > 0 ? 8 * blocks : blocks;
-  if (lds > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  PersistArgs ka = a;
   {
     const char* e = getenv("GADMM_BLK_DBG");  // experiment bits: 1 no stop polling, 2 no objective ring stores
     ka.dbg = e ? atoi(e) : 0;
   }
-  ka.xcd = xcd;
-  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
-  void* kargs[] = {&ka};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(grid), dim3(64 * MAXW), kargs, (size_t)lds, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return gadmm_persist_launch({fn, 64 * MAXW, (size_t)lds, blocks, "blocked chain kernel", true}, &ka, kargs, st);
 }
 
 // Solves one launch of chain_blocked_sweep_kernel can run side by side (one per XCD).

@@ -31,10 +31,9 @@
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
-#include <mutex>
 
 namespace {
 
@@ -70,71 +69,22 @@ __global__ void __launch_bounds__(REG ? 64 : NT) chain_persistent_kernel(Persist
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
   __shared__ int xcd_lds;
-  const bool packed = !SYS && a.xcd > 0;   // XCD packing (PersistArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  const Placement pl = place_block<SYS>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + (a.has_monitor ? 1 : 0), deadline,
+                                        &xcd_lds, a.ctl);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
   if (threadIdx.x == 0) {
     abort_lds = 0;
     stop_lds = 0;
   }
   lds_barrier();
-  bool local = false;  // publish with plain stores (every block verified on this XCD)
-  if (!SYS && a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + (a.has_monitor ? 1 : 0), deadline, &xcd_lds, (unsigned)a.xtag);
-  if (!SYS && bid == 0 && threadIdx.x == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
 
   if (a.has_monitor && bid == a.n_local) {
-    // ---------------------------------------------------------------- monitor workgroup
-    double* vals = lds;  // [n]
-    for (int it = a.start_iter;; ++it) {
-      if (a.hard_stop > 0 && it > a.hard_stop) {  // chunk exhausted without a stop decision
-        if (threadIdx.x == 0) a.ctl->done = 5;
-        return;
-      }
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      if (w0) {
-        for (int w = lane; w < n; w += 64) {
-          double v = 0.0;
-          for (;;) {
-            if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-            if (now_ticks() > deadline) {
-              abort_lds = 1;
-              break;
-            }
-            GADMM_POLL_PAUSE();
-          }
-          vals[w] = v;
-        }
-      }
-      lds_barrier();
-      if (threadIdx.x == 0) {
-        unsigned code = 0;
-        if (abort_lds) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];  // fixed order: deterministic, == multi-kernel path
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-        if (code) {
-          stop_lds = 1;
-          if (a.hard_stop > 0) {  // chunked: the workers may stop at hard_stop before seeing this decision
-            a.ctl->done = (int)code;
-            a.ctl->conv_iter = it;
-          }
-        }
-        const int k = it - a.start_iter;
-        if (TL && k < a.timeline_iters) a.timeline[((long)bid * a.timeline_iters + k) * 8] = (long long)now_ticks();
-      }
-      lds_barrier();
-      if (stop_lds) return;
-    }
+    monitor_loop<SYS, GADMM_POLL_SLEEP>(a, lds, rob, deadline, a.start_iter, a.hard_stop,
+                                        TL ? a.timeline + (long)bid * a.timeline_iters * 8 : nullptr, 8,
+                                        (int)(threadIdx.x >> 6));
+    return;
   }
 
   // ------------------------------------------------------------------ worker workgroup
@@ -570,77 +520,6 @@ static PVariant pick_variant(const PersistArgs& a) {
   return v;
 }
 
-// Workgroups of `fn` (block size, dynamic LDS) that the device can hold resident at once:
-// occupancy per CU x CUs. GADMM_CU_BUDGET=<n> replaces the CU count (tests of a partitioned or
-// shared device). A persistent launch needs every one of its workgroups resident together: the
-// workers spin on each other, so a workgroup that waits for a CU would stall the rest until the
-// deadline. 0 on error.
-// Occupancy of (kernel, threads, LDS, device), queried once: eligibility checks and launches ask for
-// it several times per solve
-namespace {
-struct OccEntry {
-  const void* fn;
-  int threads, dev, per_cu;
-  size_t shm;
-};
-std::mutex g_occ_mu;
-OccEntry g_occ[128];
-int g_occ_n = 0;
-}  // namespace
-
-extern "C" long gadmm_resident_capacity(const void* fn, int threads, size_t shm) {
-  int dev = 0, per_cu = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  {
-    std::lock_guard<std::mutex> lk(g_occ_mu);
-    for (int i = 0; i < g_occ_n; ++i)
-      if (g_occ[i].fn == fn && g_occ[i].threads == threads && g_occ[i].shm == shm && g_occ[i].dev == dev) {
-        per_cu = g_occ[i].per_cu;
-        break;
-      }
-  }
-  if (per_cu < 0) {
-    per_cu = 0;
-    if (shm > 65536 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-      return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, shm) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(g_occ_mu);
-    if (g_occ_n < 128) g_occ[g_occ_n++] = OccEntry{fn, threads, dev, per_cu, shm};
-  }
-  long cus = gadmm_cu_count();
-  if (cus <= 0) return 0;
-  if (const char* e = getenv("GADMM_CU_BUDGET")) {
-    const long b = atol(e);
-    if (b > 0 && b < cus) cus = b;
-  }
-  return (long)per_cu * cus;
-}
-
-// Effective XCD packing mode (PersistArgs::xcd / StarArgs::xcd `want`; env GADMM_XCD overrides it for
-// A/B runs) of a launch of `blocks` working workgroups: one GPU only (`multi` = 0), and only when all
-// of them fit on one XCD (cap_total / 8 of the `cap_total` resident slots), since packing deals every
-// one of them there. Mode 2 needs the placement-check buffer.
-extern "C" int gadmm_xcd_pick(int want, int multi, int blocks, long cap_total, const void* xchk) {
-  int x = want;
-  if (const char* e = getenv("GADMM_XCD")) x = atoi(e);
-  if (x < 0) x = 0;
-  if (x > 2) x = 2;
-  if (multi || blocks > XCHK || (long)blocks > cap_total / 8) x = 0;
-  if (x == 2 && !xchk) x = 1;
-  return x;
-}
-
-extern "C" int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total) {
-  return gadmm_xcd_pick(a->xcd, a->sys_scope || a->nranks > 1, blocks, cap_total, a->xchk);
-}
-
-// PersistArgs::xtag of a launch: fresh per launch in this process (high bit set, so never XTAG nor a
-// zeroed granule), so the placement-check granules an earlier launch left in xchk never match.
-extern "C" unsigned gadmm_next_xtag() {
-  static std::atomic<unsigned> launches{0};
-  return 0x80000000u | ((launches.fetch_add(1, std::memory_order_relaxed) + 1u) & 0x7fffffffu);
-}
-
 extern "C" {
 
 // Workgroups the persistent kernel for `args` can keep resident (0: shape not eligible).
@@ -671,28 +550,10 @@ int gadmm_chain_persistent_launch(const PersistArgs* args, hipStream_t st) {
                     "hard_stop >= start_iter", a.hard_stop, a.cont);
     return -1;
   }
-  const int blocks = a.n_local + (a.has_monitor ? 1 : 0);
-  const long cap = gadmm_resident_capacity(v.fn, v.threads, v.shm);
-  if (blocks > cap) {
-    gadmm_set_error("persistent chain kernel: %d workgroups but only %ld can be resident", blocks, cap);
-    return -2;
-  }
-  if (a.ring <= a.lag + 1) {
-    gadmm_set_error("persistent chain kernel: ring must exceed lag + 1");
-    return -1;
-  }
-  if (a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-    gadmm_set_error("persistent chain kernel: iteration tags limited to 2^20");
-    return -1;
-  }
-  if (v.shm > 65536) GADMM_CHECK(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.shm));
   PersistArgs ka = a;
-  ka.xcd = gadmm_xcd_mode(&a, blocks, cap);
-  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   void* kargs[] = {&ka};
-  GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(v.threads), kargs, v.shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return gadmm_persist_launch({v.fn, v.threads, v.shm, a.n_local + (a.has_monitor ? 1 : 0), "persistent chain kernel", true},
+                              &ka, kargs, st);
 }
 
 // ---- xGMI fabric buffers: fine-grained (uncached) device memory exported by IPC -----------------

@@ -26,6 +26,7 @@
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include "chain_device.h"
 #include "fast_sigm.h"
 #include <cstddef>
@@ -49,51 +50,15 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
   __shared__ int xcd_lds;
-  const bool packed = !SYS && a.xcd > 0;   // XCD packing (PersistArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  bool local = false;  // publish with plain stores (every block verified on this XCD)
-  if (!SYS && a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + (a.has_monitor ? 1 : 0), deadline, &xcd_lds, (unsigned)a.xtag);
-  if (!SYS && bid == 0 && threadIdx.x == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
+  const Placement pl = place_block<SYS>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + (a.has_monitor ? 1 : 0), deadline,
+                                        &xcd_lds, a.ctl);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
 
   if (a.has_monitor && bid == a.n_local) {
-    // ---------------------------------------------------------------- monitor (one wave)
-    double* vals = lds;  // [n]
-    for (int it = a.start_iter;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      bool okall = true;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (int spin = 0;; ++spin) {
-          if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if ((spin & 7) == 7 && now_ticks() > deadline) {
-            okall = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        vals[w] = v;
-      }
-      const bool ok = __all(okall);
-      unsigned code = 0;
-      if (lane == 0) {
-        if (!ok) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];  // worker order, == the graph engine's finish
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-      }
-      if (__shfl((int)code, 0, 64)) return;
-    }
+    monitor_loop<SYS, 1>(a, lds, rob, deadline, a.start_iter, 0, nullptr, 0, 0);
+    return;
   }
 
   // ------------------------------------------------------------------ worker (one wave)
@@ -306,6 +271,8 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
   const __amdgpu_buffer_rsrc_t rth = rsrc_of(a.thg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
+  // The placement prologue, written out (place_block in persist_device.h is the same code): through the
+  // helper this kernel's register allocation changed and a solve measured 2.3 % slower (5.09 vs 4.98 ms)
   __shared__ int xcd_lds;
   const bool packed = !SYS && a.xcd > 0;
   if (packed && (blockIdx.x & 7u)) return;
@@ -315,43 +282,8 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
   if (!SYS && bid == 0 && threadIdx.x == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
 
   if (a.has_monitor && bid == a.n_local) {
-    if (wv != 0) return;  // the monitor is one wave (the one-wave kernel's code)
-    double* vals = lds;
-    for (int it = a.start_iter;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      bool okall = true;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (int spin = 0;; ++spin) {
-          if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if ((spin & 7) == 7 && now_ticks() > deadline) {
-            okall = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        vals[w] = v;
-      }
-      const bool ok = __all(okall);
-      unsigned code = 0;
-      if (lane == 0) {
-        if (!ok) {
-          code = 4;
-        } else {
-          double sum = 0.0;
-          for (int w = 0; w < n; ++w) sum += vals[w];
-          if (it - 1 < a.max_iter) a.trace[it - 1] = sum;
-          if (!(sum == sum) || isinf(sum)) code = 3;
-          else if (fabs(sum - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-      }
-      if (__shfl((int)code, 0, 64)) return;
-    }
+    monitor_loop<SYS, 1>(a, lds, rob, deadline, a.start_iter, 0, nullptr, 0, wv);
+    return;
   }
 
   const PhaseSlot sl = a.slots[bid];
@@ -577,10 +509,6 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
   }
 }
 
-extern "C" long gadmm_resident_capacity(const void* fn, int threads, size_t shm);
-extern "C" int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total);  // chain_persistent.hip
-extern "C" unsigned gadmm_next_xtag();  // chain_persistent.hip
-
 // (Round 5's four-wave sample-class split kernel, GADMM_LOGISTIC_SPLIT=1, was bit-identical but slower --
 // 6.60 / 6.71 vs 6.37 / 6.39 ms, profiles/r05_c: the inner step is bound by its dependent chain, not FMA
 // issue -- and was removed in round 6.)
@@ -640,30 +568,18 @@ int gadmm_chain_persistent_logistic_launch(const PersistArgs* args, const LogiAr
   const PersistArgs& a = *args;
   const LogiArgs& g = *gargs;
   const void* fn = logi_variant(a, g);
-  if (!fn || !g.X || !g.Y || g.max_inner < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20) ||
-      (a.has_monitor && !a.dec_push)) {
+  if (!fn || !g.X || !g.Y || g.max_inner < 1 || (a.has_monitor && !a.dec_push)) {
     gadmm_set_error("persistent logistic kernel: unsupported configuration (d=%d m=%d)", a.d, g.m);
     return -1;
   }
-  const size_t shm = logi_shm(a);
-  const int blocks = a.n_local + (a.has_monitor ? 1 : 0);
-  const long cap = gadmm_resident_capacity(fn, logi_threads(), shm);
-  if (blocks > cap) {
-    gadmm_set_error("persistent logistic kernel: %d workgroups but only %ld can be resident", blocks, cap);
-    return -2;
-  }
-  if (shm > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   PersistArgs ka = a;
-  ka.xcd = gadmm_xcd_mode(&a, blocks, cap);
-  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   const char* fs = getenv("GADMM_LOGISTIC_FASTSIGM");
   if (fs && fs[0] == '0') ka.dbg |= 32;
   const char* pf = getenv("GADMM_LOGISTIC_POSTFENCE");
   if (pf && pf[0] == '1') ka.dbg |= 1 << 17;
   void* kargs[] = {&ka, const_cast<LogiArgs*>(&g)};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(logi_threads()), kargs, shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return gadmm_persist_launch({fn, logi_threads(), logi_shm(a), a.n_local + (a.has_monitor ? 1 : 0),
+                               "persistent logistic kernel", true}, &ka, kargs, st);
 }
 
 }  // extern "C"

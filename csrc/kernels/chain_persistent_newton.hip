@@ -26,6 +26,7 @@
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include "chain_device.h"
 #include "fast_sigm.h"
 #include <cstddef>
@@ -310,44 +311,8 @@ __global__ void __launch_bounds__(NT) chain_persistent_newton_kernel(PersistArgs
   const NLds L(m, d);
 
   if (a.has_monitor && bid == a.n_local) {
-    // ---------------------------------------------------------------- monitor (wave 0)
-    if (wid != 0) return;
-    double* vals = lds;  // [n]
-    for (int it = a.start_iter;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      bool okall = true;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (int spin = 0;; ++spin) {
-          if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if ((spin & 7) == 7 && now_ticks() > deadline) {
-            okall = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        vals[w] = v;
-      }
-      const bool ok = __all(okall);
-      unsigned code = 0;
-      if (lane == 0) {
-        if (!ok) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];  // worker order
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-      }
-      if (__shfl((int)code, 0, 64)) return;
-    }
+    monitor_loop<SYS, 1>(a, lds, rob, deadline, a.start_iter, 0, nullptr, 0, wid);
+    return;
   }
   if (bid >= a.n_local) return;
 
@@ -965,52 +930,16 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
   // all of them share one XCD's L2; with the placement verified, theta / objective granules are plain
   // write-back stores that stay in that L2 (a neighbour's poll is an L2 hit, not a fabric round trip)
   __shared__ int xcd_lds;
-  const bool packed = !SYS && a.xcd > 0;
-  if (packed && (blockIdx.x & 7u)) return;
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  bool local = false;
-  if (!SYS && a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + (a.has_monitor ? 1 : 0), deadline, &xcd_lds, (unsigned)a.xtag);
-  if (!SYS && bid == 0 && threadIdx.x == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
+  const Placement pl = place_block<SYS>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + (a.has_monitor ? 1 : 0), deadline,
+                                        &xcd_lds, a.ctl);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
   const RLds L;
 
-  if (a.has_monitor && bid == a.n_local) {  // the monitor: the one-wave kernel's
-    if (wid != 0) return;
-    double* vals = lds;
-    for (int it = a.start_iter;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      bool okall = true;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (int spin = 0;; ++spin) {
-          if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if ((spin & 7) == 7 && now_ticks() > deadline) {
-            okall = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        vals[w] = v;
-      }
-      const bool ok = __all(okall);
-      unsigned code = 0;
-      if (lane == 0) {
-        if (!ok) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-      }
-      if (__shfl((int)code, 0, 64)) return;
-    }
+  if (a.has_monitor && bid == a.n_local) {
+    monitor_loop<SYS, 1>(a, lds, rob, deadline, a.start_iter, 0, nullptr, 0, wid);
+    return;
   }
   if (bid >= a.n_local) return;
 
@@ -1467,10 +1396,6 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
   }
 }
 
-extern "C" long gadmm_resident_capacity(const void* fn, int threads, size_t shm);
-extern "C" int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total);  // chain_persistent.hip
-extern "C" unsigned gadmm_next_xtag();  // chain_persistent.hip
-
 // The pipeline kernel is the default; GADMM_NEWTON_REC=0 selects the one-wave solver kernel.
 static bool newton_rec(const LogiArgs& g) {
   const char* e = getenv("GADMM_NEWTON_REC");
@@ -1512,8 +1437,7 @@ int gadmm_chain_persistent_newton_launch(const PersistArgs* args, const LogiArgs
   const PersistArgs& a = *args;
   const LogiArgs& g = *gargs;
   const void* fn = newton_variant(a, g);
-  if (!fn || !g.X || !g.Y || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20) ||
-      (a.has_monitor && !a.dec_push)) {
+  if (!fn || !g.X || !g.Y || (a.has_monitor && !a.dec_push)) {
     gadmm_set_error("persistent Newton kernel: unsupported configuration (d=%d m=%d)", a.d, g.m);
     return -1;
   }
@@ -1522,17 +1446,7 @@ int gadmm_chain_persistent_newton_launch(const PersistArgs* args, const LogiArgs
     gadmm_set_error("persistent Newton kernel: %zu B of LDS", shm);
     return -1;
   }
-  const int blocks = a.n_local + (a.has_monitor ? 1 : 0);
-  const int nt = newton_threads(g);
-  const long cap = gadmm_resident_capacity(fn, nt, shm);
-  if (blocks > cap) {
-    gadmm_set_error("persistent Newton kernel: %d workgroups but only %ld can be resident", blocks, cap);
-    return -2;
-  }
-  if (shm > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   PersistArgs ka = a;
-  ka.xcd = newton_rec(g) ? gadmm_xcd_mode(&a, blocks, cap) : 0;  // the pipeline kernel packs onto one XCD
-  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   const char* fs = getenv("GADMM_NEWTON_FASTSIGM");
   if (fs && fs[0] == '0') ka.dbg |= 32;
   const char* rl = getenv("GADMM_NEWTON_RLAG");
@@ -1544,9 +1458,9 @@ int gadmm_chain_persistent_newton_launch(const PersistArgs* args, const LogiArgs
   const char* un = getenv("GADMM_NEWTON_URGENT_NS");
   if (un && un[0] == '1') ka.dbg |= 1 << 16;
   void* kargs[] = {&ka, const_cast<LogiArgs*>(&g)};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(nt), kargs, shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  // only the pipeline kernel has the placement prologue (it packs onto one XCD)
+  return gadmm_persist_launch({fn, newton_threads(g), shm, a.n_local + (a.has_monitor ? 1 : 0), "persistent Newton kernel",
+                               newton_rec(g)}, &ka, kargs, st);
 }
 
 // doubles of LogiArgs::scratch per local worker for the pipeline kernel

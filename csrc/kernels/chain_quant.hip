@@ -21,6 +21,7 @@
 #include "gadmm_chain.h"
 #include "chain_device.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include "quad_gemv.h"
 #include "quant_device.h"
 
@@ -30,49 +31,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int NW = NT / 64;
-
-// out[i] = sum_j M[j*d + i] * x[j]  (M symmetric), for i < d. x, out in LDS; red: NW*64*NC.
-// The summation order of chain_small.hip's symv_cols (wave k of 4 sums j = k mod 4 ascending, the
-// partials added in wave order), which quad_gemv reproduces in registers.
-template <int NC>
-__device__ __forceinline__ void symv_cols_q(const double* __restrict__ M, const double* x, double* out,
-                                            double* red, int d) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-  int j = w;
-  for (; j + NW < d; j += 2 * NW) {
-    const double x0 = x[j], x1 = x[j + NW];
-    const double* r0 = M + (long)j * d;
-    const double* r1 = M + (long)(j + NW) * d;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int i = lane + 64 * c;
-      if (i < d) acc[c] = fma(r1[i], x1, fma(r0[i], x0, acc[c]));
-    }
-  }
-  for (; j < d; j += NW) {
-    const double x0 = x[j];
-    const double* r0 = M + (long)j * d;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int i = lane + 64 * c;
-      if (i < d) acc[c] = fma(r0[i], x0, acc[c]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) red[w * 64 * NC + c * 64 + lane] = acc[c];
-  __syncthreads();
-  for (int i = threadIdx.x; i < d; i += NT) {
-    const int c = i >> 6, l = i & 63;
-    double s = 0.0;
-#pragma unroll
-    for (int ww = 0; ww < NW; ++ww) s += red[ww * 64 * NC + c * 64 + l];
-    out[i] = s;
-  }
-  __syncthreads();
-}
 
 // A 64-bit value of another lane of the same 16-lane row through DPP (no LDS round trip, unlike
 // __shfl_xor's ds_bpermute): 0xB1 / 0x4E = quad_perm [1,0,3,2] / [2,3,0,1], 0x141 = row_half_mirror,
@@ -168,7 +126,7 @@ __global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
   }
   __syncthreads();
   const double* Mi = a.Minv + ((long)sl.li * a.nvar + a.deg_to_var[deg]) * (long)d * d;
-  symv_cols_q<NC>(Mi, sh_r, sh_t, red, d);
+  symv_cols<NC, NT>(Mi, sh_r, sh_t, red, d);
 
   // -- quantize stage: R = max |theta - th_hat|, then per coordinate draw, code and th_hat update
   const int bits = a.q_bits;
@@ -219,7 +177,7 @@ __global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
     __syncthreads();  // scratch is reused by the objective's block sum
   }
   if (a.flags & PH_OBJ) {  // the objective of the TRUE theta, still in LDS
-    symv_cols_q<NC>(a.A + (long)sl.li * d * d, sh_t, sh_q, red, d);
+    symv_cols<NC, NT>(a.A + (long)sl.li * d * d, sh_t, sh_q, red, d);
     double part = 0.0;
     for (int j = threadIdx.x; j < d; j += NT) part += (0.5 * sh_q[j] - b[j]) * sh_t[j];
     const double f = block_sum_f64(part, scratch) + 0.5 * a.yy[sl.li];
@@ -289,57 +247,19 @@ __global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
   const __amdgpu_buffer_rsrc_t rq = rsrc_of(a.qg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
-  const bool packed = a.xcd > 0;            // XCD packing (PersistArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  const Placement pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + 1, deadline, &xcd_lds, a.ctl);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
   if (lane == 0) {
     abort_lds = 0;
     stop_lds = 0;
   }
   lds_barrier();
-  bool local = false;  // publish with plain stores (every block verified on this XCD)
-  if (a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + 1, deadline, &xcd_lds, (unsigned)a.xtag);
-  if (bid == 0 && lane == 0) a.ctl->placed = a.xcd > 0 ? (local ? 2 : 1) : 0;
 
   if (bid == a.n_local) {
-    // ---------------------------------------------------------------- monitor workgroup
-    double* vals = lds;  // [n]
-    for (int it = a.start_iter;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (;;) {
-          if (load_granule<false>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if (now_ticks() > deadline) {
-            abort_lds = 1;
-            break;
-          }
-          GADMM_POLL_PAUSE();
-        }
-        vals[w] = v;
-      }
-      lds_barrier();
-      if (lane == 0) {
-        unsigned code = 0;
-        if (abort_lds) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];  // fixed order: deterministic, == the graph engine's finish
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        store_dec<false>(a.decg + slot, dv);
-        if (code) stop_lds = 1;
-      }
-      lds_barrier();
-      if (stop_lds) return;
-    }
+    monitor_loop<false, GADMM_POLL_SLEEP>(a, lds, rob, deadline, a.start_iter, 0, nullptr, 0, 0);
+    return;
   }
 
   // ------------------------------------------------------------------ worker workgroup (one wave)
@@ -499,14 +419,6 @@ __global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
   }
 }
 
-extern "C" {
-
-long gadmm_resident_capacity(const void* fn, int threads, size_t shm);
-int gadmm_xcd_mode(const PersistArgs* a, int blocks, long cap_total);
-unsigned gadmm_next_xtag();
-
-}  // extern "C"
-
 namespace {
 
 struct QVariant {
@@ -559,36 +471,19 @@ int gadmm_chain_persistent_q_launch(const PersistArgs* args, hipStream_t st) {
     gadmm_set_error("persistent Q kernel: q_bits must be 4, 8 or 16, got %d", a.q_bits);
     return -1;
   }
-  if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.theta || !a.mu || !a.Minv || !a.A || !a.ctl) {
+  if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.dec_push || !a.theta || !a.mu || !a.Minv || !a.A ||
+      !a.ctl) {
     gadmm_set_error("persistent Q kernel: a required buffer is null");
     return -1;
   }
-  if (a.n_epochs > 0 || a.nranks > 1 || a.sys_scope || a.push || a.n_local != a.n || !a.has_monitor ||
+  if (a.n_epochs > 0 || a.nranks != 1 || a.sys_scope || a.push || a.n_local != a.n || !a.has_monitor ||
       a.hard_stop != 0 || a.cont) {
     gadmm_set_error("persistent Q kernel: one GPU, every worker local, a static chain, one launch per solve");
     return -1;
   }
-  const int blocks = a.n_local + 1;
-  const long cap = gadmm_resident_capacity(v.fn, 64, v.shm);
-  if (blocks > cap) {
-    gadmm_set_error("persistent Q kernel: %d workgroups but only %ld can be resident", blocks, cap);
-    return -2;
-  }
-  if (a.ring <= a.lag + 1) {
-    gadmm_set_error("persistent Q kernel: ring must exceed lag + 1");
-    return -1;
-  }
-  if (a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-    gadmm_set_error("persistent Q kernel: iteration tags limited to 2^20");
-    return -1;
-  }
   PersistArgs ka = a;
-  ka.xcd = gadmm_xcd_mode(&a, blocks, cap);
-  ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   void* kargs[] = {&ka};
-  GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(64), kargs, v.shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return gadmm_persist_launch({v.fn, 64, v.shm, a.n_local + 1, "persistent Q kernel", true}, &ka, kargs, st);
 }
 
 }  // extern "C"

@@ -38,48 +38,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int NW = NT / 64;
 
-// out[i] = sum_j M[j*d + i] * x[j]  (M symmetric), for i < d. x, out in LDS; red: NW*64*NC.
-template <int NC>
-__device__ __forceinline__ void symv_cols(const double* __restrict__ M, const double* x, double* out,
-                                          double* red, int d) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-  int j = w;
-  // 2-way unrolled over j for memory-level parallelism
-  for (; j + NW < d; j += 2 * NW) {
-    const double x0 = x[j], x1 = x[j + NW];
-    const double* r0 = M + (long)j * d;
-    const double* r1 = M + (long)(j + NW) * d;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int i = lane + 64 * c;
-      if (i < d) acc[c] = fma(r1[i], x1, fma(r0[i], x0, acc[c]));
-    }
-  }
-  for (; j < d; j += NW) {
-    const double x0 = x[j];
-    const double* r0 = M + (long)j * d;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int i = lane + 64 * c;
-      if (i < d) acc[c] = fma(r0[i], x0, acc[c]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) red[w * 64 * NC + c * 64 + lane] = acc[c];
-  __syncthreads();
-  for (int i = threadIdx.x; i < d; i += NT) {
-    const int c = i >> 6, l = i & 63;
-    double s = 0.0;
-#pragma unroll
-    for (int ww = 0; ww < NW; ++ww) s += red[ww * 64 * NC + c * 64 + l];
-    out[i] = s;
-  }
-  __syncthreads();
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -121,7 +79,7 @@ __global__ void __launch_bounds__(NT) chain_phase_linear(PhaseArgs a) {
   }
   __syncthreads();
   const double* Mi = a.Minv + ((long)sl.li * a.nvar + a.deg_to_var[deg]) * (long)d * d;
-  symv_cols<NC>(Mi, sh_r, sh_t, red, d);
+  symv_cols<NC, NT>(Mi, sh_r, sh_t, red, d);
   double* thw_out = th + (long)sl.gid * d;
   double rpart = 0.0;
   for (int j = threadIdx.x; j < d; j += NT) {
@@ -144,7 +102,7 @@ __global__ void __launch_bounds__(NT) chain_phase_linear(PhaseArgs a) {
     __syncthreads();  // scratch is reused by the objective's block sum
   }
   if (a.flags & PH_OBJ) {
-    symv_cols<NC>(a.A + (long)sl.li * d * d, sh_t, sh_q, red, d);
+    symv_cols<NC, NT>(a.A + (long)sl.li * d * d, sh_t, sh_q, red, d);
     double part = 0.0;
     for (int j = threadIdx.x; j < d; j += NT) part += (0.5 * sh_q[j] - b[j]) * sh_t[j];
     const double f = block_sum_f64(part, scratch) + 0.5 * a.yy[sl.li];
@@ -624,18 +582,9 @@ __global__ void chain_monitor_kernel(ChainCtl* ctl, const double* reduced, int r
     for (int g = 0; g < n_total; ++g) s += row[g];  // worker order == the single-rank finish
     if (j - 1 < max_iter) trace[j - 1] = s;
     ctl->monitored = j;
-    if (!(s == s) || isinf(s)) {
-      ctl->done = 3;
-      ctl->conv_iter = j;
-      return;
-    }
-    if (fabs(s - obj0) < tol) {
-      ctl->done = 1;
-      ctl->conv_iter = j;
-      return;
-    }
-    if (j >= max_iter) {
-      ctl->done = 2;
+    const int code = stop_code(s, obj0, tol, j, max_iter);
+    if (code) {
+      ctl->done = code;
       ctl->conv_iter = j;
       return;
     }

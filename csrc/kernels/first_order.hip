@@ -36,6 +36,7 @@
 #include "gadmm_common.h"
 #include "gadmm_fo.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include <hip/hip_runtime.h>
 
 namespace {
@@ -256,11 +257,10 @@ __global__ void __launch_bounds__(NT) fo_persistent_kernel(FoArgs a) {
   const __amdgpu_buffer_rsrc_t rpart = rsrc_of(a.part);
   FoCtl* ctl = a.ctl;
   const bool multi = SYS && a.nranks > 1;
-  const bool packed = !SYS && a.xcd > 0;    // XCD packing (FoArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  bool local = false;  // publish with plain stores (every block verified on this XCD)
-  if (!SYS && a.xcd > 1) local = xcd_verdict(a.xchk, bid, nl + (a.has_monitor ? 1 : 0), deadline, &flag_lds);
+  const Placement pl = place_block<SYS>(a.xcd, a.xchk, XTAG, nl + (a.has_monitor ? 1 : 0), deadline, &flag_lds);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
 
   if (a.has_monitor && bid == nl) {
     // ------------------------------------------------------------------ monitor (wave 0 only)
@@ -674,8 +674,6 @@ __global__ void __launch_bounds__(NT) fo_persistent_kernel(FoArgs a) {
     a.pushc[2 * li + 1] = flags_pushed;
   }
 }
-
-extern "C" int gadmm_xcd_pick(int want, int multi, int blocks, long cap_total, const void* xchk);  // chain_persistent.hip
 
 extern "C" {
 

@@ -18,6 +18,7 @@
 // written. Objective partials are per (worker, 128-element block) and summed in a fixed order.
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
+#include "stop_rule.h"
 #include "sym_gemv.h"
 
 namespace {
@@ -293,10 +294,7 @@ __global__ void fob_finish(const double* part, int nw, int nblk, const double* y
       trace[rec - 1] = obj;
       tstamp[rec - 1] = (long long)__builtin_amdgcn_s_memrealtime();
     }
-    int code = 0;
-    if (!(obj == obj) || isinf(obj)) code = 3;
-    else if (tol >= 0.0 && fabs(obj - obj0) < tol) code = 1;
-    else if (rec >= max_iter) code = 2;
+    const int code = stop_code(obj, obj0, tol >= 0.0 ? tol : 0.0, rec, max_iter);  // tol < 0: no gap test
     if (code) {
       ctl->done = code;
       ctl->conv_iter = rec;

@@ -23,6 +23,7 @@
 // (no extra pass over the inverse); exact mode (obj_mode 0) adds one GEMV with A per worker.
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
+#include "stop_rule.h"
 #include "big_gemv.h"
 
 using namespace biggemv;
@@ -193,10 +194,7 @@ __global__ void sb_finish(StarBigArgs a) {
     a.trace[it - 1] = obj;
     a.tstamp[it - 1] = (long long)__builtin_amdgcn_s_memrealtime();
   }
-  int code = 0;
-  if (!(obj == obj) || isinf(obj)) code = 3;
-  else if (fabs(obj - a.obj0) < a.tol) code = 1;
-  else if (it >= a.max_iter) code = 2;
+  const int code = stop_code(obj, a.obj0, a.tol, it, a.max_iter);
   if (code) {
     ctl->done = code;
     ctl->conv_iter = it;

@@ -23,6 +23,7 @@
 #include "gadmm_chain.h"
 #include "gadmm_star.h"
 #include "persist_device.h"
+#include "persist_launch.h"
 #include <stdlib.h>
 #include <cstddef>
 
@@ -49,55 +50,18 @@ __global__ void __launch_bounds__(64 * HW) star_persistent_kernel(StarArgs a) {
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
   __shared__ int xcd_lds;
-  const bool packed = !SYS && a.xcd > 0;   // XCD packing (StarArgs::xcd)
-  if (packed && (blockIdx.x & 7u)) return;  // a spacer block: only b % 8 == 0 work (one XCD)
-  const int bid = packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  const Placement pl = place_block<SYS>(a.xcd, a.xchk, XTAG, a.n_local + (a.has_monitor ? 1 : 0), deadline, &xcd_lds);
+  if (pl.spacer) return;
+  const int bid = pl.bid;
+  const bool local = pl.local;
   if (threadIdx.x == 0) stop_flag = 0;
-  bool local = false;  // publish with plain stores (every block verified on this XCD)
-  if (!SYS && a.xcd > 1) local = xcd_verdict(a.xchk, bid, a.n_local + (a.has_monitor ? 1 : 0), deadline, &xcd_lds);
   lds_barrier();
 
   if (a.has_monitor && bid == a.n_local) {
-    if (wv != 0) return;
-    // ---- monitor: sum f_n in worker order, record, decide, fan the decision out
-    double* vals = lds;
-    for (int it = 1;; ++it) {
-      const unsigned tag = make_tag(a.epoch, it);
-      const int slot = it % a.ring;
-      bool okall = true;
-      for (int w = lane; w < n; w += 64) {
-        double v = 0.0;
-        for (int spin = 0;; ++spin) {
-          if (load_granule<SYS>(rob, (slot * n + w) * 16, tag, &v)) break;
-          if ((spin & 7) == 7 && now_ticks() > deadline) {
-            okall = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        vals[w] = v;
-      }
-      const bool ok = __all(okall);
-      unsigned code = 0;
-      if (lane == 0) {
-        if (!ok) {
-          code = 4;
-        } else {
-          double s = 0.0;
-          for (int w = 0; w < n; ++w) s += vals[w];
-          if (it - 1 < a.max_iter) a.trace[it - 1] = s;
-          if (!(s == s) || isinf(s)) code = 3;
-          else if (fabs(s - a.obj0) < a.tol) code = 1;
-          else if (it >= a.max_iter) code = 2;
-          if (a.tstamp && it - 1 < a.max_iter) a.tstamp[it - 1] = (long long)now_ticks();
-        }
-        const unsigned long long dv = ((unsigned long long)tag << 32) | code;
-        for (int r = 0; r < a.nranks; ++r) store_dec<SYS>(a.dec_push[r] + slot, dv);
-        if (a.timeline && it - 1 < a.timeline_iters)
-          a.timeline[((long)bid * a.timeline_iters + it - 1) * 4] = (long long)now_ticks();
-      }
-      if (__shfl((int)code, 0, 64)) return;
-    }
+    // ---- monitor: iterations count from 1; the timeline row has 4 stamps per iteration
+    monitor_loop<SYS, 1>(a, lds, rob, deadline, 1, 0,
+                         a.timeline ? a.timeline + (long)bid * a.timeline_iters * 4 : nullptr, 4, wv);
+    return;
   }
 
   // ---- worker / hub
@@ -289,9 +253,6 @@ __global__ void __launch_bounds__(64 * HW) star_persistent_kernel(StarArgs a) {
     }
   }
 }
-
-extern "C" long gadmm_resident_capacity(const void* fn, int threads, size_t shm);
-extern "C" int gadmm_xcd_pick(int want, int multi, int blocks, long cap_total, const void* xchk);  // chain_persistent.hip
 
 static const void* star_variant(const StarArgs& a) {
   if (a.d > 64) return nullptr;

@@ -16,11 +16,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "gadmm_chain.h"
 #include "gadmm_fo.h"
 #include "gadmm_star.h"
+#include "stop_rule.h"
 
 extern "C" {
 const char* gadmm_last_error();
@@ -302,6 +304,23 @@ void host_only_checks() {
          "blocked inverse rejects nb = 100");
   EXPECT(gadmm_spd_inverse_blocked_workspace(300, 128) > gadmm_spd_inverse_blocked_workspace(300, 64),
          "blocked inverse workspace grows with the block");
+  // the stop rule: NaN / inf before tol before max_iter
+  {
+    const double obj0 = 100.0, tol = 1e-4, inf = std::numeric_limits<double>::infinity();
+    // gaps just inside / outside tol (1e-6 relative: well above the rounding of obj0 + gap, 1.4e-14)
+    const double below = obj0 + tol * (1.0 - 1e-6), above = obj0 - tol * (1.0 + 1e-6);
+    EXPECT(std::fabs(below - obj0) < tol && !(std::fabs(above - obj0) < tol), "stop_code test gaps");
+    EXPECT(stop_code(std::nan(""), obj0, tol, 7, 5) == 3, "stop_code: NaN -> 3 past max_iter");
+    EXPECT(stop_code(inf, obj0, tol, 7, 5) == 3 && stop_code(-inf, obj0, tol, 5, 5) == 3, "stop_code: +-inf -> 3");
+    EXPECT(stop_code(std::nan(""), obj0, tol, 1, 5) == 3, "stop_code: NaN -> 3");
+    EXPECT(stop_code(below, obj0, tol, 7, 5) == 1 && stop_code(below, obj0, tol, 1, 5) == 1,
+           "stop_code: gap < tol -> 1, also past max_iter");
+    EXPECT(stop_code(above, obj0, tol, 4, 5) == 0, "stop_code: gap > tol before max_iter -> 0");
+    EXPECT(stop_code(above, obj0, tol, 5, 5) == 2, "stop_code: gap > tol at max_iter -> 2");
+    EXPECT(stop_code(obj0, obj0, 0.0, 1, 5) == 0 && stop_code(obj0, obj0, 0.0, 5, 5) == 2 &&
+               stop_code(below, obj0, 0.0, 1, 5) == 0,
+           "stop_code: tol = 0 never gives 1");
+  }
 }
 
 // ------------------------------------------------------------------ GPU checks
