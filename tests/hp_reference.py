@@ -11,6 +11,8 @@ specification), in the form the kernels evaluate them:
   three Newton-Schulz steps ``X <- X (2 I - M X)`` (quadratic: 1e-13 -> 1e-26 -> below 2^-63);
 * the linear objective is the Gram form ``1/2 th'A th - b'th + 1/2 y'y``;
 * chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form);
+* D-GADMM (``dgadmm_linear``) is that recurrence over a list of chains: neighbours, roles and the
+  degree's inverse follow the chain of the iteration; ``dgadmm_chains`` prescribes the chains;
 * the exact logistic prox (``gadmm_logistic_newton``) has no oracle counterpart: it follows the header
   of csrc/kernels/chain_newton.hip and is held against the torch path (models/logistic.py:newton_prox)
   by tests/test_hp_reference_cpu.py. Its long-double run is the converged prox (stop tolerance 1e-17);
@@ -96,6 +98,107 @@ def gadmm_linear(X, y, rho, K, dtype=LD):
         thetas[k] = th
         obj[k] = _gram_objective(A, b, yy, th)
     return thetas, mu, obj
+
+
+def chain_tables(chains):
+    """What every worker is in every epoch of ``chains`` (a list of ``(first_iteration, path)``, ``path``
+    position -> worker), by plain loops over the chains: a list, one entry per epoch, of
+    ``(first_iteration, {worker: (position, left, right)})`` with neighbours as worker ids (None at an
+    end). A worker at an even position is a head; its degree is the number of its neighbours."""
+    out = []
+    for first, path in chains:
+        path = [int(w) for w in path]
+        n = len(path)
+        assert sorted(path) == list(range(n)), "a chain is a permutation of the workers"
+        out.append((int(first), {w: (p, path[p - 1] if p > 0 else None, path[p + 1] if p < n - 1 else None)
+                                 for p, w in enumerate(path)}))
+    assert all(a[0] < b[0] for a, b in zip(out, out[1:])), "epochs start at increasing iterations"
+    return out
+
+
+def flush_pairs(chains):
+    """Per epoch e, ``{worker: (old left, old right)}`` of the workers that were HEADS of epoch e - 1's
+    chain: their dual update of the last iteration before the re-chain is still pending there and must
+    be applied with these, the OLD chain's, neighbours. Epoch 0: empty."""
+    tabs = chain_tables(chains)
+    out = [{}]
+    for (_, old), _ in zip(tabs, tabs[1:]):
+        out.append({w: (l, r) for w, (p, l, r) in old.items() if p % 2 == 0})
+    return out
+
+
+DGADMM_MUTANTS = ("ignore", "flush-new", "old-degree")
+
+
+def _dgadmm_run(X, y, rho, K, chains, dtype, mutant=None):
+    """The recurrence of ``dgadmm_linear`` with the duals of EVERY iteration (K, N, d): a run to
+    iteration k is a prefix of a longer one over the same chains."""
+    N, m, d = X.shape
+    assert mutant is None or mutant in DGADMM_MUTANTS
+    if mutant == "ignore":
+        chains = chains[:1]
+    tabs = chain_tables(chains)
+    assert tabs[0][0] == 1 and len(tabs[0][1]) == N
+    A, b, yy = _gram(X, y, dtype)
+    rho = np.asarray(rho, dtype=dtype)
+    eye = np.eye(d, dtype=dtype)
+    Minv = [{g: spd_inverse(A[n] + g * rho * eye, dtype) for g in (1, 2)} for n in range(N)]
+    th = np.zeros((N, d), dtype=dtype)
+    mu = np.zeros((N, d), dtype=dtype)
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    mus = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    e = 0
+    for k in range(1, K + 1):
+        first_of_epoch = e + 1 < len(tabs) and tabs[e + 1][0] == k
+        if first_of_epoch:
+            e += 1
+        tab = tabs[e][1]
+        order = sorted(tab, key=lambda w: tab[w][0])  # workers by chain position
+        for phase in (0, 1):
+            for w in order[phase::2]:
+                _, l, r = tab[w]
+                rhs = b[w] - mu[w]
+                if l is not None:
+                    rhs = rhs + rho * th[l]
+                if r is not None:
+                    rhs = rhs + rho * th[r]
+                src = tabs[e - 1][1] if (mutant == "old-degree" and first_of_epoch) else tab
+                deg = (src[w][1] is not None) + (src[w][2] is not None)
+                th[w] = Minv[w][deg] @ rhs
+        last_of_epoch = e + 1 < len(tabs) and tabs[e + 1][0] == k + 1
+        for w in order:
+            p, l, r = tab[w]
+            if mutant == "flush-new" and last_of_epoch and p % 2 == 0:
+                _, l, r = tabs[e + 1][1][w]  # a head's pending update, applied with the NEW neighbours
+            upd = np.zeros(d, dtype=dtype)
+            if r is not None:
+                upd = upd + rho * (th[w] - th[r])
+            if l is not None:
+                upd = upd - rho * (th[l] - th[w])
+            mu[w] = mu[w] + upd
+        thetas[k - 1] = th
+        mus[k - 1] = mu
+        obj[k - 1] = _gram_objective(A, b, yy, th)
+    return thetas, mus, obj
+
+
+def dgadmm_linear(X, y, rho, K, chains, dtype=LD, mutant=None):
+    """D-GADMM (``oracle.reference.dgadmm_linear``): GADMM with per-worker duals whose chain changes.
+    ``chains``: a list of ``(first_iteration, path)``, ``path`` position -> worker, the first at
+    iteration 1 (what ``NativeChainEngine.run_persistent(epochs=...)`` takes). Iteration k runs on the
+    chain of the last epoch that started at or before k: the workers at even positions (heads), then
+    the others (tails), each applying the cached inverse of ``A_n + g rho I`` for ITS degree g in
+    {1, 2} on THAT chain, then every worker's ``mu`` with the neighbours of that chain (so the update of
+    the last iteration before a re-chain uses the old chain). On the single epoch ``(1, identity)`` the
+    operations and their order are ``gadmm_linear``'s.
+    ``mutant`` names a wrong implementation (tests/test_hp_reference_cpu.py measures how far each sits
+    from the reference): ``"ignore"`` never re-chains; ``"flush-new"`` applies the heads' dual update of
+    the last iteration before a re-chain with the NEW chain's neighbours; ``"old-degree"`` takes, in
+    the first iteration after a re-chain, the inverse of each worker's degree on the OLD chain.
+    Returns ``(theta (K, N, d), mu (N, d) after iteration K, objectives (K,))``."""
+    th, mus, obj = _dgadmm_run(np.asarray(X), y, rho, K, chains, dtype, mutant)
+    return th, mus[-1], obj
 
 
 def star_admm_linear(X, y, rho, K, dtype=LD):
@@ -1170,4 +1273,111 @@ def gram_int_shapes():
     out = {(m, d) for d in GRAM_F64_D for m in GRAM_F64_M} | {(m, d) for d in GRAM_F64_SPLIT_D for m, _ in GRAM_F64_SPLIT}
     out |= {GRAM_F64_AUTO[1:]} | {(m, d) for d in GRAM_OZ_D for m in GRAM_OZ_M} | {(m, 3) for m in GRAM_OZ_LONG}
     out |= {(m, d) for d in GRAM_CRT_D for m in GRAM_CRT_M} | {(m, 3) for m in GRAM_CRT_LONG}
+    return sorted(out)
+
+
+# ------------------------------------------------------------------------------------------------
+# D-GADMM (tests/test_gpu_dgadmm_classes.py): prescribed chains, the cases and their references.
+DGADMM_MOVES = ("reverse", "rotate", "same", "random")
+
+
+def dgadmm_chains(n, K, coherence):
+    """The prescribed chains of a D-GADMM case: ``[(first_iteration, path), ...]``, deterministic, no
+    ``find_path2`` draw. The initial chain is a seeded permutation that is not the identity (worker id !=
+    chain position != local index); at every re-chain iteration (``rechain_iterations(K, coherence)``)
+    the next move of the cycle ``DGADMM_MOVES`` is applied to the current chain:
+
+    * reverse: left and right swap; at even n every head becomes a tail;
+    * rotate by one: every role flips (but the wrapped worker's at odd n), the first worker, an end,
+      goes to the other end, its neighbour becomes an end and the old last worker an interior one;
+    * the same chain again;
+    * a new seeded random permutation.
+
+    The cycle starts at "reverse" for even n and at "rotate" for odd n: the reversal of an odd chain
+    leaves every worker its role and its pair of neighbours, so a case whose only re-chain it were
+    (coherence K) would not notice a kernel that ignores re-chains."""
+    from gadmm_amd.parallel.topology import rechain_iterations
+    rng = np.random.default_rng([int(n), int(coherence), 7919])
+    path = [int(v) for v in rng.permutation(n)]
+    if path == list(range(n)):
+        path = path[::-1]
+    chains = [(1, list(path))]
+    step = n % 2
+    for it in rechain_iterations(K, coherence):
+        move = DGADMM_MOVES[step % len(DGADMM_MOVES)]
+        step += 1
+        if move == "reverse":
+            path = path[::-1]
+        elif move == "rotate":
+            path = path[1:] + path[:1]
+        elif move == "random":
+            path = [int(v) for v in rng.permutation(n)]
+        chains.append((int(it), list(path)))
+    assert len(chains) == 1 or any(a[1] != b[1] for a, b in zip(chains, chains[1:])), "no re-chain changes the chain"
+    return chains
+
+
+def _chains_key(chains):
+    return tuple((int(f), tuple(int(w) for w in p)) for f, p in chains)
+
+
+def _dgadmm_history(n, m, d, chains, K, dtype, mutant=None):
+    """One run of the recurrence per (case, chains, arithmetic), K_ITERS long for the tests that stop
+    at the cap and PERSISTENT_OVERRUN longer for the iteration a persistent kernel happens to stop at
+    (the chains end at the cap: the kernels re-chain at none of the iterations past it)."""
+    run = K if K <= K_ITERS else max(K, K_ITERS + PERSISTENT_OVERRUN)
+
+    def build():
+        X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
+        out = _dgadmm_run(X, y, rho, run, chains, dtype, mutant)
+        _freeze(X, y, *out)
+        return (X, y, rho) + out
+    return _cached(("dgadmm-run", n, m, d, _chains_key(chains), run, np.dtype(dtype).name, mutant), build)
+
+
+def dgadmm_case(n, m, d, coherence, K=K_ITERS, chains=None):
+    """``(X, y, rho, chains, Reference)`` of ``dgadmm_linear`` on ``make_linear(n, m, d, seed_of(n, m,
+    d))`` over ``dgadmm_chains(n, min(K, K_ITERS), coherence)`` (or the explicit ``chains``), K iterations
+    long: the long-double run, and the float64 run of the same recurrence as the noise measure. A
+    ``K > K_ITERS`` is the iteration a persistent kernel stopped at, past a cap of K_ITERS."""
+    if chains is None:
+        chains = dgadmm_chains(n, min(K, K_ITERS), coherence)
+    chains = [(int(f), [int(w) for w in p]) for f, p in chains]
+
+    def build():
+        X, y, rho, th, mus, obj = _dgadmm_history(n, m, d, chains, K, LD)
+        _, _, _, th64, mus64, obj64 = _dgadmm_history(n, m, d, chains, K, np.float64)
+        return X, y, rho, chains, Reference((th[:K], mus[K - 1], obj[:K]), (th64[:K], mus64[K - 1], obj64[:K]), rho, d)
+    return _cached(("dgadmm", n, m, d, _chains_key(chains), K), build)
+
+
+def dgadmm_matrices(chains):
+    """``(path_matrix (E, n), cost_matrix (E, n - 1) of ones)`` of ``chains`` for
+    ``dynamic_group_admm_v0`` / ``PathSchedule(kind="matrix")``: row e is the chain of epoch e."""
+    P = np.asarray([p for _, p in chains], dtype=np.int64)
+    return P, np.ones((P.shape[0], max(P.shape[1] - 1, 0)))
+
+
+# (n, m, d) -> coherences of tests/test_gpu_dgadmm_classes.py (why each shape is there is written next
+# to that file's parameter lists; the d of the LDS thresholds are derived from the kernels' LDS formula
+# there and asserted to be these).
+DGADMM_SMALL = [(2, 3, 1), (3, 7, 3), (5, 40, 32), (4, 40, 33), (5, 60, 52)]
+DGADMM_REG16 = [(5, 70, 53), (4, 40, 64)]
+DGADMM_LDS_EXACT = [(3, 80, 65), (3, 100, 81)]
+DGADMM_LDS_IDENTITY = [(3, 100, 82), (3, 120, 99)]
+DGADMM_INELIGIBLE = (3, 120, 100)
+DGADMM_MULTI_WG = [(13, 20, 8), (25, 12, 5), (13, 60, 52)]
+DGADMM_GRAPH = [(3, 7, 3), (3, 80, 65), (3, 150, 129), (3, 280, 257)]
+DGADMM_SWEEP = [((2, 40, 33), 1), ((3, 40, 33), 3), ((5, 40, 33), 7), ((13, 40, 33), 3)]
+
+
+def dgadmm_cases():
+    """Every ``(n, m, d, coherence)`` a GPU test of D-GADMM runs, sorted."""
+    out = set()
+    for s in DGADMM_SMALL + DGADMM_REG16 + DGADMM_LDS_EXACT + DGADMM_LDS_IDENTITY + DGADMM_MULTI_WG:
+        out |= {s + (1,), s + (3,)}
+    for s in [(5, 60, 52), (13, 20, 8)]:
+        out |= {s + (7,), s + (K_ITERS,)}
+    out |= {DGADMM_INELIGIBLE + (3,), (3, 80, 65, 1)} | {s + (3,) for s in DGADMM_GRAPH}
+    out |= {s + (c,) for s, c in DGADMM_SWEEP}
     return sorted(out)

@@ -215,10 +215,12 @@ def test_blocked_kernel_stops_at_52(monkeypatch):
 # register kernel with both degree variants resident (NV = 2), QT = 13 at d <= 52 and 16 at 53..64
 @pytest.mark.parametrize("n,m,d", [(5, 60, 52), (5, 70, 53)])
 def test_dgadmm_per_worker_dynamic(n, m, d, monkeypatch):
-    """Coherence 3 for K iterations against the float64 oracle (oracle.reference.dgadmm_linear, fed the
-    chains tests/test_gpu_dyn_sweep.py feeds it: find_path2 drawn from the schedule's seed). float64
-    against float64; the bound is the static chain's of the same shape (the long-double helper does not
-    re-chain). The kernel stops ``lag`` iterations after the cap and re-chains at none of them."""
+    """Coherence 3 for K iterations over the chains tests/test_gpu_dyn_sweep.py uses (find_path2 drawn
+    from the schedule's seed), against the long-double run of the re-chaining recurrence over those
+    very chains (hp_reference.dgadmm_case with explicit chains) under its own bound; the float64 oracle
+    (oracle.reference.dgadmm_linear), fed them through its callback, is held to the same reference.
+    The kernel stops ``lag`` iterations after the cap and re-chains at none of them.
+    tests/test_gpu_dgadmm_classes.py covers the other dynamic classes over prescribed chains."""
     from gadmm_amd.algorithms import dynamic_group_admm
     from gadmm_amd.models import LinearRegression
     from gadmm_amd.oracle import reference as R
@@ -248,11 +250,13 @@ def test_dgadmm_per_worker_dynamic(n, m, d, monkeypatch):
 
     o = R.dgadmm_linear(X, y, rho, last, 0.0, 0.0, p0, c0, 3, rechain)
     assert len(seq) == len([it for it in range(2, K + 1) if it % 3 == 0])
-    ref = H.linear_case(n, m, d, last)[3]
-    sc = float(np.max(np.abs(o.theta)))
-    out = {"objective": H.noise_level(np.asarray(o.obj[:K]), a.obj, np.abs(o.obj[:K])) / ref.b_obj,
-           "theta": H.noise_level(o.theta, _host(theta), sc) / ref.b_theta,
-           "dual": H.noise_level(o.dual, _host(mu), rho * sc) / ref.b_dual}
+    chains = [(1, list(p0))] + [(it, list(seq[it][0])) for it in sorted(seq)]
+    assert any(a_[1] != b_[1] for a_, b_ in zip(chains, chains[1:]))
+    ref = H.dgadmm_case(n, m, d, 3, last, chains=chains)[4]
+    out = {"objective": ref.err_obj(a.obj) / ref.b_obj, "theta": ref.err_theta(_host(theta), last) / ref.b_theta,
+           "dual": ref.err_dual(_host(mu)) / ref.b_dual,
+           "oracle objective": ref.err_obj(np.asarray(o.obj)) / ref.b_obj,
+           "oracle theta": ref.err_theta(o.theta, last) / ref.b_theta, "oracle dual": ref.err_dual(o.dual) / ref.b_dual}
     eng.close()
     _report("D-GADMM per-worker dynamic %s" % ((n, m, d),), out)
 

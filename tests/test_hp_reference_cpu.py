@@ -1,5 +1,6 @@
 """CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py,
-tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py and tests/test_gpu_setup_kernels.py.
+tests/test_gpu_dgadmm_classes.py, tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py and
+tests/test_gpu_setup_kernels.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
@@ -216,6 +217,138 @@ def test_bound_catches_what_a_wrong_kernel_does(n, m, d):
     Xb[0, :, d - 1] *= 1.0 + 1e-9  # the last column of worker 0's shard, nine digits in
     thb, mub, obb = H.gadmm_linear(Xb, y, rho, K, np.float64)
     assert ref.err_theta(thb[-1]) > ref.b_theta and ref.err_dual(mub) > ref.b_dual and ref.err_obj(obb) > ref.b_obj
+
+
+# ------------------------------------------------------------------------------------------------
+# D-GADMM (tests/test_gpu_dgadmm_classes.py): the re-chaining recurrence against the static one, the
+# oracle and the torch path over the same prescribed chains; the host's epoch tables against the
+# neighbours, roles and flush pairs the reference derives; and the power of the bound against three
+# wrong re-chains.
+DGADMM_CASES = H.dgadmm_cases()
+DGADMM_POWER = 1000.0
+
+
+@pytest.mark.parametrize("n,m,d", [(2, 3, 1), (5, 60, 52), (3, 80, 65)])
+def test_dgadmm_single_identity_epoch_is_gadmm(n, m, d):
+    """One epoch on the identity chain: the operations of ``gadmm_linear`` in its order, bit for bit."""
+    X, y, rho = H.make_linear(n, m, d, H.seed_of(n, m, d))
+    for dtype in (H.LD, np.float64):
+        a = H.dgadmm_linear(X, y, rho, K, [(1, list(range(n)))], dtype)
+        b = H.gadmm_linear(X, y, rho, K, dtype)
+        assert all(u.dtype == dtype and np.array_equal(u, v) for u, v in zip(a, b))
+
+
+def test_dgadmm_chains_are_prescribed():
+    from gadmm_amd.parallel.topology import rechain_iterations
+    for n, _, _, coh in DGADMM_CASES:
+        chains = H.dgadmm_chains(n, K, coh)
+        assert chains == H.dgadmm_chains(n, K, coh)  # deterministic
+        assert [f for f, _ in chains] == [1] + [int(v) for v in rechain_iterations(K, coh)]
+        assert all(sorted(p) == list(range(n)) for _, p in chains) and chains[0][1] != list(range(n))
+        assert any(a[1] != b[1] for a, b in zip(chains, chains[1:]))
+    # the cycle at even and at odd n, and what each move does to the roles
+    c4, c5 = H.dgadmm_chains(4, K, 3), H.dgadmm_chains(5, K, 3)
+    assert c4[1][1] == c4[0][1][::-1] and c4[2][1] == c4[1][1][1:] + c4[1][1][:1] and c4[3][1] == c4[2][1]
+    assert c5[1][1] == c5[0][1][1:] + c5[0][1][:1] and c5[2][1] == c5[1][1] and c5[4][1] == c5[3][1][::-1]
+    t = H.chain_tables(c5[:2])
+    first = c5[0][1][0]
+    assert t[0][1][first][:2] == (0, None) and t[1][1][first][0] == 4 and t[1][1][first][2] is None
+    assert all((t[0][1][w][0] + t[1][1][w][0]) % 2 == 1 for w in range(5) if w != first)  # every other role flips
+    assert H.flush_pairs(c5[:2])[1] == {w: v[1:] for w, v in t[0][1].items() if v[0] % 2 == 0}
+
+
+@pytest.mark.parametrize("n,m,d,coh", DGADMM_CASES)
+def test_dgadmm_reproduces_oracle_and_torch_path(n, m, d, coh):
+    """The oracle's D-GADMM, fed the prescribed chains through its ``rechain`` callback, and the torch
+    path, fed them as a path matrix, are within the case's bound of the long-double run."""
+    import torch
+    from gadmm_amd.algorithms import dynamic_group_admm_v0
+    from gadmm_amd.models import LinearRegression
+    X, y, rho, chains, ref = H.dgadmm_case(n, m, d, coh)
+    assert ref.theta.dtype == H.LD and ref.theta.shape == (K, n, d) and ref.obj.shape == (K,)
+    by_it = {f: p for f, p in chains}
+    ones = np.ones(max(n - 1, 0))
+    o = R.dgadmm_linear(X, y, rho, K, 0.0, 0.0, chains[0][1], ones, coh, lambda it: (by_it[it], ones))
+    assert o.iters == K and len(o.obj) == K
+    _check("D-GADMM oracle %s coh %s" % ((n, m, d), coh), ref, o.theta, o.dual, o.obj)
+    P, C = H.dgadmm_matrices(chains)
+    model = LinearRegression(torch.from_numpy(np.array(X)), torch.from_numpy(np.array(y)))
+    a = dynamic_group_admm_v0(model, rho, 0.0, 0.0, K, P, C, coh, faithful_initial_cost=False, backend="torch")
+    theta, mu, nxt = a.extra["state"]
+    assert a.extra["backend"] == "torch" and a.iters == K and nxt == K + 1 and len(a.obj) == K
+    _check("D-GADMM torch %s coh %s" % ((n, m, d), coh), ref, theta.numpy(), mu.numpy(), a.obj)
+
+
+def _epoch_expectation(chains):
+    """(slots (E, n, 4), positions (E, n), flush (E, n, 2)) in the layout of ``epoch_tables_numpy`` (local
+    workers 0..n-1) and ``epoch_flush_table`` from the reference's own tables, by plain loops."""
+    tabs, fl = H.chain_tables(chains), H.flush_pairs(chains)
+    E, n = len(tabs), len(tabs[0][1])
+    slots = np.zeros((E, n, 4), dtype=np.int32)
+    pos = np.zeros((E, n), dtype=np.int32)
+    flush = np.full((E, n, 2), -1, dtype=np.int32)
+    for e, (_, tab) in enumerate(tabs):
+        for w, (p, l, r) in tab.items():
+            slots[e, w] = (w, w, -1 if l is None else l, -1 if r is None else r)
+            pos[e, w] = p
+            if w in fl[e]:
+                flush[e, p] = [-1 if v is None else v for v in fl[e][w]]
+    return slots, pos, flush
+
+
+@pytest.mark.parametrize("n,coh", sorted({(c[0], c[3]) for c in DGADMM_CASES}))
+def test_epoch_tables_agree_with_the_reference(n, coh):
+    """The tables the dynamic kernels read (engine/chain_engine.py: ``epoch_tables_numpy``,
+    ``epoch_flush_table``; csrc/runtime/topology.cpp: ``gadmm_epoch_tables``,
+    ``gadmm_epoch_tables_blocked`` where the library is already built) against the neighbours, roles and
+    old-chain flush pairs of the reference's chains."""
+    from gadmm_amd.engine.chain_engine import epoch_flush_table, epoch_tables_numpy
+    from gadmm_amd.ops import native
+    chains = H.dgadmm_chains(n, K, coh)
+    slots, pos, flush = _epoch_expectation(chains)
+    P = np.ascontiguousarray(H.dgadmm_matrices(chains)[0])
+    E = len(chains)
+    loc = np.arange(n, dtype=np.int64)
+    s_np, p_np = epoch_tables_numpy(P, loc)
+    assert np.array_equal(s_np, slots) and np.array_equal(p_np, pos)
+    assert np.array_equal(epoch_flush_table(P), flush)
+    sub = loc[::2].copy()  # a rank that holds every other worker
+    s_sub, p_sub = epoch_tables_numpy(P, sub)
+    assert np.array_equal(s_sub[:, :, 1:], slots[:, ::2, 1:]) and np.array_equal(p_sub, pos[:, ::2])
+    assert np.array_equal(s_sub[:, :, 0], np.broadcast_to(np.arange(len(sub)), (E, len(sub))))
+    lib = native.load(build_if_missing=False)
+    if lib is None or getattr(lib, "gadmm_epoch_tables_blocked", None) is None:
+        return  # the native builders are held to the same tables wherever the library is built
+    es, pp = np.empty((E * n * 4,), dtype=np.int32), np.empty((E * n,), dtype=np.int32)
+    assert lib.gadmm_epoch_tables(P.ctypes.data, E, n, loc.ctypes.data, n, es.ctypes.data, pp.ctypes.data) == 0
+    assert np.array_equal(es.reshape(E, n, 4), slots) and np.array_equal(pp.reshape(E, n), pos)
+    fl = np.empty((E * n * 2,), dtype=np.int32)
+    assert lib.gadmm_epoch_tables_blocked(P.ctypes.data, E, n, es.ctypes.data, pp.ctypes.data, fl.ctypes.data) == 0
+    # the blocked tables are in chain-position order: slot p is the worker at position p
+    by_pos = np.take_along_axis(slots, P[:, :, None].astype(np.int64), axis=1)
+    assert np.array_equal(es.reshape(E, n, 4), by_pos) and np.array_equal(pp.reshape(E, n), pos)
+    assert np.array_equal(fl.reshape(E, n, 2), flush)
+
+
+@pytest.mark.parametrize("n,m,d,coh", DGADMM_CASES)
+def test_dgadmm_bound_rejects_a_wrong_rechain(n, m, d, coh):
+    """Power of the GPU tests, as a condition on the reference alone: a float64 run that ignores the
+    re-chains, one that applies the heads' pending dual with the NEW chain's neighbours, and one that
+    takes the OLD degree's inverse in the first solve after a re-chain each sit at least 1000 bounds
+    from the reference in some compared quantity (the last two are defined from three workers on: with
+    two, every chain has the same neighbours and degrees). The float64 run itself sits below 1/8."""
+    X, y, rho, chains, ref = H.dgadmm_case(n, m, d, coh)
+
+    def ratios(run):
+        th, mu, ob = run
+        return (ref.err_theta(th[-1]) / ref.b_theta, ref.err_dual(mu) / ref.b_dual, ref.err_obj(ob) / ref.b_obj)
+
+    assert max(ratios(H.dgadmm_linear(X, y, rho, K, chains, np.float64))) <= 1.0 / 8
+    for mutant in H.DGADMM_MUTANTS if n >= 3 else H.DGADMM_MUTANTS[:1]:
+        r = ratios(H.dgadmm_linear(X, y, rho, K, chains, np.float64, mutant=mutant))
+        print("D-GADMM %s coh %s mutant %-10s: err/bound theta %.2e dual %.2e objective %.2e"
+              % ((n, m, d), coh, mutant, *r))
+        assert max(r) >= DGADMM_POWER, (mutant, r)
 
 
 # ------------------------------------------------------------------------------------------------
