@@ -13,6 +13,9 @@ specification), in the form the kernels evaluate them:
 * chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form);
 * D-GADMM (``dgadmm_linear``) is that recurrence over a list of chains: neighbours, roles and the
   degree's inverse follow the chain of the iteration; ``dgadmm_chains`` prescribes the chains;
+* Q-GADMM (``qgadmm_linear``) is ``gadmm_linear`` over a static chain whose theta table holds the public
+  models th_hat; its quantizer line restates gadmm_amd/algorithms/quantize.py and is held against it bit
+  for bit, the run against the torch path, by tests/test_hp_reference_cpu.py;
 * the exact logistic prox (``gadmm_logistic_newton``) has no oracle counterpart: it follows the header
   of csrc/kernels/chain_newton.hip and is held against the torch path (models/logistic.py:newton_prox)
   by tests/test_hp_reference_cpu.py. Its long-double run is the converged prox (stop tolerance 1e-17);
@@ -1381,3 +1384,320 @@ def dgadmm_cases():
     out |= {DGADMM_INELIGIBLE + (3,), (3, 80, 65, 1)} | {s + (3,) for s in DGADMM_GRAPH}
     out |= {s + (c,) for s, c in DGADMM_SWEEP}
     return sorted(out)
+
+
+# ------------------------------------------------------------------------------------------------
+# Q-GADMM (tests/test_gpu_qgadmm_classes.py): the quantized recurrence, the cases and their seeds.
+QGADMM_MUTANTS = ("dual-true", "rhs-true", "obj-hat", "u-position", "no-clamp")
+_M64 = (1 << 64) - 1
+
+
+def q_uniforms(seed, it, n_workers, w, d):
+    """The ``d`` uniforms of worker id ``w`` at iteration ``it`` (1-based): the counter formula of the
+    gadmm_amd/algorithms/quantize.py docstring restated in Python integers mod 2^64 (no code shared with
+    ``quantize.u01``): ``x = seed + 0x9e3779b97f4a7c15 * (((it * N + w) * d + i) + 1)``, the splitmix64
+    finaliser, ``u = (z >> 11) * 2^-53``. float64 (d,): 53-bit integers times a power of two, exact."""
+    out = np.empty(d, dtype=np.float64)
+    for i in range(d):
+        z = (int(seed) + 0x9e3779b97f4a7c15 * ((int(it) * int(n_workers) + int(w)) * int(d) + i + 1)) & _M64
+        z = ((z ^ (z >> 30)) * 0xbf58476d1ce4e5b9) & _M64
+        z = ((z ^ (z >> 27)) * 0x94d049bb133111eb) & _M64
+        z ^= z >> 31
+        out[i] = float(z >> 11) * 2.0 ** -53
+    return out
+
+
+def q_line(theta, hat, u, bits, dtype=LD, clamp=True):
+    """The quantizer line on one worker's row, every operation in ``dtype``: ``R = max|theta - hat|``,
+    ``delta = 2R / L``, ``q = clamp(floor((diff + R) / delta + u), 0, L)``, ``hat + (q delta - R)``; at
+    ``R == 0`` every code is 0 and ``hat`` stays. Returns ``(R, q (d,) int64, new hat (d,), margin)``;
+    the margin is ``min(frac, 1 - frac) * delta / max|theta|`` over the coordinates with ``|diff| < R``
+    (``frac`` the fractional part of ``(diff + R) / delta + u``), inf when there is none."""
+    theta = np.asarray(theta, dtype=dtype)
+    hat = np.asarray(hat, dtype=dtype)
+    u = np.asarray(u, dtype=dtype)
+    L = np.asarray((1 << int(bits)) - 1, dtype=dtype)
+    diff = theta - hat
+    R = np.max(np.abs(diff))
+    if R == 0:
+        return R, np.zeros(theta.shape, dtype=np.int64), hat.copy(), np.inf
+    delta = (np.asarray(2.0, dtype=dtype) * R) / L
+    s = (diff + R) / delta + u
+    fl = np.floor(s)
+    q = np.minimum(np.maximum(fl, np.asarray(0.0, dtype=dtype)), L) if clamp else fl
+    new = hat + (q * delta - R)
+    inner = np.abs(diff) < R
+    top = np.max(np.abs(theta))
+    margin = np.inf
+    if np.any(inner) and top > 0:
+        frac = (s - fl)[inner]
+        margin = float(np.min(np.minimum(frac, np.asarray(1.0, dtype=dtype) - frac)) * delta / top)
+    return R, q.astype(np.int64), new, margin
+
+
+def _qgadmm_run(X, y, rho, K, bits, seed, path, dtype, mutant=None):
+    """The recurrence of ``qgadmm_linear`` with the state of EVERY iteration: ``(theta (K, N, d),
+    th_hat (K, N, d), mu (K, N, d), objectives (K,), codes (K, N, d) int64, R (K, N), residual (K,),
+    margin (K,) the smallest flip margin up to each iteration)``; a run to k is a prefix of a longer one."""
+    N, m, d = X.shape
+    assert mutant is None or mutant in QGADMM_MUTANTS
+    path = list(range(N)) if path is None else [int(w) for w in path]
+    tab = chain_tables([(1, path)])[0][1]
+    assert len(tab) == N and N >= 2
+    A, b, yy = _gram(X, y, dtype)
+    rho = np.asarray(rho, dtype=dtype)
+    eye = np.eye(d, dtype=dtype)
+    Minv = [spd_inverse(A[w] + ((tab[w][1] is not None) + (tab[w][2] is not None)) * rho * eye, dtype)
+            for w in range(N)]
+    th = np.zeros((N, d), dtype=dtype)    # the true iterates
+    hat = np.zeros((N, d), dtype=dtype)   # the public models: what neighbours hold
+    mu = np.zeros((N, d), dtype=dtype)
+    thetas = np.zeros((K, N, d), dtype=dtype)
+    hats = np.zeros((K, N, d), dtype=dtype)
+    mus = np.zeros((K, N, d), dtype=dtype)
+    obj = np.zeros((K,), dtype=dtype)
+    codes = np.zeros((K, N, d), dtype=np.int64)
+    Rs = np.zeros((K, N), dtype=dtype)
+    res = np.zeros((K,), dtype=dtype)
+    margins = np.zeros((K,), dtype=np.float64)
+    margin = np.inf
+    seen = th if mutant == "rhs-true" else hat   # what a solve reads of its neighbours
+    dual = th if mutant == "dual-true" else hat  # what the dual update reads
+    for k in range(1, K + 1):
+        for phase in (0, 1):
+            for w in path[phase::2]:
+                p, l, r = tab[w]
+                rhs = b[w] - mu[w]
+                if l is not None:
+                    rhs = rhs + rho * seen[l]
+                if r is not None:
+                    rhs = rhs + rho * seen[r]
+                th[w] = Minv[w] @ rhs
+                u = q_uniforms(seed, k, N, p if mutant == "u-position" else w, d)
+                Rs[k - 1, w], codes[k - 1, w], hat[w], mg = q_line(th[w], hat[w], u, bits, dtype,
+                                                                   clamp=mutant != "no-clamp")
+                margin = min(margin, mg)
+        for w in path:
+            _, l, r = tab[w]
+            v = mu[w]
+            if l is not None:
+                v = v - rho * (dual[l] - dual[w])
+            if r is not None:
+                v = v + rho * (dual[w] - dual[r])
+            mu[w] = v
+        thetas[k - 1] = th
+        hats[k - 1] = hat
+        mus[k - 1] = mu
+        obj[k - 1] = _gram_objective(A, b, yy, hat if mutant == "obj-hat" else th)
+        tot = np.zeros((), dtype=dtype)
+        for a_, b_ in zip(path, path[1:]):   # K4 on public models: every chain edge once
+            e = hat[a_] - hat[b_]
+            tot = tot + e @ e
+        res[k - 1] = tot
+        margins[k - 1] = margin
+    return thetas, hats, mus, obj, codes, Rs, res, margins
+
+
+def qgadmm_linear(X, y, rho, K, bits, seed, path=None, dtype=LD, mutant=None):
+    """Q-GADMM (header of csrc/kernels/chain_quant.hip; specification gadmm_amd/algorithms/quantize.py)
+    on the static chain ``path`` (position -> worker; None: the identity): GADMM whose theta table holds
+    the public models ``th_hat``. Heads (even positions), then tails: worker w solves with the cached
+    inverse of ``A_w + deg rho I`` from ``b_w - mu_w + rho (th_hat_l + th_hat_r)``, then quantizes
+    ``theta_w - th_hat_w`` (``q_line``) with the uniforms of ``(iteration, worker ID w)`` -- not its chain
+    position -- and moves ``th_hat_w``; then every worker's ``mu`` from ``th_hat`` of itself and its
+    neighbours. The objective reads the true theta, the K4 residual (sum over chain edges of
+    ``|th_hat_a - th_hat_b|^2``) the public models. All arithmetic in ``dtype``.
+    ``mutant`` names a wrong implementation (tests/test_hp_reference_cpu.py measures how far each sits
+    from the reference): ``"dual-true"`` the duals read true theta; ``"rhs-true"`` the right-hand side
+    reads the neighbours' true theta; ``"obj-hat"`` the objective of ``th_hat``; ``"u-position"`` the
+    uniforms indexed by chain position; ``"no-clamp"`` no clamp of the code.
+    Returns ``(theta (K, N, d) true iterates, th_hat (N, d) after K, mu (N, d) after K, objectives (K,),
+    codes (K, N, d), R (K, N), K4 residual (K,), the run's smallest flip margin)``."""
+    th, hats, mus, obj, codes, Rs, res, margins = _qgadmm_run(np.asarray(X), y, rho, K, bits, seed, path, dtype, mutant)
+    return th, hats[-1], mus[-1], obj, codes, Rs, res, float(margins[-1])
+
+
+# The shapes of tests/test_gpu_qgadmm_classes.py (the edge each one sits on is written there).
+QGADMM_BITS = (4, 8, 16)
+QGADMM_GRAPH_SHAPES = [(2, 3, 1), (3, 7, 3), (3, 20, 4), (3, 20, 5), (3, 20, 8), (3, 20, 9), (4, 30, 16), (3, 30, 17),
+                       (4, 40, 64), (3, 80, 65), (4, 150, 128), (3, 150, 129), (3, 280, 256)]
+QGADMM_PERSISTENT_SHAPES = [(2, 3, 1), (3, 20, 4), (3, 20, 5), (3, 20, 8), (3, 20, 9), (4, 30, 16), (3, 30, 17),
+                            (5, 40, 32), (4, 40, 33), (5, 60, 52), (5, 70, 53), (4, 40, 64)]
+QGADMM_PERSISTENT_K = 8     # the cap of the persistent runs; the kernel stops up to PERSISTENT_OVERRUN later
+QGADMM_PERSISTENT_RUN = QGADMM_PERSISTENT_K + PERSISTENT_OVERRUN
+QGADMM_PATHS = {(5, 40, 33): (2, 0, 4, 1, 3), (4, 30, 16): (3, 2, 1, 0)}   # the permuted static chains (b = 8)
+QGADMM_FIRST_SEED, QGADMM_LAST_SEED = 1234, 1297
+QGADMM_MARGIN = 4.0         # a case is comparable while its smallest flip margin >= this many b_theta
+
+
+def _qgadmm_history(n, m, d, bits, seed, path, run, dtype, mutant=None, data=0):
+    def build():
+        X, y, rho = make_linear(n, m, d, seed_of(n, m, d) + data)
+        out = _qgadmm_run(X, y, rho, run, bits, seed, path, dtype, mutant)
+        _freeze(X, y, *out)
+        return (X, y, rho) + out
+    return _cached(("qgadmm-run", n, m, d, bits, seed, path, run, np.dtype(dtype).name, mutant, data), build)
+
+
+class QReference(Reference):
+    """``Reference`` of a Q-GADMM case (``theta`` the TRUE iterates (K, N, d), ``dual`` = mu after K,
+    ``obj``) plus ``hat`` (N, d) the public models after K, ``codes`` (K, N, d), ``R`` (K, N),
+    ``res`` (K,) the K4 residual, ``margin`` the run's smallest flip margin, ``seed``, ``path``, and
+    the bounds ``b_hat`` / ``b_R`` (errors over ``scale_theta``) and ``b_res`` (each entry over its own
+    value where that exceeds 1e-20 of the trace's largest, over the largest below that)."""
+
+    def __init__(self, ld, f64, rho, d, seed, path):
+        th, hats, mus, obj, codes, Rs, res, margins = ld
+        super().__init__((th, mus[-1], obj), (f64[0], f64[2][-1], f64[3]), rho, d)
+        self.seed, self.path = seed, path
+        self.hat, self.codes, self.R, self.res, self.margin = hats[-1], codes, Rs, res, float(margins[-1])
+        self.codes_agree = bool(np.array_equal(codes, f64[4]))
+        top = np.max(np.abs(res))
+        self.res_scale = np.where(np.abs(res) > 1e-20 * top, np.abs(res), top)
+        self.e_hat = noise_level(hats, f64[1], self.scale_theta)
+        self.e_R = noise_level(Rs, f64[5], self.scale_theta)
+        self.e_res = noise_level(res, f64[6], self.res_scale)
+        self.b_hat, self.b_R, self.b_res = bound(self.e_hat, d), bound(self.e_R, d), bound(self.e_res, d)
+
+    def err_hat(self, hat):
+        return noise_level(self.hat, hat, self.scale_theta)
+
+    def err_R(self, R):
+        """``R`` (N,) of every worker's last message against the reference's iteration-K values."""
+        return noise_level(self.R[-1], R, self.scale_theta)
+
+    def err_res(self, res):
+        res = np.asarray(res)
+        return noise_level(self.res[:len(res)], res, self.res_scale[:len(res)])
+
+
+def qgadmm_condition(n, m, d, bits, run, path=None, seed=QGADMM_FIRST_SEED):
+    """The condition on the reference alone that makes a quantized run comparable, at ``run``
+    iterations: ``(codes of the long-double and the float64 run identical, margin / b_theta)``; the
+    case qualifies when the first holds and the second is >= QGADMM_MARGIN."""
+    ref = _qgadmm_reference(n, m, d, bits, run, path, seed)[3]
+    return ref.codes_agree, ref.margin / ref.b_theta
+
+
+def _qgadmm_reference(n, m, d, bits, K, path, seed, run=None, data=0):
+    path = None if path is None else tuple(int(w) for w in path)
+    run = K if run is None else run
+    assert K <= run
+
+    def build():
+        ld = _qgadmm_history(n, m, d, bits, seed, path, run, LD, data=data)
+        f64 = _qgadmm_history(n, m, d, bits, seed, path, run, np.float64, data=data)
+        return ld[:3] + (QReference(tuple(a[:K] for a in ld[3:]), tuple(a[:K] for a in f64[3:]), ld[2], d, seed, path),)
+    return _cached(("qgadmm", n, m, d, bits, K, path, seed, run, data), build)
+
+
+# (n, m, d, bits, path) -> the quantizer seed of the case: the first of 1234, 1235, ... at which the
+# long-double and the float64 run produce identical codes and the smallest flip margin is
+# >= QGADMM_MARGIN b_theta over the longest run a test asks for (``qgadmm_run_length``). Found once by
+# a search on the CPU; only the cases that 1234 does not serve are listed, each with what 1234 gave.
+# tests/test_hp_reference_cpu.py asserts the condition for every case and that an earlier seed fails.
+QGADMM_SEEDS = {
+    (3, 20, 5, 16, None): 1235,   # 1234: margin / b_theta = 0.75 at 20 iterations
+    (2, 3, 2, 16, None): 1235,    # (a CPU-only case, qgadmm_power_cases) 1234: 1.63 at 24 iterations
+}
+# (shape, bits) pairs of QGADMM_PERSISTENT_SHAPES that no seed up to QGADMM_LAST_SEED serves over
+# QGADMM_PERSISTENT_RUN iterations (they would be left out of the persistent tests): none.
+QGADMM_DROPPED = ()
+
+
+def qgadmm_run_length(d):
+    """The longest run a test asks of a case: the persistent kernel (d <= 64) stops up to
+    PERSISTENT_OVERRUN iterations past its cap of QGADMM_PERSISTENT_K; above it K_ITERS on the graph
+    engine. The flip margin only falls as a run goes on, so a seed that serves it serves every prefix."""
+    return max(K_ITERS, QGADMM_PERSISTENT_RUN) if d <= 64 else K_ITERS
+
+
+def qgadmm_seed(n, m, d, bits, path=None):
+    """``(seed, run length it is good for)`` of a case."""
+    path = None if path is None else tuple(int(w) for w in path)
+    return QGADMM_SEEDS.get((n, m, d, bits, path), QGADMM_FIRST_SEED), qgadmm_run_length(d)
+
+
+def qgadmm_case(n, m, d, bits, K, path=None):
+    """``(X, y, rho, QReference)`` of ``qgadmm_linear`` on ``make_linear(n, m, d, seed_of(n, m, d))`` with
+    the case's seed (``QReference.seed``), K iterations long: the long-double run, and the float64 run of
+    the same recurrence as the noise measure. Every K of a case is a prefix of one cached run."""
+    seed, run = qgadmm_seed(n, m, d, bits, path)
+    return _qgadmm_reference(n, m, d, bits, K, path, seed, run)
+
+
+def qgadmm_power_cases():
+    """The cases on which tests/test_hp_reference_cpu.py measures how far wrong variants of the
+    recurrence land: ``qgadmm_cases()`` with the data of (2, 3, 1) replaced by (2, 3, 2). With ONE
+    coordinate the difference is always extremal, its code is 0 or L and ``th_hat + (q delta - R)`` is
+    theta itself up to rounding: th_hat == theta whatever the data, and a variant that reads the one
+    for the other computes the recurrence. Two coordinates are the fewest at which one is interior."""
+    return [((2, 3, 2) if c[:3] == (2, 3, 1) else c[:3]) + c[3:] for c in qgadmm_cases()]
+
+
+def qgadmm_cases():
+    """Every ``(n, m, d, bits, path)`` a GPU test of Q-GADMM runs."""
+    shapes = QGADMM_GRAPH_SHAPES + [s for s in QGADMM_PERSISTENT_SHAPES if s not in QGADMM_GRAPH_SHAPES]
+    return [s + (b, None) for s in shapes for b in QGADMM_BITS] + [s + (8, p) for s, p in QGADMM_PATHS.items()]
+
+
+# ------------------------------------------------------------------------------------------------
+# Cases for the sensitivity of the bound to a MISSING CLAMP. With ``|diff| <= R`` the code
+# ``floor((diff + R) / delta + u)`` is in [0, L] already; the clamp acts only on an extremal coordinate
+# with ``diff = +R`` whose ``c = L`` and whose draw is so close to 1 that ``c + u`` ROUNDS up to L + 1
+# (``u > 1 - 2^-50`` at b = 4, ``> 1 - 2^-38`` at b = 16): no seed 1234, 1235, ... gets there in a short
+# run. The counter formula is a bijection of the seed, though, so a seed can be SOLVED for: the one at
+# which a chosen (iteration, worker, coordinate) draws the largest uniform there is, ``1 - 2^-53``.
+_QM1, _QM2, _QGOLD = 0xbf58476d1ce4e5b9, 0x94d049bb133111eb, 0x9e3779b97f4a7c15
+
+
+def q_seed_drawing_top(low, it, n_workers, w, d, i):
+    """The seed at which ``q_uniforms(seed, it, n_workers, w, d)[i] == 1 - 2^-53``: the splitmix64
+    finaliser inverted (each xor-shift and each odd multiplier is a bijection mod 2^64) on
+    ``z = (2^53 - 1) << 11 | low``; ``low`` in 0 .. 2047 are the bits the uniform drops, so there are
+    2048 such seeds, which differ in every other draw."""
+    assert 0 <= int(low) < 2048
+    z = (((1 << 53) - 1) << 11) | int(low)
+    z ^= (z >> 31) ^ (z >> 62)
+    z = (z * pow(_QM2, -1, 1 << 64)) & _M64
+    z ^= (z >> 27) ^ (z >> 54)
+    z = (z * pow(_QM1, -1, 1 << 64)) & _M64
+    z ^= (z >> 30) ^ (z >> 60)
+    return (z - _QGOLD * ((int(it) * int(n_workers) + int(w)) * int(d) + int(i) + 1)) & _M64
+
+
+QGADMM_CLAMP_K = 8   # iterations of a missing-clamp case: the clamp acts in the first
+
+
+def qgadmm_clamp_case(n, m, d, bits, path=None):
+    """``(X, y, rho, QReference, (data offset, worker, coordinate, low))`` of the missing-clamp case of a
+    shape: data and seed chosen so that IN THE FIRST ITERATION the clamp of a head acts. A head's first
+    solve, ``Minv_w b_w``, depends on no draw; the case needs a head whose largest coordinate is positive
+    (``diff = +R``) and whose ``c`` is L exactly in float64, so that ``c + (1 - 2^-53)`` rounds to L + 1
+    (about every third head: it turns on how ``2R / L`` rounds). The data is
+    ``make_linear(n, m, d, seed_of(n, m, d) + t)`` for the first t = 0, 1, ... that has such a head (the
+    first along the chain), the seed ``q_seed_drawing_top(low, 1, n, w, d, i)`` for the first ``low``
+    at which the case is comparable (identical codes in long double and float64, margin >=
+    QGADMM_MARGIN b_theta) over QGADMM_CLAMP_K iterations. The long-double run needs no clamp there
+    (``L + 1 - 2^-53`` is a long double: its floor is L), the float64 run does, and both give L."""
+    path_l = list(range(n)) if path is None else [int(w) for w in path]
+    top = np.float64(1.0) - 2.0 ** -53
+
+    def build():
+        for t in range(64):
+            X, y, rho = make_linear(n, m, d, seed_of(n, m, d) + t)
+            A, b, _ = _gram(X, y, np.float64)
+            for pos in range(0, n, 2):
+                w = path_l[pos]
+                th = spd_inverse(A[w] + ((pos > 0) + (pos < n - 1)) * rho * np.eye(d), np.float64) @ b[w]
+                i = int(np.argmax(np.abs(th)))
+                u = np.zeros(d)
+                u[i] = top
+                if th[i] > 0 and q_line(th, np.zeros(d), u, bits, np.float64, clamp=False)[1][i] == (1 << bits):
+                    for low in range(2048):
+                        seed = q_seed_drawing_top(low, 1, n, w, d, i)
+                        out = _qgadmm_reference(n, m, d, bits, QGADMM_CLAMP_K, path, seed, data=t)
+                        if out[3].codes_agree and out[3].margin >= QGADMM_MARGIN * out[3].b_theta:
+                            return out + ((t, w, i, low),)
+        raise AssertionError("no missing-clamp case for %r" % ((n, m, d, bits, path),))
+    return _cached(("qgadmm-clamp", n, m, d, bits, None if path is None else tuple(path_l)), build)

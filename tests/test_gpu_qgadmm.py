@@ -153,7 +153,8 @@ def test_against_the_spec(N, d):
     condition on the reference alone: its smallest flip margin is >= 1e-10 (the CPU prototype gives
     >= 1.6e-10 on these cases), far above the engines' rounding differences, so no code flips and the
     traces agree at rtol 1e-11, the tolerance tests/test_gpu_sweep.py uses for the oracle. (b = 16 is
-    left out: its margins are about 1e-12.)"""
+    left out: its margins are about 1e-12; tests/test_gpu_qgadmm_classes.py holds b = 16 to a long-double
+    reference under a bound that is checked against the flip margin case by case.)"""
     from gadmm_amd.algorithms import quantized_group_admm
     from gadmm_amd.models.linear import LinearRegression
     X, y, obj0 = _problem(N, d)

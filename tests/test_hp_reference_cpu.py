@@ -1,6 +1,6 @@
 """CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py,
-tests/test_gpu_dgadmm_classes.py, tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py and
-tests/test_gpu_setup_kernels.py.
+tests/test_gpu_dgadmm_classes.py, tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py,
+tests/test_gpu_setup_kernels.py and tests/test_gpu_qgadmm_classes.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
@@ -791,3 +791,189 @@ def test_non_spd_matrix_first_bad_pivot(d, bad):
     assert np.isnan(Mn[bad, bad]) and np.isnan(Mn).sum() == 1
     Mn[bad, bad] = 1.5
     assert np.linalg.eigvalsh(Mn)[0] > 0.5
+
+
+# ------------------------------------------------------------------------------------------------
+# Q-GADMM (tests/test_gpu_qgadmm_classes.py). A quantized run is comparable only while no rounding
+# decision can flip: the condition on the reference alone for every case the GPU file uses, the
+# quantizer line against the specification bit for bit, the float64 reference against the torch path,
+# and the power of the bound against five wrong variants of the recurrence.
+QGADMM_CASES = H.qgadmm_cases()
+QGADMM_POWER_CASES = H.qgadmm_power_cases()   # (2, 3, 1) replaced by (2, 3, 2): see there
+QGADMM_ALL_CASES = QGADMM_CASES + [c for c in QGADMM_POWER_CASES if c not in QGADMM_CASES]
+QGADMM_POWER = 100.0
+
+
+def _q_qualifies(n, m, d, bits, run, path, seed):
+    agree, ratio = H.qgadmm_condition(n, m, d, bits, run, path, seed)
+    return agree and ratio >= H.QGADMM_MARGIN, agree, ratio
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", QGADMM_ALL_CASES)
+def test_qgadmm_case_is_comparable(n, m, d, bits, path):
+    """At the longest run a GPU test asks of the case the long-double and the float64 run produce
+    identical codes in every iteration and the smallest flip margin is >= 4 b_theta; the case's seed is
+    the first from 1234 on of which that is true."""
+    seed, run = H.qgadmm_seed(n, m, d, bits, path)
+    assert H.QGADMM_FIRST_SEED <= seed <= H.QGADMM_LAST_SEED
+    assert run == (H.K_ITERS if d > 64 else H.QGADMM_PERSISTENT_K + H.PERSISTENT_OVERRUN) and run >= H.K_ITERS
+    ok, agree, ratio = _q_qualifies(n, m, d, bits, run, path, seed)
+    ref = H.qgadmm_case(n, m, d, bits, run, path)[3]
+    print("Q-GADMM %s b=%d chain %s seed %d, %d iterations: codes agree %s, margin %.3g = %.3g b_theta"
+          % ((n, m, d), bits, path, seed, run, agree, ref.margin, ratio))
+    assert ok and ref.seed == seed and ref.codes.shape == (run, n, d) and ref.theta.dtype == H.LD
+    for earlier in range(H.QGADMM_FIRST_SEED, seed):
+        ok, agree, ratio = _q_qualifies(n, m, d, bits, run, path, earlier)
+        print("   seed %d: codes agree %s, margin / b_theta %.3g" % (earlier, agree, ratio))
+        assert not ok
+    # a shorter run of the case is a prefix of this one, and its margin is no smaller
+    short = H.qgadmm_case(n, m, d, bits, H.QGADMM_PERSISTENT_K, path)[3]
+    assert np.array_equal(short.codes, ref.codes[:H.QGADMM_PERSISTENT_K]) and short.margin >= ref.margin
+
+
+def test_qgadmm_dropped_pairs():
+    """No (shape, 16-bit) pair of the persistent tests is dropped; the rule for one that were: at most
+    two, none at d in {16, 17, 52, 53, 64}, and truly no seed in 1234..1297 that serves 24 iterations."""
+    dropped = H.QGADMM_DROPPED
+    assert len(dropped) <= 2
+    for (n, m, d), bits in dropped:
+        assert bits == 16 and (n, m, d) in H.QGADMM_PERSISTENT_SHAPES and d not in (16, 17, 52, 53, 64)
+        assert not any(_q_qualifies(n, m, d, bits, H.QGADMM_PERSISTENT_RUN, None, s)[0]
+                       for s in range(H.QGADMM_FIRST_SEED, H.QGADMM_LAST_SEED + 1))
+    assert set(H.QGADMM_SEEDS) <= set(QGADMM_ALL_CASES)
+
+
+def test_qgadmm_uniforms_restate_the_counter_formula():
+    from gadmm_amd.algorithms import quantize as Q
+    for seed, it, n, w, d in [(1234, 1, 3, 0, 1), (1235, 24, 5, 4, 64), (7, 20, 4, 2, 256), (2 ** 64 - 1, 3, 2, 1, 9)]:
+        u = H.q_uniforms(seed, it, n, w, d)
+        assert u.dtype == np.float64 and np.all((u >= 0) & (u < 1))
+        assert np.array_equal(u, Q.u01(seed, it, n, w, d))
+    assert not np.array_equal(H.q_uniforms(1234, 2, 5, 1, 8), H.q_uniforms(1234, 2, 5, 3, 8))
+
+
+@pytest.mark.parametrize("bits", H.QGADMM_BITS)
+def test_qgadmm_quantizer_line_is_the_specification(bits):
+    """On hand-picked (theta, hat, u) the float64 quantizer line of the reference equals
+    ``quantize.quantize_rows`` bit for bit: a generic row, R == 0, and a row whose first two coordinates
+    are extremal (diff = +R with u = 1 - 2^-53, diff = -R with u = 0; R = L / 8, so delta = 1 / 4 and
+    c = L are exact and c + u rounds to L + 1: the one place where the clamp is live)."""
+    from gadmm_amd.algorithms import quantize as Q
+    L = (1 << bits) - 1
+    rng = np.random.default_rng(bits)
+    hat = rng.standard_normal(9)
+    rows = [(hat + 0.3 * rng.standard_normal(9), hat, rng.random(9)),
+            (hat.copy(), hat, rng.random(9)),
+            (np.zeros(9), np.zeros(9), rng.random(9))]
+    R = L / 8.0
+    step = np.array([R, -R, 0.0, 0.25 * R, -0.5 * R, R / 3, -R / 7, 0.999 * R, -0.999 * R])
+    base = np.arange(9.0) / 4 - 1.0   # multiples of 1/4: base + step is exact, so diff = step exactly
+    u = np.concatenate([[1.0 - 2.0 ** -53, 0.0], rng.random(7)])
+    rows.append((base + step, base, u))
+    for i, (theta, h, u) in enumerate(rows):
+        Rq, q, new, _ = Q.quantize_rows(theta[None], h[None], bits, u[None])
+        r64, q64, new64, margin = H.q_line(theta, h, u, bits, np.float64)
+        assert r64.dtype == np.float64 and new64.dtype == np.float64
+        assert np.array_equal(np.float64(r64).view(np.uint64), Rq[0].view(np.uint64)), i
+        assert np.array_equal(q64, q[0]) and np.array_equal(new64.view(np.uint64), new[0].view(np.uint64)), i
+        if i in (1, 2):
+            assert r64 == 0 and not q64.any() and np.array_equal(new64, h) and margin == np.inf
+        rld, qld, newld, _ = H.q_line(theta, h, u, bits, H.LD)
+        assert newld.dtype == H.LD and (i != 0 or np.array_equal(qld, q64))
+    assert np.array_equal(theta - h, step) and q64[0] == L and q64[1] == 0
+    assert np.array_equal(new64[:2], theta[:2])   # both ends land on theta: L delta - R = R exactly here
+    loose = H.q_line(theta, h, u, bits, np.float64, clamp=False)[1]
+    assert loose[0] == L + 1 and np.array_equal(loose[1:], q64[1:])
+
+
+@pytest.mark.parametrize("bits", H.QGADMM_BITS)
+@pytest.mark.parametrize("n,m,d", [(3, 7, 3), (4, 30, 16), (3, 80, 65)])
+def test_qgadmm_reproduces_torch_path(n, m, d, bits):
+    """The torch path (``quantized_group_admm`` on CPU tensors, identity chain) stands where a kernel
+    stands: true theta, th_hat (any flipped code moves it by a whole delta, >= 4 b_theta), the duals and
+    the objectives are within the case's bounds of the long-double run, the residual within its own."""
+    import torch
+    from gadmm_amd.algorithms import quantized_group_admm
+    from gadmm_amd.models import LinearRegression
+    X, y, rho, ref = H.qgadmm_case(n, m, d, bits, K)
+    model = LinearRegression(torch.from_numpy(np.array(X)), torch.from_numpy(np.array(y)))
+    a = quantized_group_admm(model, rho, 0.0, 0.0, K, bits, seed=ref.seed)
+    hat, mu, nxt = a.extra["state"]
+    assert a.extra["backend"] == "torch" and a.iters == K and nxt == K + 1 and len(a.obj) == K
+    _check("Q-GADMM torch %s b=%d" % ((n, m, d), bits), ref, a.extra["theta_true"].numpy(), mu.numpy(), a.obj)
+    rh, rr = ref.err_hat(hat.numpy()) / ref.b_hat, ref.err_res(a.primal_res) / ref.b_res
+    print("   th_hat %.3f residual %.3f; torch margin %.3g, reference %.3g" % (rh, rr, a.extra["min_flip_margin"], ref.margin))
+    assert rh <= 1.0 and rr <= 1.0
+
+
+def _q_distances(n, m, d, bits, path, mutant):
+    """(theta, objective) err / bound of the float64 run of ``mutant`` (None: the recurrence itself)."""
+    seed, run = H.qgadmm_seed(n, m, d, bits, path)
+    X, y, rho, ref = H.qgadmm_case(n, m, d, bits, run, path)
+    out = H.qgadmm_linear(X, y, rho, run, bits, seed, path, np.float64, mutant)
+    return ref.err_theta(out[0][-1]) / ref.b_theta, ref.err_obj(out[3]) / ref.b_obj
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", QGADMM_POWER_CASES)
+def test_qgadmm_bound_rejects_a_wrong_variant(n, m, d, bits, path):
+    """Power of the GPU tests, as a condition on the reference alone: a float64 run whose duals read the
+    true theta, one whose right-hand side reads the neighbours' true theta, one that evaluates the
+    objective of th_hat and (on a permuted chain; on the identity chain it is the recurrence itself) one
+    that indexes the uniforms by chain position each sit at least 100 bounds from the reference in theta
+    or in the objective. The float64 run itself sits below 1/8.
+
+    The cases are those of the GPU file, but for (2, 3, 1), whose data is replaced by (2, 3, 2): with one
+    coordinate th_hat == theta up to rounding whatever the data (``qgadmm_power_cases``), and every
+    variant sat at 2.5e-3 / 2.2e-2 bounds, the distance of the recurrence itself. Measured: >= 2.3e6
+    bounds in the objective everywhere (and, obj-hat aside, >= 80 in theta, >= 2.6e3 from d = 3 on);
+    the table is in profiles/qgadmm_classes/README.md."""
+    assert max(_q_distances(n, m, d, bits, path, None)) <= 1.0 / 8
+    for mutant in H.QGADMM_MUTANTS[:4] if path is not None else H.QGADMM_MUTANTS[:3]:
+        r = _q_distances(n, m, d, bits, path, mutant)
+        print("Q-GADMM %s b=%d chain %s mutant %-10s: err/bound theta %.2e objective %.2e"
+              % ((n, m, d), bits, path, mutant, *r))
+        assert max(r) >= QGADMM_POWER, (mutant, r)
+    if path is not None:
+        X, y, rho, ref = H.qgadmm_case(n, m, d, bits, K)
+        same = H.qgadmm_linear(X, y, rho, K, bits, ref.seed, None, np.float64, "u-position")
+        assert np.array_equal(same[0], H.qgadmm_linear(X, y, rho, K, bits, ref.seed, None, np.float64)[0])
+
+
+def test_qgadmm_seed_solved_for_a_draw():
+    """``q_seed_drawing_top`` inverts the counter formula: the chosen draw is 1 - 2^-53, under both
+    statements of the formula, and its 2048 solutions differ elsewhere."""
+    from gadmm_amd.algorithms import quantize as Q
+    for low, it, n, w, d, i in [(0, 1, 2, 0, 1, 0), (5, 1, 3, 2, 9, 4), (2047, 7, 5, 3, 256, 255)]:
+        seed = H.q_seed_drawing_top(low, it, n, w, d, i)
+        assert 0 <= seed < 2 ** 64
+        for u in (H.q_uniforms(seed, it, n, w, d), Q.u01(seed, it, n, w, d)):
+            assert u[i] == 1.0 - 2.0 ** -53 and (d == 1 or np.sum(u == u[i]) == 1)
+    a, b = (H.q_uniforms(H.q_seed_drawing_top(low, 1, 3, 2, 9, 4), 1, 3, 2, 9) for low in (0, 1))
+    assert a[4] == b[4] and not np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", QGADMM_CASES)
+def test_qgadmm_bound_rejects_a_missing_clamp(n, m, d, bits, path):
+    """The fifth variant, no clamp of the code, held to the same 100 bounds on every shape of the GPU
+    file. With the seeds 1234, 1235, ... the variant IS the recurrence (it sat at 0.02 .. 0.125 bounds
+    in every case): with ``|diff| <= R`` the code is in [0, L] before the clamp, which acts only when
+    ``c = L`` and ``c + u`` rounds up to L + 1, and no such draw comes up. So the data of every case is
+    replaced (``qgadmm_clamp_case``): the first data seed with a head whose first difference has
+    ``c = L`` exactly, and the quantizer seed SOLVED from the counter formula so that this coordinate
+    draws 1 - 2^-53 in iteration 1. The case is comparable (asserted), the float64 recurrence with the
+    clamp sits below 1/8, and the variant's code L + 1 moves th_hat by a whole delta: measured
+    >= 1.7e6 bounds in theta and >= 3.9e6 in the objective."""
+    X, y, rho, ref, (t, w, i, low) = H.qgadmm_clamp_case(n, m, d, bits, path)
+    Kc, L = H.QGADMM_CLAMP_K, (1 << bits) - 1
+    assert ref.codes_agree and ref.margin >= H.QGADMM_MARGIN * ref.b_theta and ref.codes.shape == (Kc, n, d)
+    assert ref.seed == H.q_seed_drawing_top(low, 1, n, w, d, i) and ref.codes[0, w, i] == L
+    out = {}
+    for mutant in (None, "no-clamp"):
+        run = H.qgadmm_linear(X, y, rho, Kc, bits, ref.seed, path, np.float64, mutant)
+        out[mutant] = (ref.err_theta(run[0][-1]) / ref.b_theta, ref.err_obj(run[3]) / ref.b_obj, run[4])
+    print("Q-GADMM %s b=%d chain %s (data +%d, worker %d coordinate %d, low %d, margin %.3g b_theta) mutant no-clamp: "
+          "err/bound theta %.2e objective %.2e" % ((n, m, d), bits, path, t, w, i, low, ref.margin / ref.b_theta,
+                                                   *out["no-clamp"][:2]))
+    assert max(out[None][:2]) <= 1.0 / 8 and np.array_equal(out[None][2], ref.codes)
+    assert out["no-clamp"][2][0, w, i] == L + 1   # the clamp is what the float64 recurrence relied on
+    assert max(out["no-clamp"][:2]) >= QGADMM_POWER, out["no-clamp"][:2]
