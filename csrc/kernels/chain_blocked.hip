@@ -18,11 +18,16 @@
 //
 // Schedule per iteration it (reference semantics, group_ADMM_closedForm.m / A4 with a static chain):
 //   [every k iterations] publish owned (theta, mu), refresh halo (theta, mu)      -- 1 hand-off
-//   [stop rule] decision of iteration it - lag (prefetched one iteration ahead)
-//   head phase: heads apply the lazy dual with the tails' theta^{it-1}, solve, write theta^it to LDS
+//   head phase: heads apply the lazy dual with the tails' theta^{it-1}, solve, write theta^it to LDS;
+//               an idle tail wave polls the decision of iteration it + 1 - lag (prefetched one
+//               iteration ahead) and writes the stop flags
 //   barrier
-//   tail phase: tails solve with the heads' theta^it, dual update
-//   barrier
+//   tail phase: every wave reads the stop / abort flags with its operand reads; tails solve with the
+//               heads' theta^it, dual update
+//   barrier, then a scalar test of the flags read in the tail phase (no LDS access between the
+//   barrier and the next head phase's operand reads)
+// The dependent path of a phase is LDS reads -> right-hand side -> staging -> 52 FMAs -> permlane
+// reduce -> LDS write -> barrier; the flag reads are kept off it (profiles/phase_critical_path).
 // Owned workers also post theta^it into a ring; OBJECTIVE workgroups (one wave per worker, A_n in
 // VGPRs) evaluate f_n(theta^it) off the critical path and feed the monitor, which sums in worker
 // order and posts the stop decision (monitor as in chain_persistent.hip). Grid: W worker
@@ -256,22 +261,32 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
   const int deg = (int)has_l + (int)has_r;
   const double rho = a.rho;
   const bool in = lane < d;
-  // Decision wave: polls the stop decision during the tail phase, when heads are idle. A halo head
-  // is preferred: it never stores to global memory, so its decision load does not queue behind
+  // Decision wave: polls the stop decision during the HEAD phase, when tails are idle, so that the
+  // flags it writes are published by the mid-iteration barrier and every wave picks them up with its
+  // tail-phase operand reads, one phase before the iteration's closing barrier acts on them. A halo
+  // tail is preferred: it never stores to global memory, so its decision load does not queue behind
   // write-through granule stores (vmcnt counts stores on gfx9).
-  // Next best: an idle wave (u >= nv: no position). A computed tail can never be it (it is busy in
-  // exactly the phase the poll runs in) -- a workgroup whose only position is a tail (one worker per
-  // rank, odd position) polls on an idle wave.
+  // Next best: an idle wave (u >= nv: no position), then an owned tail (it posts its deferred
+  // ring granule at the start of the iteration and is idle after that). A head can never be it (it is busy in exactly the phase the
+  // poll runs in), nor can a tail wave that hosts a row group of the halo head (HALO, hq below). One
+  // always exists: nv < MAXW leaves an idle wave, nv == MAXW has six tails of which at most four host.
   // Invariant: every wave of the workgroup, inactive ones included, executes the same sequence of
   // lds_barrier()s (exchange, re-chain, stop) -- the decision wave may be an idle one, which is only
   // correct because idle waves follow the active waves' schedule exactly (DYN: from the same staged
   // epoch starts, see stage_epochs below).
-  int vdec = -1;
-  for (int u = 0; u < nv && vdec < 0; ++u)
-    if (((ra + u) % 2) == 0 && (ra + u < s0 || ra + u > e0)) vdec = u;
-  if (vdec < 0 && nv < MAXW) vdec = nv;
-  if (vdec < 0) vdec = (ra % 2 == 0) ? 0 : 1;
-  const bool dec_wave = u == vdec;
+  int vdec = -1, cdec = 3;
+  for (int vv = 0; vv < MAXW; ++vv) {
+    const int uu = vv < MAXW / 2 ? 2 * vv + h0 : 2 * (vv - MAXW / 2) + (1 - h0);
+    const bool act = uu < nv, hd_ = act && ((ra + uu) % 2) == 0;
+    const bool own = act && ra + uu >= s0 && ra + uu <= e0;
+    if (hd_ || (hosted && vv >= MAXW / 2 && vv < MAXW / 2 + 4)) continue;
+    const int c = act ? (own ? 2 : 0) : 1;
+    if (c < cdec) {
+      cdec = c;
+      vdec = vv;
+    }
+  }
+  const bool dec_wave = v == vdec;
 
   double* thS = lds;                       // [MAXW][64] theta of every computed worker
   double* xs = thS + MAXW * 64;            // [MAXW][QSTAGE] per-wave quad GEMV staging
@@ -365,8 +380,9 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
   if (threadIdx.x == 0) stop_iter_lds = 0;
   lds_barrier();
 
-  // a stop decision for iteration j arrives before iteration j + lag runs: polled during the tail
-  // phase of iteration j + lag - 1 and published by that phase's closing barrier
+  // a stop decision for iteration j arrives before iteration j + lag runs: polled during the head
+  // phase of iteration j + lag - 1, published by the mid-iteration barrier, read by every wave in the
+  // tail phase and acted on after that iteration's closing barrier
   // owned (theta, mu) after iteration j, for the exchange at the start of iteration j + 1: into
   // this GPU's table and into every peer GPU that computes position p too
   auto publish = [&](int j) {
@@ -435,6 +451,32 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
   int rslot = a.start_iter % a.ring;                  // == it % ring
   int dslot = (a.start_iter + 1 - a.lag) % a.ring;     // == (it + 1 - lag) % ring (>= 0 once polled)
   if (dslot < 0) dslot += a.ring;
+  // Decision wave, in the head phase of iteration it: decision[it + 1 - lag] into stop_lds /
+  // stop_iter_lds ahead of the mid-iteration barrier. A late decision is waited for, never skipped.
+  auto poll_decision = [&]() {
+    if (!(TL && (a.dbg & 1)) && dec_wave && lane == 0 && it + 1 - a.start_iter >= a.lag) {
+      const int jdec = it + 1 - a.lag;
+      const unsigned tj = make_tag(a.epoch, jdec);
+      // loaded during the previous iteration's head phase: its L2 round trip (~0.7 us) is off the
+      // critical path; a decision that was not yet published then is re-polled here
+      unsigned long long dv = dv_pref;
+      if ((unsigned)(dv >> 32) != tj) dv = load_dec<SYS>(&a.decg[dslot]);
+      for (int spin = 0; (unsigned)(dv >> 32) != tj; ++spin) {
+        if ((spin & 7) == 7 && now_ticks() > deadline) {
+          abort_lds = 1;
+          break;
+        }
+        GADMM_POLL_PAUSE();
+        dv = load_dec<SYS>(&a.decg[dslot]);
+      }
+      const unsigned code = (unsigned)(dv & 0xffffffffu);
+      if (code && (unsigned)(dv >> 32) == tj) {
+        stop_lds = (int)code;
+        stop_iter_lds = jdec;
+      }
+      dv_pref = load_dec<SYS>(&a.decg[dslot + 1 == a.ring ? 0 : dslot + 1]);
+    }
+  };
   for (;; ++it, rslot = rslot + 1 == a.ring ? 0 : rslot + 1, dslot = dslot + 1 == a.ring ? 0 : dslot + 1) {
     if (ring_defer) {  // tails: theta^{it-1}, before a re-chain may replace th
       put_granule<SYS>(local, rtab, ring_p + (rslot == 0 ? a.ring - 1 : rslot - 1) * ring_slot_bytes,
@@ -472,7 +514,11 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
           if (solver) {  // the new worker's inverse (lane-major padded image, coalesced unmasked loads)
                          // and b: issued before the state poll below, so they overlap the hand-off
             quad_load_image<QT>(Mq, a.minv_pad + ((long)li * a.nvar + a.deg_to_var[deg]) * (long)(512 * ((QT + 1) / 2)));
-            bb = in ? a.b[(long)li * d + lane] : 0.0;
+            // (the address is formed here: hoisted, `a.b + lane` would hold two VGPRs across the whole
+            // loop for this rare block, which the d = 50 instantiation does not have to spare)
+            int bl = lane;
+            asm volatile("" : "+v"(bl));
+            bb = in ? a.b[(long)li * d + bl] : 0.0;
           }
           const bool fl = pending && of.x >= 0, fr = pending && of.y >= 0;  // it was a head: dual pending
           double t0 = 0.0, t1 = 0.0, tl = 0.0, tr = 0.0;
@@ -505,7 +551,9 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
         next_x = it + k;
         blk0 = it;
         lds_barrier();
-        if (abort_lds) break;
+        // (one GPU: a timed-out re-chain is seen with the flags read after the mid-iteration barrier)
+        if constexpr (SYS)
+          if (abort_lds) break;
       }
     }
     // ---- halo exchange every k iterations (state after iteration it - 1); the owned workers
@@ -536,7 +584,15 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
         thS[u * 64 + lane] = th;
       }
       lds_barrier();  // refreshed halo theta visible to the neighbouring waves
-      if (abort_lds) break;
+      // One GPU: a timed-out refresh is seen with the flags read after the mid-iteration barrier; until
+      // then the workgroup computes one iteration on partly loaded halos, which done = 4 discards. In
+      // that iteration its heads still post theta^it to the objective ring and, with k = 1, the owned
+      // workers publish(it): granules with VALID tags and garbage payload reach the neighbouring
+      // workgroups and the monitor. Nothing may rely on ring or table contents after an abort.
+      // Across GPUs a workgroup that flagged an abort must not push further granules to a peer: it
+      // leaves here.
+      if constexpr (SYS)
+        if (abort_lds) break;
       blk0 = it;
       next_x = it + k;
       ++xc;
@@ -596,20 +652,35 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
       if (hsr) r = r + rho * tr;
       hst[256 + hq * 64 + lane] = quad_rowgroup_lds<QT>(Mh, hq, in ? r : 0.0, myx);
     }
+    poll_decision();  // the (idle tail) decision wave fetches decision[it + 1 - lag]
     pending = 1;
     lds_barrier();
+    // One GPU: the stop and abort flags as of the mid-iteration barrier, read by EVERY wave (idle ones
+    // too) in the shadow of the tail phase's operand reads: one lgkmcnt wait covers both, and the test
+    // after the closing barrier is a scalar compare. The fence keeps the read up here. Across GPUs the
+    // flags are read after the closing barrier, as before (see there).
+    int stop_v = 0, abort_v = 0;
+    if constexpr (!SYS) {
+      stop_v = stop_lds;
+      abort_v = abort_lds;
+      asm volatile("" ::: "memory");
+    }
     if (stamp) ts[4] = (long long)now_ticks();
 
-    // ---- tail phase; the (idle head) decision wave fetches decision[it + 1 - lag]
+    // ---- tail phase
     // the next iteration starts with a regular exchange (DYN: unless it starts a new epoch)
     const bool xnext = !HALO && it + 1 == next_x && !(DYN && it + 1 == next_start);
     // tail-wave stamps (wave MAXW/2 by default), timeline row 128 + g: [start, rhs, gemv, stores, barrier]
     // (GADMM_BLK_DBG bits 4-6 pick another tail wave: MAXW/2 + ((dbg >> 4) & 7))
     const bool tstamp = TL && v == MAXW / 2 + ((a.dbg >> 4) & 7) && it - a.start_iter < a.timeline_iters && g < 128;
     long long tt[4] = {0, 0, 0, 0};
+    int flags_s;  // the flags in an SGPR: taken once the operand wait has covered their read
     if (active && !head && u >= uo_lo - (slack - 1) && u <= uo_hi + (slack - 1)) {
       if (tstamp) tt[0] = (long long)now_ticks();
       double tl = nbl ? thL[lane] : 0.0, tr = nbr ? thR[lane] : 0.0;
+      // (taken right behind the operand reads, whose wait covers the flag read: the two words are
+      // not held in VGPRs across the right-hand side)
+      flags_s = __builtin_amdgcn_readfirstlane(stop_v) | __builtin_amdgcn_readfirstlane(abort_v);
       if (HALO && hdir != 0) {  // the hosted halo head's theta^it: fold the four row-group partials
         double pq[4] = {hst[256 + lane], hst[320 + lane], hst[384 + lane], hst[448 + lane]};
         const double y = quad_reduce(pq);
@@ -648,35 +719,16 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
         if (lane == 0 && it - 1 < a.max_iter) a.rres[(long)(it - 1) * n + w] = rs;
       }
       if (tstamp) tt[3] = (long long)now_ticks();
-    } else if (active && owned && in) {  // heads: theta^it and the (still pending) mu are final
-      if (xnext) publish(it);
-      if (ring_post) put_granule<SYS>(local, rtab, ring_p + rslot * ring_slot_bytes, make_tag(a.epoch, it), th);
+    } else {
+      flags_s = __builtin_amdgcn_readfirstlane(stop_v) | __builtin_amdgcn_readfirstlane(abort_v);
+      if (active && owned && in) {  // heads: theta^it and the (still pending) mu are final
+        if (xnext) publish(it);
+        if (ring_post) put_granule<SYS>(local, rtab, ring_p + rslot * ring_slot_bytes, make_tag(a.epoch, it), th);
+      }
     }
     if (TL && g < 8 && it - a.start_iter < a.timeline_iters && lane == 0) {
       const long long t_end = (long long)now_ticks();  // this wave's tail-phase work done
       a.timeline[((long)(160 + g * MAXW + v) * a.timeline_iters + (it - a.start_iter)) * 8] = t_end;
-    }
-    if (!(TL && (a.dbg & 1)) && dec_wave && !(active && !head) && lane == 0 && it + 1 - a.start_iter >= a.lag) {
-      const int jdec = it + 1 - a.lag;
-      const unsigned tj = make_tag(a.epoch, jdec);
-      // loaded during the previous iteration's tail phase: its L2 round trip (~0.7 us) is off the
-      // critical path; a decision that was not yet published then is re-polled here
-      unsigned long long dv = dv_pref;
-      if ((unsigned)(dv >> 32) != tj) dv = load_dec<SYS>(&a.decg[dslot]);
-      for (int spin = 0; (unsigned)(dv >> 32) != tj; ++spin) {
-        if ((spin & 7) == 7 && now_ticks() > deadline) {
-          abort_lds = 1;
-          break;
-        }
-        GADMM_POLL_PAUSE();
-        dv = load_dec<SYS>(&a.decg[dslot]);
-      }
-      const unsigned code = (unsigned)(dv & 0xffffffffu);
-      if (code && (unsigned)(dv >> 32) == tj) {
-        stop_lds = (int)code;
-        stop_iter_lds = jdec;
-      }
-      dv_pref = load_dec<SYS>(&a.decg[dslot + 1 == a.ring ? 0 : dslot + 1]);
     }
     lds_barrier();
     if (tstamp && lane == 0) {
@@ -691,7 +743,10 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
       tl[6] = ts[6];
       tl[7] = ts[7];
     }
-    if (abort_lds || stop_lds) {
+    // across GPUs the flags are read here: an abort flagged in this tail phase (a peer's theta did not
+    // come) ends the loop before another granule is pushed to a peer; one GPU: the mid-iteration read
+    if constexpr (SYS) flags_s = abort_lds | stop_lds;
+    if (flags_s) {
       ++it;  // the next iteration to run
       break;
     }
