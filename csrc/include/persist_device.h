@@ -292,6 +292,28 @@ __device__ __forceinline__ Placement place_block(int xcd, u32x4* xchk, unsigned 
   return p;
 }
 
+// A sweep slot's PersistArgs (kernels that run up to 8 solves in one launch, slot j on the blocks
+// b % 8 == j): written by the host before the launch and never by a kernel, so it is read like kernel
+// arguments, through the constant address space (wave-uniform scalar loads).
+typedef __attribute__((address_space(4))) PersistArgs SweepArgs;
+
+// place_block for a block of a sweep slot: the layout is always 8-strided (one GPU), the slot's working
+// blocks are blockIdx.x >> 3 < nb, and the grid is sized for the widest slot of the launch, so a block
+// with bid >= nb belongs to a wider slot: it is returned as a spacer BEFORE the placement check and
+// before any barrier (it posts nothing and nobody waits for it). xchk / tag / ctl are the slot's own:
+// nothing assumes which XCD a slot gets, and `local` is the verdict on the slot's own blocks.
+__device__ __forceinline__ Placement place_block_sweep(int xcd, u32x4* xchk, unsigned tag, int nb,
+                                                       unsigned long long deadline, int* lds_flag, ChainCtl* ctl) {
+  Placement p;
+  p.bid = (int)(blockIdx.x >> 3);
+  p.spacer = p.bid >= nb;
+  p.local = false;
+  if (p.spacer) return p;
+  if (xcd > 1) p.local = xcd_verdict(xchk, p.bid, nb, deadline, lds_flag, tag);
+  if (ctl && p.bid == 0 && threadIdx.x == 0) ctl->placed = p.local ? 2 : 1;
+  return p;
+}
+
 // The stop-rule monitor of every persistent engine: one workgroup per run (on the monitor rank), of
 // which wave 0 works and the others return (`wave`: the caller's wave index, wave-uniform). Per iteration it polls the tagged objective granules of
 // all n workers in ring slot it % ring, sums them in worker order (the order of the graph engine's

@@ -774,10 +774,6 @@ __device__ __forceinline__ void chain_blocked_body(const PA& a) {
   }
 }
 
-// A sweep slot's PersistArgs: written by the host before the launch and never by a kernel, so it is
-// read like kernel arguments, through the constant address space.
-typedef __attribute__((address_space(4))) PersistArgs SweepArgs;
-
 template <int DB, bool SYS, bool TL, bool DYN = false, bool HALO = false>
 __global__ void __launch_bounds__(64 * MAXW) chain_blocked_kernel(PersistArgs a) {
   chain_blocked_body<DB, SYS, TL, DYN, HALO, false>(a);

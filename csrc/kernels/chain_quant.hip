@@ -8,13 +8,15 @@
 // whose theta table holds th_hat: rhs and duals read th_hat of the neighbours (and of the worker
 // itself for the duals), the objective and the stop rule read the true theta.
 //
-// Two kernels, the same arithmetic in the same order (bit-identical iterates, as the unquantized
+// Two kernel families, the same arithmetic in the same order (bit-identical iterates, as the unquantized
 // engines: symv_cols / quad_gemv sum in one order):
 //   chain_phase_linear_q     one GADMM phase of the graph engine, d <= 256 (body of chain_phase_linear
 //                            + the quantize stage): th_hat goes into the theta table.
 //   chain_persistent_q_kernel  the whole solve in one launch, d <= 64, one wave per worker, static
 //                            chain, one GPU: the hand-off is the packed message itself.
+//   chain_persistent_q_sweep_kernel  up to 8 such solves in one launch, one per XCD (the same body).
 #define GADMM_POLL_SLEEP 0  // one hand-off wait per phase on the critical path: poll back to back
+#include <stdio.h>
 #include <stdlib.h>
 #include <cstddef>
 #include "gadmm_common.h"
@@ -236,8 +238,15 @@ __device__ __forceinline__ unsigned long long raw_bits(const u32x4& g) {
   return ((unsigned long long)g.w << 32) | g.y;
 }
 
-template <int QT>
-__global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
+// The persistent Q solve (described above) as a body shared by the single-solve and the sweep kernel.
+// SWEEP: the body runs as one slot of chain_persistent_q_sweep_kernel (below): always 8-strided, this
+// slot's blocks are blockIdx.x >> 3, and a block past the slot's own n_local + 1 leaves before the
+// placement check and before any barrier (place_block_sweep). Everything the body reads or writes is
+// named by the slot's own arguments.
+// PA: PersistArgs (the kernel's own argument) or SweepArgs (a slot's entry, read through the constant
+// address space: wave-uniform scalar loads, like the kernarg segment).
+template <int QT, bool SWEEP, class PA>
+__device__ __forceinline__ void q_persistent_body(const PA& a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int abort_lds;
   __shared__ int stop_lds;
@@ -247,7 +256,9 @@ __global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
   const __amdgpu_buffer_rsrc_t rq = rsrc_of(a.qg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
-  const Placement pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + 1, deadline, &xcd_lds, a.ctl);
+  Placement pl;
+  if constexpr (SWEEP) pl = place_block_sweep(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + 1, deadline, &xcd_lds, a.ctl);
+  else pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, a.n_local + 1, deadline, &xcd_lds, a.ctl);
   if (pl.spacer) return;
   const int bid = pl.bid;
   const bool local = pl.local;
@@ -419,6 +430,26 @@ __global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
   }
 }
 
+template <int QT>
+__global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
+  q_persistent_body<QT, false>(a);
+}
+
+// Up to 8 independent Q-GADMM solves in one launch, one per XCD: slot j = blockIdx.x & 7 runs solve j
+// on the blocks b % 8 == j, i.e. on the blocks that the single-solve launch leaves as exiting spacers.
+// batch[j] is solve j's own PersistArgs: its own message table, theta / mu / true theta, objective and
+// decision rings, ctl, trace, tstamp, xchk, tag salt, quantizer (bits, seed), rho, stop rule and
+// deadline; only the read-only inputs (A, b, yy, Minv, slots, pos) may be shared. Slots may differ in
+// n, d (within the QT class) and bits. Nothing assumes WHICH XCD a slot gets: with xcd = 2 a slot
+// verifies that its own blocks share one (xcd_verdict on its own xchk under its own xtag) before it
+// publishes with plain stores, else it publishes with sc1 stores; readers load with sc1 either way.
+template <int QT>
+__global__ void __launch_bounds__(64) chain_persistent_q_sweep_kernel(const PersistArgs* __restrict__ batch, int nb) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  q_persistent_body<QT, true>(*(const SweepArgs*)(batch + j));
+}
+
 namespace {
 
 struct QVariant {
@@ -434,6 +465,30 @@ QVariant pick_q_variant(const PersistArgs& a) {
   const size_t mon = (size_t)a.n * 8, stg = (size_t)QSTAGE * 8;
   v.shm = mon > stg ? mon : stg;
   return v;
+}
+
+// The persistent Q body takes `a` (else: the reason in gadmm_set_error, prefixed `who`). No HIP call.
+bool q_entry_ok(const PersistArgs& a, const char* who) {
+  const QVariant v = pick_q_variant(a);
+  if (!v.fn || v.shm > 65536) {
+    gadmm_set_error("%s: d=%d, n=%d not eligible (d <= 64)", who, a.d, a.n);
+    return false;
+  }
+  if (a.q_bits != 4 && a.q_bits != 8 && a.q_bits != 16) {
+    gadmm_set_error("%s: q_bits must be 4, 8 or 16, got %d", who, a.q_bits);
+    return false;
+  }
+  if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.dec_push || !a.theta || !a.mu || !a.Minv || !a.A ||
+      !a.ctl) {
+    gadmm_set_error("%s: a required buffer is null", who);
+    return false;
+  }
+  if (a.n_epochs > 0 || a.nranks != 1 || a.sys_scope || a.push || a.n_local != a.n || !a.has_monitor ||
+      a.hard_stop != 0 || a.cont) {
+    gadmm_set_error("%s: one GPU, every worker local, a static chain, one launch per solve", who);
+    return false;
+  }
+  return true;
 }
 
 }  // namespace
@@ -462,28 +517,109 @@ long gadmm_chain_persistent_q_capacity(const PersistArgs* args) {
 
 int gadmm_chain_persistent_q_launch(const PersistArgs* args, hipStream_t st) {
   const PersistArgs& a = *args;
+  if (!q_entry_ok(a, "persistent Q kernel")) return -1;
   const QVariant v = pick_q_variant(a);
-  if (!v.fn || v.shm > 65536) {
-    gadmm_set_error("persistent Q kernel: d=%d, n=%d not eligible (d <= 64)", a.d, a.n);
-    return -1;
-  }
-  if (a.q_bits != 4 && a.q_bits != 8 && a.q_bits != 16) {
-    gadmm_set_error("persistent Q kernel: q_bits must be 4, 8 or 16, got %d", a.q_bits);
-    return -1;
-  }
-  if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.dec_push || !a.theta || !a.mu || !a.Minv || !a.A ||
-      !a.ctl) {
-    gadmm_set_error("persistent Q kernel: a required buffer is null");
-    return -1;
-  }
-  if (a.n_epochs > 0 || a.nranks != 1 || a.sys_scope || a.push || a.n_local != a.n || !a.has_monitor ||
-      a.hard_stop != 0 || a.cont) {
-    gadmm_set_error("persistent Q kernel: one GPU, every worker local, a static chain, one launch per solve");
-    return -1;
-  }
   PersistArgs ka = a;
   void* kargs[] = {&ka};
   return gadmm_persist_launch({v.fn, 64, v.shm, a.n_local + 1, "persistent Q kernel", true}, &ka, kargs, st);
+}
+
+// Solves one launch of chain_persistent_q_sweep_kernel can run side by side (one per XCD).
+int gadmm_chain_persistent_q_sweep_capacity() { return 8; }
+
+// nb <= 8 independent Q-GADMM solves (one GPU each, one QT class: d <= 52 or 53..64) in ONE launch, solve j
+// on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its own ctl,
+// trace, theta, mu, true theta, message table, objective / decision rings and xchk (per-XCD L2s are not
+// coherent: two slots never write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each,
+// owned by the caller and left alone until the stream has drained; the entries go up in one async copy
+// ahead of the kernel. -1: refused before any HIP call; -2: the workgroups cannot all be resident.
+int gadmm_chain_persistent_q_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage,
+                                          PersistArgs* dev_stage, hipStream_t st) {
+  if (nb < 1 || nb > gadmm_chain_persistent_q_sweep_capacity()) {
+    gadmm_set_error("persistent Q sweep: %d solves, one launch takes 1..%d", nb,
+                    gadmm_chain_persistent_q_sweep_capacity());
+    return -1;
+  }
+  if (!batch || !host_stage || !dev_stage) {
+    gadmm_set_error("persistent Q sweep: null batch or staging buffer");
+    return -1;
+  }
+  for (int j = 1; j < nb; ++j)
+    if ((batch[j].d <= 52) != (batch[0].d <= 52)) {
+      gadmm_set_error("persistent Q sweep: solves of different register classes (d = %d and %d; d <= 52 or 53..64)",
+                      batch[0].d, batch[j].d);
+      return -1;
+    }
+  int blocks[8], max_blocks = 0, sum_blocks = 0;
+  size_t shm = 0;
+  for (int j = 0; j < nb; ++j) {
+    const PersistArgs& a = batch[j];
+    char who[48];
+    snprintf(who, sizeof(who), "persistent Q sweep: solve %d", j);
+    if (!q_entry_ok(a, who)) return -1;
+    if (!a.trace || !a.b || !a.yy) {  // (the single launch leaves these to its one caller)
+      gadmm_set_error("%s: a required buffer is null", who);
+      return -1;
+    }
+    if (!a.xchk) {
+      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
+      return -1;
+    }
+    blocks[j] = a.n_local + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i) {
+      const PersistArgs& o = batch[i];
+      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.qg == a.qg ||
+          (a.q_true && o.q_true == a.q_true) || o.objg == a.objg || o.decg == a.decg || o.dec_push == a.dec_push ||
+          o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres)) {
+        gadmm_set_error("persistent Q sweep: solves %d and %d share a buffer that both write", i, j);
+        return -1;
+      }
+    }
+    // the ranges gadmm_persist_launch checks for the single launch
+    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+      gadmm_set_error("%s: ring/lag/tag range", who);
+      return -1;
+    }
+    sum_blocks += blocks[j];
+    if (blocks[j] > max_blocks) max_blocks = blocks[j];
+    const size_t need = pick_q_variant(a).shm;
+    if (need > shm) shm = need;
+  }
+  const void* fn = batch[0].d <= 52 ? (const void*)chain_persistent_q_sweep_kernel<13>
+                                    : (const void*)chain_persistent_q_sweep_kernel<16>;
+  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
+  // its 8-strided blocks are dealt to
+  const long cap = gadmm_resident_capacity(fn, 64, shm);
+  const long cus_xcd = gadmm_cu_count() / 8;
+  if (sum_blocks > cap) {
+    gadmm_set_error("persistent Q sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
+    return -2;
+  }
+  for (int j = 0; j < nb; ++j)
+    if (blocks[j] > cus_xcd) {
+      gadmm_set_error("persistent Q sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
+      return -2;
+    }
+  int xenv = -1;
+  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
+  for (int j = 0; j < nb; ++j) {
+    PersistArgs& ka = host_stage[j];
+    ka = batch[j];
+    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
+    const int x = xenv >= 0 ? xenv : ka.xcd;
+    ka.xcd = x >= 2 ? 2 : 1;
+    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
+  const PersistArgs* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb};
+  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64), kargs, shm, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

@@ -1125,6 +1125,119 @@ def quantized_group_admm(model, rho, obj0, acc, max_iter, bits, seed=1234, **kw)
     return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, quantize=(bits, seed), **kw)
 
 
+def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float, max_iter: int, *,
+                               tols: Optional[Sequence[float]] = None, placement: Optional[Placement] = None,
+                               backend: str = "auto", name: str = "Q-GADMM", engine_opts: Optional[dict] = None,
+                               comm: Optional[Comm] = None, n_total: Optional[int] = None,
+                               local_ids: Optional[Sequence[int]] = None) -> List[RunResult]:
+    """Q-GADMM on a static chain under every ``(rho, bits, seed)`` of ``configs``: one ``RunResult`` per
+    config, in the order given, equal to ``[chain_admm(model, ..., rho, ..., quantize=(bits, seed)) for
+    ...]``. On one HIP device the solves run side by side, up to eight per kernel launch, one per XCD
+    (engine/quant_sweep.py; more configs run in groups), each to its own stop: ``tols`` gives one
+    tolerance per config (default ``tol`` for all). Each result then carries the single native Q
+    solve's fields plus ``extra['sweep'] = {width, slot, kernel, placed, wall_ms_launch}``, and its
+    ``wall_s`` is that solve's OWN time (as ``chain_admm_sweep``: the wall clock of its launch less the
+    device time between its stop decision and the last member's). ``extra['state']`` is not produced.
+    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, the exchange checker, no native
+    library, a non-linear model, not every worker local, d > 64, or a device that cannot hold the
+    group's workgroups -- it IS that loop, and every result records ``extra['sweep_fallback'] =
+    reason``. A hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``, as in ``chain_admm``."""
+    configs = [(float(r), int(b), int(s)) for r, b, s in configs]
+    opts = dict(engine_opts or {})
+    n_total = model.n_local if n_total is None else int(n_total)
+    local_ids = list(range(model.n_local)) if local_ids is None else [int(w) for w in local_ids]
+    tols = [float(tol)] * len(configs) if tols is None else [float(t) for t in tols]
+    if len(tols) != len(configs):
+        raise ValueError("tols: one per config")
+    nranks = comm.nranks if comm is not None else 1
+
+    def sequential(reason: str) -> List[RunResult]:
+        out = []
+        for (rho, bits, seed), t in zip(configs, tols):
+            r = chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
+                           backend=backend, name=name, engine_opts=engine_opts, quantize=(bits, seed))
+            r.extra["sweep_fallback"] = reason
+            out.append(r)
+        return out
+
+    if not configs:
+        return []
+    if model.device.type != "cuda":
+        return sequential("cpu tensors")
+    if backend == "torch":
+        return sequential("torch backend")
+    if nranks > 1:
+        return sequential("several ranks")
+    if getenv("GADMM_CHECK_EXCHANGE", "0") == "1":
+        return sequential("exchange checker")
+    if model.kind != "linear":
+        return sequential("not the linear closed-form model")
+    if sorted(local_ids) != list(range(n_total)):
+        return sequential("not every worker local")
+    if model.d > 64:
+        return sequential("d > 64")
+    from ..ops import native
+    if not native.available():
+        return sequential("native library unavailable")
+    from ..engine.chain_engine import ResidencyError
+    from ..engine.quant_sweep import QuantSweepEngine, quant_sweep_capacity
+    from . import quantize as Q
+
+    xcd = int(opts.get("xcd", 2))
+
+    def run_group(g_cfgs, idx):
+        t_begin = time.perf_counter()
+        g_tols = [tols[i] for i in idx]
+        key = ("qsweep", n_total, tuple(local_ids), tuple(g_cfgs), int(max_iter), xcd)
+        cache = getattr(model, "_chain_engines", None)
+        sw = cache.get(key) if cache is not None else None
+        if sw is None:
+            sw = QuantSweepEngine.build(model.X, model.y, local_ids, n_total, g_cfgs, obj0=obj0, tols=g_tols,
+                                        max_iters=max_iter, precomputed=(model.A, model.b, model.yy),
+                                        placement=placement, xcd=xcd)
+            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
+            if opts.get("cache", True):
+                if cache is None:
+                    cache = {}
+                    model._chain_engines = cache
+                cache[key] = sw
+        else:
+            sw.set_targets(obj0, g_tols)
+        runs = sw.run()
+        wall = time.perf_counter() - t_begin
+        ticks = sw.stop_ticks(runs)
+        last = max(ticks)
+        out = []
+        for j, (m, r, (rho, bits, seed)) in enumerate(zip(sw.members, runs, g_cfgs)):
+            iters, done = int(r.iters), int(r.done)
+            tr, tt = m.traces(iters)
+            own = wall - (last - ticks[j]) * 1e-8 if ticks[j] > 0 else wall
+            G = Q.granules_per_row(model.d, bits)
+            res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(done == 1),
+                            wall_s=own, time_trace=tt,
+                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
+                            com_cost=np.arange(1, iters + 1) * 0.0, bytes_sent=0, bytes_total=0, primal_res=None,
+                            extra={"backend": "native", "engine": "persistent", "kernel": sw.last_kernel, "rank": 0,
+                                   "nranks": 1, "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0,
+                                   "transport": "local", "obj_mode": m.obj_mode_name, "engine_obj": m,
+                                   "q_granules": G, "q_wire_bytes": iters * n_total * G * 16,
+                                   "placed": int(sw.last_placed[j]),
+                                   "sweep": {"width": len(g_cfgs), "slot": j, "kernel": sw.last_kernel,
+                                             "placed": int(sw.last_placed[j]), "wall_ms_launch": sw.last_wall_ms},
+                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j})
+            _quant_accounting(res, bits, seed, n_total, model.d)
+            out.append(res)
+        return out
+
+    try:
+        with roctx_range("%s sweep native-Q N=%d K=%d" % (name, n_total, len(configs))):
+            return run_in_groups(configs, quant_sweep_capacity(), run_group)
+    except ResidencyError as e:
+        return sequential("ResidencyError: %s" % e)
+    except ValueError as e:  # a shape or a device budget the sweep kernel does not take
+        return sequential("not eligible: %s" % e)
+
+
 def group_admm_closed_form(model, rho, obj0, acc, max_iter, **kw) -> RunResult:
     """``group_ADMM_closedForm`` (A1) on all local workers (single rank unless comm given)."""
     n_total = kw.pop("n_total", model.n_local)

@@ -583,15 +583,16 @@ class NativeChainEngine:
             memo[key] = int(self.lib.gadmm_chain_persistent_q_capacity(ctypes.byref(pa)))
         return self.n_local + 1 <= memo[key]
 
-    def _run_persistent_q(self, lag: int, timeout_s: float, start_iter: int, fetch_trace: bool) -> EngineRun:
-        """Q-GADMM, the whole solve in one launch of chain_persistent_q_kernel."""
-        import time as _time
+    # ---- a persistent Q solve in two halves, for launches that carry several solves (quant_sweep.py)
+    def prepare_persistent_q(self, lag: int = 4, timeout_s: float = 20.0) -> native.PersistArgs:
+        """The ``PersistArgs`` of a fresh Q-GADMM solve on the persistent Q body, without launching:
+        state must be reset by the caller. The message table is allocated and zeroed here, on the stream
+        the engine runs on NOW, so an engine that joins a sweep prepares after ``adopt_stream`` and the
+        launch must use that stream. Raises ValueError when the engine is not eligible."""
         if not self.persistent_q_eligible():
-            raise RuntimeError("persistent Q kernel not eligible for this engine/config")
-        if start_iter != 1:
-            raise ValueError("persistent Q kernel: a fresh solve only (start_iter 1)")
+            raise ValueError("persistent Q kernel not eligible for this engine/config")
         ring = lag + 4
-        pa, slots, pos, _ = self._persist_args(lag, ring, timeout_s, start_iter, 0, None, False, 0, False)
+        pa, slots, pos, _ = self._persist_args(lag, ring, timeout_s, 1, 0, None, False, 0, False)
         G = self.q_words + 1
         if getattr(self, "_qg", None) is None:
             with torch.cuda.stream(self.stream):  # zeroed once, ordered before the kernel; tags are salted per solve
@@ -599,7 +600,24 @@ class NativeChainEngine:
         pa.obj_mode = 0
         pa.qg, pa.q_true = self._qg.data_ptr(), self.theta_true.data_ptr()
         pa.q_bits, pa.q_seed = self.quant
-        self.last_kernel = "persistent-Q(b=%d,G=%d)" % (self.quant[0], G)
+        return pa
+
+    def finish_persistent_q(self, wall_ms: float, fetch: bool, what: str) -> EngineRun:
+        """The ``EngineRun`` of a persistent Q solve whose read-back (``_queue_readback``) has completed."""
+        self._tr_valid = fetch
+        self.last_timeline = self.last_timeline_slots = None
+        done, conv, nxt = self._decode_ctl(what)
+        return EngineRun(conv, done, nxt - 1, 1, wall_ms, 0, 0, 0, 0)
+
+    def _run_persistent_q(self, lag: int, timeout_s: float, start_iter: int, fetch_trace: bool) -> EngineRun:
+        """Q-GADMM, the whole solve in one launch of chain_persistent_q_kernel."""
+        import time as _time
+        if not self.persistent_q_eligible():
+            raise RuntimeError("persistent Q kernel not eligible for this engine/config")
+        if start_iter != 1:
+            raise ValueError("persistent Q kernel: a fresh solve only (start_iter 1)")
+        pa = self.prepare_persistent_q(lag, timeout_s)
+        self.last_kernel = "persistent-Q(b=%d,G=%d)" % (self.quant[0], self.q_words + 1)
         t0 = _time.perf_counter()
         rc = int(self.lib.gadmm_chain_persistent_q_launch(ctypes.byref(pa), self.stream.cuda_stream))
         if rc == -2:
@@ -607,11 +625,7 @@ class NativeChainEngine:
         native.check(rc, "chain_persistent_q_launch")
         fetch = self._queue_readback(fetch_trace)
         self.stream.synchronize()
-        self._tr_valid = fetch
-        t1 = _time.perf_counter()
-        self.last_timeline = self.last_timeline_slots = None
-        done, conv, nxt = self._decode_ctl("persistent Q kernel")
-        return EngineRun(conv, done, nxt - start_iter, 1, (t1 - t0) * 1e3, 0, 0, 0, 0)
+        return self.finish_persistent_q((_time.perf_counter() - t0) * 1e3, fetch, "persistent Q kernel")
 
     def persistent_eligible(self, fabric=None) -> bool:
         if self.plan is None or self.path is None:

@@ -312,7 +312,10 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
     one GADMM solve per rho on its engine (``gadmm_solve``); ``state_rho``: that run keeps its state for
     a checkpoint. With the preset field ``sweep='concurrent'`` the linear closed-form rho list runs
     side by side in one kernel launch (``chain_admm_sweep``) on a one-GPU session, unless the backend
-    is torch or a run must keep its state; each run's summary then names the sweep kernel and its slot."""
+    is torch or a run must keep its state; each run's summary then names the sweep kernel and its slot.
+    With ``quant_bits`` set, the same switch sends the Q-GADMM ``quant_bits x rhos`` list through
+    ``quantized_group_admm_sweep`` (same run keys and names; where that call is the sequential loop,
+    the summaries carry ``sweep_fallback``)."""
     from ..utils.timing import roctx_range
 
     cfg = prob.cfg
@@ -337,7 +340,23 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
         out["GADMM_rho%g" % rho] = attach_modelled_clock(r, prob.model, rho, sess)
     if cfg.quant_bits and cfg.model != "linear":
         raise ValueError("quant_bits: Q-GADMM runs on the linear entries (closed-form local solves)")
-    for bits in cfg.quant_bits:  # Q-GADMM next to the sweep; comm_units counts equivalent full-precision messages
+    # the sweep call decides by itself where it is the sequential loop (CPU tensors, the torch backend,
+    # several ranks, ...) and says so in every result (extra['sweep_fallback'])
+    q_concurrent = cfg.sweep == "concurrent" and cfg.model == "linear" and len(cfg.quant_bits) > 0 and len(cfg.rhos) > 0
+    if q_concurrent:  # the bits x rho list side by side, up to eight solves per launch, one per XCD
+        from ..algorithms import quantized_group_admm_sweep
+
+        q_cfgs = [(rho, int(bits), cfg.quant_seed) for bits in cfg.quant_bits for rho in cfg.rhos]
+        with roctx_range("qgadmm sweep concurrent"):
+            rs = quantized_group_admm_sweep(prob.model, q_cfgs, prob.obj0, cfg.acc, cfg.gadmm_iters,
+                                            placement=prob.placement, backend=backend, comm=sess.comm,
+                                            n_total=prob.n_total, local_ids=prob.local_ids)
+        for (rho, bits, _), r in zip(q_cfgs, rs):
+            r.algorithm = "Q-GADMM(b=%d,rho=%g)" % (bits, rho)
+            for k in ("engine_obj", "theta_true", "state"):
+                r.extra.pop(k, None)
+            out["Q-GADMM_b%d_rho%g" % (bits, rho)] = attach_modelled_clock(r, prob.model, rho, sess)
+    for bits in ([] if q_concurrent else cfg.quant_bits):  # Q-GADMM next to the sweep; comm_units counts equivalent full-precision messages
         from ..algorithms import chain_admm
 
         for rho in cfg.rhos:

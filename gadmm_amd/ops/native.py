@@ -189,6 +189,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_chain_persistent_capacity": (c_long, [ctypes.POINTER(PersistArgs)]),
         "gadmm_chain_persistent_q_launch": (c_int, [ctypes.POINTER(PersistArgs), c_void_p]),
         "gadmm_chain_persistent_q_capacity": (c_long, [ctypes.POINTER(PersistArgs)]),
+        "gadmm_chain_persistent_q_sweep_capacity": (c_int, []),
+        "gadmm_chain_persistent_q_sweep_launch": (c_int, [ctypes.POINTER(PersistArgs), c_int, c_void_p, c_void_p,
+                                                          c_void_p]),
         "gadmm_quant_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
         "gadmm_chain_persistent_logistic_capacity": (c_long, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
         "gadmm_chain_persistent_logistic_launch": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs),
