@@ -13,6 +13,9 @@ specification), in the form the kernels evaluate them:
 * chain duals are the per-worker aggregates ``mu_n = lam_n - lam_{n-1}`` (D-GADMM form);
 * D-GADMM (``dgadmm_linear``) is that recurrence over a list of chains: neighbours, roles and the
   degree's inverse follow the chain of the iteration; ``dgadmm_chains`` prescribes the chains;
+* the K4 primal residual (``chain_residual``) is a function of a run's theta history and its chains: the
+  tails' ``|th_l - th|^2 + |th - th_r|^2`` per (iteration, worker), what the chain kernels emit beside
+  theta, the duals and the objective; ``Reference`` holds it for every chain case;
 * Q-GADMM (``qgadmm_linear``) is ``gadmm_linear`` over a static chain whose theta table holds the public
   models th_hat; its quantizer line restates gadmm_amd/algorithms/quantize.py and is held against it bit
   for bit, the run against the torch path, by tests/test_hp_reference_cpu.py;
@@ -202,6 +205,69 @@ def dgadmm_linear(X, y, rho, K, chains, dtype=LD, mutant=None):
     Returns ``(theta (K, N, d), mu (N, d) after iteration K, objectives (K,))``."""
     th, mus, obj = _dgadmm_run(np.asarray(X), y, rho, K, chains, dtype, mutant)
     return th, mus[-1], obj
+
+
+RESIDUAL_MUTANTS = ("one-edge", "stale-head", "pre-update", "lanes-64", "old-chain", "by-position")
+
+
+def _chain_at(tabs, it):
+    """The table of the chain in force at iteration ``it`` (1-based) of ``chain_tables`` output."""
+    e = 0
+    while e + 1 < len(tabs) and tabs[e + 1][0] <= it:
+        e += 1
+    return tabs[e][1]
+
+
+def tail_mask(chains, K, N):
+    """(K, N) bool: worker w is a tail (odd 0-based chain position) of the chain in force at iteration
+    k + 1. ``chains`` None: the identity chain."""
+    tabs = chain_tables([(1, list(range(N)))] if chains is None else chains)
+    mask = np.zeros((K, N), dtype=bool)
+    for it in range(1, K + 1):
+        for w, (p, _, _) in _chain_at(tabs, it).items():
+            mask[it - 1, w] = p % 2 == 1
+    return mask
+
+
+def chain_residual(theta_hist, chains=None, dtype=LD, mutant=None):
+    """The K4 primal residual the chain kernels emit beside theta, the duals and the objective, from a
+    theta history (K, N, d): entry ``[it - 1, w]`` of a worker w that is a TAIL (odd 0-based position) of
+    the chain in force at iteration ``it`` is
+
+        sum((th[it, left] - th[it, w])^2) + sum((th[it, w] - th[it, right])^2)
+
+    over the edges it has (every chain edge has exactly one tail end), all thetas those after iteration
+    ``it``; a head's entry is 0. Indexed by worker id; ``chains`` as ``dgadmm_linear`` takes them (None:
+    the identity chain). Plain NumPy in ``dtype``.
+    ``mutant`` names a mistake a kernel's residual branch could make (tests/test_hp_reference_cpu.py
+    measures how far each sits from the reference): ``"one-edge"`` drops the right edge; ``"stale-head"``
+    reads the heads' theta of iteration ``it - 1`` (0 before the first); ``"pre-update"`` the tail's own
+    theta of ``it - 1``; ``"lanes-64"`` sums the coordinates < 64 only; ``"old-chain"`` takes the chain
+    of ``it - 1``; ``"by-position"`` writes a tail's entry at its chain position instead of its id."""
+    assert mutant is None or mutant in RESIDUAL_MUTANTS
+    th = np.asarray(theta_hist, dtype=dtype)
+    K, N, d = th.shape
+    tabs = chain_tables([(1, list(range(N)))] if chains is None else chains)
+    assert len(tabs[0][1]) == N and tabs[0][0] == 1
+    out = np.zeros((K, N), dtype=dtype)
+    start = np.zeros((N, d), dtype=dtype)
+    cols = slice(0, 64) if mutant == "lanes-64" else slice(None)
+    for it in range(1, K + 1):
+        tab = _chain_at(tabs, max(it - 1, 1) if mutant == "old-chain" else it)
+        cur = th[it - 1]
+        prev = th[it - 2] if it > 1 else start
+        nbr = prev if mutant == "stale-head" else cur
+        for w, (p, l, r) in tab.items():
+            if p % 2 == 0:
+                continue
+            own = prev[w] if mutant == "pre-update" else cur[w]
+            tot = np.zeros((), dtype=dtype)
+            if l is not None:
+                tot = tot + np.sum(((nbr[l] - own)[cols]) ** 2)
+            if r is not None and mutant != "one-edge":
+                tot = tot + np.sum(((own - nbr[r])[cols]) ** 2)
+            out[it - 1, p if mutant == "by-position" else w] = tot
+    return out
 
 
 def star_admm_linear(X, y, rho, K, dtype=LD):
@@ -427,6 +493,14 @@ def noise_level(ref_ld, ref_f64, scale):
     return float(np.max(diff)) if diff.size else 0.0
 
 
+def _own_or_largest(ref):
+    """The scale of a trace that decays over many orders: each entry's own magnitude where that exceeds
+    1e-20 of the trace's largest, the largest elsewhere (as ``QReference.res_scale``)."""
+    mag = np.abs(np.asarray(ref, dtype=LD))
+    top = np.max(mag) if mag.size else np.asarray(0.0, dtype=LD)
+    return np.where(mag > 1e-20 * top, mag, top)
+
+
 def bound(e64, d, m_logistic=0, truncation=0.0, n=0):
     """``FACTOR * max(e64, max(d, m_logistic, n, 16) * 2^-53, truncation)``: the float64 noise of the
     recurrence, with the standard dot-product bound as the floor for runs that happen to round luckily.
@@ -450,9 +524,17 @@ class Reference:
 
     ``theta`` (K, N, d), ``dual`` (N, d), ``obj`` (K,) in long double; ``rho``; ``scale_theta`` =
     max |theta| over the run; ``b_theta`` / ``b_dual`` / ``b_obj``: the bounds of the three relative
-    errors ``err_theta`` / ``err_dual`` / ``err_obj`` measure."""
+    errors ``err_theta`` / ``err_dual`` / ``err_obj`` measure.
 
-    def __init__(self, ld, f64, rho, d, m_logistic=0, chord=0.0):
+    Chain references (``residual=True``; ``f64[0]`` is then the float64 theta history (K, N, d)) also hold
+    the K4 primal residual of the long-double history over ``chains`` (``chain_residual``): ``res_w``
+    (K, N) per worker, ``res`` (K,) its row sums, ``tails`` (K, N) which entries are tails'. Their noise
+    ``e_res_w`` / ``e_res`` is the distance of the same function of the float64 history, in float64; each
+    entry is taken over its own reference value where that exceeds 1e-20 of the trace's largest, over
+    the largest below that, and of ``res_w`` the tails' entries only (a head's is exactly 0). Bounds
+    ``b_res_w`` / ``b_res`` and errors ``err_res_w`` / ``err_res`` as for the other quantities."""
+
+    def __init__(self, ld, f64, rho, d, m_logistic=0, chord=0.0, chains=None, residual=True):
         self.theta, self.dual, self.obj = ld[0], ld[1], ld[2]
         self.extra = ld[3:]
         self.rho = float(rho)
@@ -464,6 +546,34 @@ class Reference:
         self.b_theta = bound(self.e_theta, d, m_logistic, self.truncation)
         self.b_dual = bound(self.e_dual, d, m_logistic, self.truncation)
         self.b_obj = bound(self.e_obj, d, m_logistic, self.truncation)
+        if residual:
+            K, N = self.theta.shape[:2]
+            self.chains = chains
+            self.theta64 = f64[0]  # the float64 history: what the residual's power is measured on
+            self.tails = tail_mask(chains, K, N)
+            self.res_w = chain_residual(self.theta, chains, LD)
+            self.res = self.res_w.sum(axis=1)
+            res64 = chain_residual(np.asarray(f64[0], dtype=np.float64), chains, np.float64)
+            self.res_w_scale, self.res_scale = _own_or_largest(self.res_w), _own_or_largest(self.res)
+            self.e_res_w = self._tails_level(self.res_w, res64)
+            self.e_res = noise_level(self.res, res64.sum(axis=1), self.res_scale)
+            self.b_res_w, self.b_res = bound(self.e_res_w, d, m_logistic), bound(self.e_res, d, m_logistic)
+            _freeze(self.tails, self.res_w, self.res, self.res_w_scale, self.res_scale)
+
+    def _tails_level(self, ref, rows):
+        k = len(rows)
+        diff = np.abs(ref[:k] - np.asarray(rows, dtype=LD)) / self.res_w_scale[:k]
+        diff = diff[self.tails[:k]]
+        return float(np.max(diff)) if diff.size else 0.0
+
+    def err_res_w(self, rows):
+        """``rows`` (k, N), the per-worker residual of iterations 1..k, against the reference's first k
+        rows: the tails' entries only."""
+        return self._tails_level(self.res_w, rows)
+
+    def err_res(self, res):
+        res = np.asarray(res)
+        return noise_level(self.res[:len(res)], res, self.res_scale[:len(res)])
 
     def err_theta(self, theta, k=None):
         """``theta`` (N, d) against the reference after iteration ``k`` (1-based; None: the last)."""
@@ -518,13 +628,37 @@ def linear_case(n, m, d, K=K_ITERS):
     return _cached(("lin", n, m, d, K), build)
 
 
+RESIDUAL_PATHS = {(4, 40, 33): (3, 2, 1, 0), (5, 40, 33): (2, 0, 4, 1, 3)}  # the permuted static chains
+
+
+def linear_path_case(n, m, d, path, K=K_ITERS):
+    """``(X, y, rho, Reference)`` of GADMM on the static chain ``path`` (position -> worker) over the
+    data of ``linear_case``: ``gadmm_linear`` on the shards in chain order (``X[path]``, ``y[path]``), its
+    theta history and duals mapped back to worker ids, and the K4 residual over that chain."""
+    path = [int(w) for w in path]
+    assert sorted(path) == list(range(n))
+
+    def build():
+        X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
+        _freeze(X, y)
+
+        def run(dtype):
+            th_p, mu_p, obj = gadmm_linear(X[path], y[path], rho, K, dtype)
+            th, mu = np.zeros_like(th_p), np.zeros_like(mu_p)
+            th[:, path] = th_p
+            mu[path] = mu_p
+            return th, mu, obj
+        return X, y, rho, Reference(run(LD), run(np.float64), rho, d, chains=[(1, path)])
+    return _cached(("lin-path", n, m, d, tuple(path), K), build)
+
+
 def star_case(n, m, d, K=K_ITERS):
     """As ``linear_case`` for ``star_admm_linear`` (the same data)."""
     def build():
         X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
         _freeze(X, y)
         return X, y, rho, Reference(star_admm_linear(X, y, rho, K, LD), star_admm_linear(X, y, rho, K, np.float64),
-                                    rho, d)
+                                    rho, d, residual=False)
     return _cached(("star", n, m, d, K), build)
 
 
@@ -1350,7 +1484,8 @@ def dgadmm_case(n, m, d, coherence, K=K_ITERS, chains=None):
     def build():
         X, y, rho, th, mus, obj = _dgadmm_history(n, m, d, chains, K, LD)
         _, _, _, th64, mus64, obj64 = _dgadmm_history(n, m, d, chains, K, np.float64)
-        return X, y, rho, chains, Reference((th[:K], mus[K - 1], obj[:K]), (th64[:K], mus64[K - 1], obj64[:K]), rho, d)
+        return X, y, rho, chains, Reference((th[:K], mus[K - 1], obj[:K]), (th64[:K], mus64[K - 1], obj64[:K]), rho, d,
+                                            chains=chains)
     return _cached(("dgadmm", n, m, d, _chains_key(chains), K), build)
 
 
@@ -1544,11 +1679,14 @@ class QReference(Reference):
     ``obj``) plus ``hat`` (N, d) the public models after K, ``codes`` (K, N, d), ``R`` (K, N),
     ``res`` (K,) the K4 residual, ``margin`` the run's smallest flip margin, ``seed``, ``path``, and
     the bounds ``b_hat`` / ``b_R`` (errors over ``scale_theta``) and ``b_res`` (each entry over its own
-    value where that exceeds 1e-20 of the trace's largest, over the largest below that)."""
+    value where that exceeds 1e-20 of the trace's largest, over the largest below that). Its residual is
+    the recurrence's own, on the PUBLIC models: ``Reference``'s (``res_w`` and the rest, a function of the
+    true theta history) is not built here, and ``res`` / ``e_res`` / ``b_res`` / ``err_res`` are this
+    class's."""
 
     def __init__(self, ld, f64, rho, d, seed, path):
         th, hats, mus, obj, codes, Rs, res, margins = ld
-        super().__init__((th, mus[-1], obj), (f64[0], f64[2][-1], f64[3]), rho, d)
+        super().__init__((th, mus[-1], obj), (f64[0], f64[2][-1], f64[3]), rho, d, residual=False)
         self.seed, self.path = seed, path
         self.hat, self.codes, self.R, self.res, self.margin = hats[-1], codes, Rs, res, float(margins[-1])
         self.codes_agree = bool(np.array_equal(codes, f64[4]))

@@ -20,6 +20,10 @@ tests/test_hp_reference_cpu.py shows, on these very cases, that ignoring a re-ch
 head's pending dual with the new chain, or taking the old degree's inverse lands >= 1000 bounds away.
 A persistent kernel stops ``last - K <= 16`` iterations after the cap and re-chains at none of them:
 the reference runs to ``last`` over chains that end at K.
+These solves run with the K4 primal residual on (the algorithm's default): the K sums the solve returns
+and the per-worker rows of the engine are held to hp_reference.chain_residual over the case's chains -- a
+worker's row is non-zero exactly in the iterations in which it is a tail, and is indexed by worker id,
+not by chain position (profiles/residual_classes/README.md).
 Each test prints err / bound; profiles/dgadmm_classes/README.md records the measured table.
 
 Each parameter list names the dispatch condition that puts its shape in its class: if a threshold
@@ -37,7 +41,7 @@ import pytest
 import torch
 
 import hp_reference as H
-from test_gpu_dispatch_classes import _dev, _host, _report
+from test_gpu_dispatch_classes import _dev, _host, _report, _residual_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -93,8 +97,12 @@ def solve(n, m, d, coh, engine, **opts):
     assert chains2 == chains and rho2 == rho and np.array_equal(X2, X)
     th, du = _host(theta), _host(mu)
     assert np.all(np.isfinite(th)) and np.all(np.isfinite(du)) and np.all(np.isfinite(a.obj))
+    # the K4 primal residual, on by the algorithm's default: the K sums the solve returns over the case's
+    # chains and the per-worker rows behind them (a worker's row is non-zero exactly while it is a tail)
+    assert a.primal_res is not None and len(a.primal_res) == K and np.all(np.isfinite(a.primal_res))
     return {"objective": ref.err_obj(a.obj) / ref.b_obj, "theta": ref.err_theta(th, last) / ref.b_theta,
-            "dual": ref.err_dual(du) / ref.b_dual}, eng
+            "dual": ref.err_dual(du) / ref.b_dual, "residual": ref.err_res(a.primal_res) / ref.b_res,
+            "residual rows": _residual_rows(eng, ref)}, eng
 
 
 def _lds_thresholds():

@@ -16,6 +16,10 @@ different summation order, FMA contraction and the ~2 ulp of the fast sigmoid; a
 stale-LDS mistake moves theta by ~1/d relative, eleven orders of magnitude above the bound.
 Each test prints err / bound; profiles/dispatch_classes/README.md records the measured table.
 
+The "K4 primal residual" section runs the chain classes once more with ``residual=True`` (the setting of
+every solve a user runs) and holds the K residual sums and the per-worker rows behind them to
+hp_reference.chain_residual under the same rule (profiles/residual_classes/README.md).
+
 Each parameter list names the dispatch condition that puts its d in its class: if a threshold moves,
 the list next to it is the one to revisit.
 
@@ -67,12 +71,12 @@ def _report(tag, ratios):
 
 # ------------------------------------------------------------------------------------------------
 # Linear chain
-def _linear_engine(n, m, d, **kw):
+def _linear_engine(n, m, d, residual=False, **kw):
     from gadmm_amd.engine.chain_engine import NativeChainEngine
     from gadmm_amd.parallel.topology import Placement
     X, y, rho, _ = H.linear_case(n, m, d)
     eng = NativeChainEngine(_dev(X), _dev(y), list(range(n)), n, "linear", rho=rho, obj0=0.0, tol=0.0, max_iter=K,
-                            obj_mode="exact", block=BLOCK, **kw)
+                            obj_mode="exact", block=BLOCK, residual=residual, **kw)
     eng.set_path(list(range(n)), Placement.contiguous(n, 1), 0)
     eng.reset()
     return eng
@@ -89,26 +93,55 @@ def _state_ratios(eng, ref, last, prefix=""):
     return {prefix + "theta": ref.err_theta(th, last) / ref.b_theta, prefix + "dual": ref.err_dual(mu) / ref.b_dual}
 
 
-def run_linear_graph(n, m, d, use_graph=True):
+def _residual_rows(eng, ref):
+    """err / bound of the per-worker K4 rows of iterations 1..K (``eng.rres``, (K, n) by worker id) against
+    ``ref`` (which may run past K: a persistent kernel's; ``max_iter = K``, so no row past K exists).
+    Every head's entry is exactly 0.0 -- nothing writes it, ``reset()`` zeroed it -- and every tail's is
+    finite and positive."""
+    n = eng.n_total
+    eng.stream.synchronize()
+    assert eng.rres is not None and eng.rres.numel() >= K * n
+    rows = _host(eng.rres[:K * n].view(K, n))
+    tails = ref.tails[:K]
+    assert np.all(rows[~tails] == 0.0), ("a head's row is not 0", rows)
+    assert np.all(np.isfinite(rows[tails])) and np.all(rows[tails] > 0), rows
+    return ref.err_res_w(rows) / ref.b_res_w
+
+
+def _residual_ratios(eng, ref):
+    """The K4 primal residual of an engine built with ``residual=True``: the K sums ``primal_residual``
+    returns and the per-worker rows behind them (``_residual_rows``)."""
+    rows = _residual_rows(eng, ref)
+    return {"residual": ref.err_res(eng.primal_residual(K)) / ref.b_res, "residual rows": rows}
+
+
+def run_linear_graph(n, m, d, use_graph=True, residual=False):
     """The phase kernels (chain_small.hip chain_phase_linear<NC>, chain_big.hip), replayed as a graph
-    or launched eagerly: K iterations, then theta, mu and the K objectives."""
+    or launched eagerly: K iterations, then theta, mu and the K objectives (``residual``: and the K4
+    primal residual, ``_residual_ratios``)."""
     ref = H.linear_case(n, m, d)[3]
-    eng = _linear_engine(n, m, d)
+    eng = _linear_engine(n, m, d, residual=residual)
     r = eng.run(stop_iter=K, use_graph=use_graph)
     assert r.iters == K and eng.ctl_state()["iter"] == K + 1, (r.iters, r.done, eng.ctl_state())
     # (a block shorter than the captured one is enqueued kernel by kernel: BLOCK divides K, none is)
     assert r.replays == K // BLOCK and (eng.graph_ok() or not use_graph) and eng.obj_mode_name == "exact"
     out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
     out.update(_state_ratios(eng, ref, K))
+    if residual:
+        out.update(_residual_ratios(eng, ref))
     eng.close()
     return out
 
 
-def run_linear_persistent(n, m, d, family):
+def run_linear_persistent(n, m, d, family, residual=False, eng=None, case=None):
     """One persistent launch (``family``: "per-worker" or "blocked(", chosen by the environment the
     caller set). The kernel learns the cap's stop decision ``lag`` iterations late and stops after
-    iteration ctl.iter - 1: theta and mu are compared with the reference run that far."""
-    eng = _linear_engine(n, m, d)
+    iteration ctl.iter - 1: theta and mu are compared with the reference run that far. ``eng``: an
+    engine of the caller's (it stays open) in place of a fresh one; ``case``: ``last -> Reference`` of
+    what that engine solves, in place of ``linear_case``."""
+    own = eng is None
+    if own:
+        eng = _linear_engine(n, m, d, residual=residual)
     assert eng.persistent_eligible()
     if family == "blocked(":
         assert eng.blocked_plan() is not None
@@ -116,11 +149,14 @@ def run_linear_persistent(n, m, d, family):
     assert eng.last_kernel.startswith(family), eng.last_kernel
     last = eng.ctl_state()["iter"] - 1
     assert r.iters == K and K <= last <= K + 16, (r.iters, r.done, last)
-    ref = H.linear_case(n, m, d, last)[3]
+    ref = H.linear_case(n, m, d, last)[3] if case is None else case(last)
     out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
     out.update(_state_ratios(eng, ref, last))
+    if residual:
+        out.update(_residual_ratios(eng, ref))
     kern = eng.last_kernel
-    eng.close()
+    if own:
+        eng.close()
     return out, kern
 
 
@@ -254,29 +290,31 @@ def test_dgadmm_per_worker_dynamic(n, m, d, monkeypatch):
     assert any(a_[1] != b_[1] for a_, b_ in zip(chains, chains[1:]))
     ref = H.dgadmm_case(n, m, d, 3, last, chains=chains)[4]
     out = {"objective": ref.err_obj(a.obj) / ref.b_obj, "theta": ref.err_theta(_host(theta), last) / ref.b_theta,
-           "dual": ref.err_dual(_host(mu)) / ref.b_dual,
+           "dual": ref.err_dual(_host(mu)) / ref.b_dual, "residual": ref.err_res(a.primal_res) / ref.b_res,
            "oracle objective": ref.err_obj(np.asarray(o.obj)) / ref.b_obj,
            "oracle theta": ref.err_theta(o.theta, last) / ref.b_theta, "oracle dual": ref.err_dual(o.dual) / ref.b_dual}
+    out["residual rows"] = _residual_rows(eng, ref)
     eng.close()
     _report("D-GADMM per-worker dynamic %s" % ((n, m, d),), out)
 
 
 # ------------------------------------------------------------------------------------------------
 # Logistic, inner gradient descent: max_inner = 6, inner_tol = 0 (every local solve takes 6 steps)
-def _logistic_engine(n, m, d, inner_tol=0.0):
+def _logistic_engine(n, m, d, inner_tol=0.0, residual=False):
     from gadmm_amd.engine.chain_engine import NativeChainEngine
     from gadmm_amd.parallel.topology import Placement
     X, y, rho, lam, step, _ = H.logistic_case(n, m, d, inner_tol=inner_tol)
     eng = NativeChainEngine(_dev(X), _dev(y), list(range(n)), n, "logistic", rho=rho, obj0=0.0, tol=0.0, max_iter=K,
-                            lam=lam, step=step, max_inner=H.MAX_INNER, inner_tol=inner_tol, block=BLOCK)
+                            lam=lam, step=step, max_inner=H.MAX_INNER, inner_tol=inner_tol, block=BLOCK,
+                            residual=residual)
     eng.set_path(list(range(n)), Placement.contiguous(n, 1), 0)
     eng.reset()
     return eng
 
 
-def run_logistic_graph(n, m, d, inner_tol=0.0):
+def run_logistic_graph(n, m, d, inner_tol=0.0, residual=False):
     ref = H.logistic_case(n, m, d, inner_tol=inner_tol)[5]
-    eng = _logistic_engine(n, m, d, inner_tol)
+    eng = _logistic_engine(n, m, d, inner_tol, residual=residual)
     r = eng.run(stop_iter=K)
     assert r.iters == K and eng.graph_ok() and eng.ctl_state()["iter"] == K + 1, (r.iters, r.done)
     assert r.replays == K // BLOCK
@@ -284,12 +322,14 @@ def run_logistic_graph(n, m, d, inner_tol=0.0):
     assert np.array_equal(inner, ref.extra[0][K - 1]), (inner, ref.extra[0][K - 1])
     out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
     out.update(_state_ratios(eng, ref, K))
+    if residual:
+        out.update(_residual_ratios(eng, ref))
     eng.close()
     return out
 
 
-def run_logistic_persistent(n, m, d):
-    eng = _logistic_engine(n, m, d)
+def run_logistic_persistent(n, m, d, residual=False):
+    eng = _logistic_engine(n, m, d, residual=residual)
     assert eng.persistent_eligible()
     r = eng.run_persistent()
     assert eng.last_kernel == "per-worker-logistic", eng.last_kernel
@@ -299,6 +339,8 @@ def run_logistic_persistent(n, m, d):
     assert np.all(_host(eng.inner_iters)[:n] == H.MAX_INNER)
     out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj}
     out.update(_state_ratios(eng, ref, last))
+    if residual:
+        out.update(_residual_ratios(eng, ref))
     eng.close()
     return out
 
@@ -353,6 +395,114 @@ LOGISTIC_PERSISTENT = [
 def test_logistic_persistent_kernel(n, m, d, zrec, monkeypatch):
     monkeypatch.setenv("GADMM_LOGISTIC_ZREC", zrec)
     _report("logistic persistent zrec=%s %s" % (zrec, (n, m, d)), run_logistic_persistent(n, m, d))
+
+
+# ------------------------------------------------------------------------------------------------
+# K4 primal residual (residual=True, what every solve a user runs has on): each tail writes
+# |th_l - th|^2 + |th - th_r|^2 of iteration it into rres[(it - 1) n + worker], a hand-written branch of
+# its own at every kernel family (tail mask, reduction, row index, `it - 1 < max_iter` guard). The
+# same runs as above with the branch on: the K sums and the per-worker rows against
+# hp_reference.chain_residual of the long-double theta history, under the bound rule of this file with
+# each entry over its own reference value; heads' rows exactly 0. The objective, theta and the duals
+# stay in the report: a residual branch that disturbs the iterates (the scratch buffer it shares with
+# the objective's block sum in chain_small.hip) fails there. tests/test_hp_reference_cpu.py shows that a
+# dropped edge, a stale theta, a 64-lane sum or a row indexed by chain position lands >= 100 bounds away.
+@pytest.mark.parametrize("n,m,d", LINEAR_GRAPH)
+def test_residual_linear_graph(n, m, d):
+    _report("K4 linear graph %s" % ((n, m, d),), run_linear_graph(n, m, d, residual=True))
+
+
+def test_residual_linear_eager_phases():
+    _report("K4 linear eager (3, 80, 65)", run_linear_graph(3, 80, 65, use_graph=False, residual=True))
+
+
+@pytest.mark.parametrize("n,m,d", LINEAR_PER_WORKER)
+def test_residual_linear_per_worker_persistent(n, m, d, monkeypatch):
+    """REG QT = 13 / 16, and the LDS kernel NC = 2, whose `lane + 64 c < d` mask has a partial second
+    chunk at d = 65 and a full one at 128."""
+    monkeypatch.setenv("GADMM_BLOCKED", "0")
+    out, kern = run_linear_persistent(n, m, d, "per-worker", residual=True)
+    assert kern == "per-worker"
+    _report("K4 linear per-worker %s" % ((n, m, d),), out)
+
+
+@pytest.mark.parametrize("n,m,d,pw", LINEAR_BLOCKED)
+def test_residual_linear_blocked_persistent(n, m, d, pw, monkeypatch):
+    monkeypatch.delenv("GADMM_BLOCKED", raising=False)
+    if pw != 1:
+        monkeypatch.setenv("GADMM_BLOCK_PW", str(pw))
+    out, kern = run_linear_persistent(n, m, d, "blocked(", residual=True)
+    assert ("pw=%d" % pw) in kern, kern
+    _report("K4 linear blocked pw=%d %s" % (pw, (n, m, d)), out)
+
+
+@pytest.mark.parametrize("pw", [1, 2])
+def test_residual_blocked_several_owned_positions(pw, monkeypatch):
+    """(13, 20, 8) with three owned positions per workgroup (GADMM_BLOCK_L=3): five worker workgroups
+    and two objective workgroups. A workgroup also computes the halo positions around its own; their
+    tails' residuals are computed from values that are wrong after k iterations and must not reach
+    the owner's row."""
+    n, m, d = 13, 20, 8
+    monkeypatch.delenv("GADMM_BLOCKED", raising=False)
+    monkeypatch.delenv("GADMM_BLOCK_K", raising=False)
+    monkeypatch.setenv("GADMM_BLOCK_L", "3")
+    monkeypatch.setenv("GADMM_BLOCK_PW", str(pw))
+    eng = _linear_engine(n, m, d, residual=True)
+    plan = eng.blocked_plan()
+    assert plan is not None and plan[1] == 3 and plan[2] == 5 and plan[3] == pw, plan
+    out, kern = run_linear_persistent(n, m, d, "blocked(", residual=True, eng=eng)
+    eng.close()
+    assert ("pw=%d" % pw) in kern and "L=3" in kern, kern
+    _report("K4 linear blocked L=3 pw=%d %s" % (pw, (n, m, d)), out)
+
+
+# a permuted static chain, and a second solve on the same engine: worker id != chain position, and every
+# head of the first solve is a tail of the second (its row, 0 after the first solve, must be written)
+# and the other way round (its row, non-zero after the first solve, must read exactly 0).
+RESIDUAL_PATHS = [((4, 40, 33), (3, 2, 1, 0)), ((5, 40, 33), (2, 0, 4, 1, 3))]
+assert dict(RESIDUAL_PATHS) == H.RESIDUAL_PATHS
+
+
+@pytest.mark.parametrize("family", ["per-worker", "blocked("])
+@pytest.mark.parametrize("shape,path", RESIDUAL_PATHS)
+def test_residual_permuted_chain_second_solve(shape, path, family, monkeypatch):
+    from gadmm_amd.parallel.topology import Placement
+    n, m, d = shape
+    if family == "per-worker":
+        monkeypatch.setenv("GADMM_BLOCKED", "0")
+    else:
+        monkeypatch.delenv("GADMM_BLOCKED", raising=False)
+    eng = _linear_engine(n, m, d, residual=True)
+    out1, kern1 = run_linear_persistent(n, m, d, family, residual=True, eng=eng)
+    first = H.linear_case(n, m, d)[3]
+    eng.set_path(list(path), Placement.contiguous(n, 1), 0)
+    eng.reset()
+    out2, kern2 = run_linear_persistent(n, m, d, family, residual=True, eng=eng,
+                                        case=lambda last: H.linear_path_case(n, m, d, path, last)[3])
+    eng.close()
+    second = H.linear_path_case(n, m, d, path)[3]
+    assert np.any(first.tails[0] & ~second.tails[0]) and np.any(second.tails[0] & ~first.tails[0])
+    if path == (3, 2, 1, 0):
+        assert np.array_equal(second.tails[0], ~first.tails[0])  # every role flips
+    _report("K4 linear %s identity chain %s" % (kern1, shape), out1)
+    _report("K4 linear %s chain %s, second solve %s" % (kern2, path, shape), out2)
+
+
+@pytest.mark.parametrize("n,m,d", LOGISTIC_GRAPH)
+def test_residual_logistic_graph(n, m, d):
+    _report("K4 logistic graph %s" % ((n, m, d),), run_logistic_graph(n, m, d, residual=True))
+
+
+def test_residual_logistic_live_stop_rule():
+    (n, m, d), tol = H.LIVE_STOP
+    _report("K4 logistic graph live stop %s" % ((n, m, d),), run_logistic_graph(n, m, d, inner_tol=tol, residual=True))
+
+
+@pytest.mark.parametrize("zrec", ["0", "1"])
+@pytest.mark.parametrize("n,m,d", LOGISTIC_PERSISTENT)
+def test_residual_logistic_persistent_kernel(n, m, d, zrec, monkeypatch):
+    monkeypatch.setenv("GADMM_LOGISTIC_ZREC", zrec)
+    _report("K4 logistic persistent zrec=%s %s" % (zrec, (n, m, d)), run_logistic_persistent(n, m, d, residual=True))
 
 
 # ------------------------------------------------------------------------------------------------

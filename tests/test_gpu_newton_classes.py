@@ -20,6 +20,8 @@ previous iterate, refreshes are lagged or urgent), hence the same bound. Every t
 kernel ran, ctl inner_fail == 0, 1 <= inner_iters < 50 and, at c = 0, each worker's step count of its
 last solve within +-1 of the float64 reference's (a stop test can tie).
 Each test prints err / bound; profiles/newton_classes/README.md records the measured table.
+The "K4 primal residual" section runs every kernel once more with ``residual=True`` at chord 0 and holds
+the residual sums and per-worker rows to hp_reference.chain_residual (profiles/residual_classes/README.md).
 
 Run with: pytest -m gpu tests/test_gpu_newton_classes.py -s
 """
@@ -28,6 +30,7 @@ import pytest
 import torch
 
 import hp_reference as H
+from test_gpu_dispatch_classes import _residual_ratios
 
 pytestmark = pytest.mark.gpu
 
@@ -66,14 +69,15 @@ def _report(tag, ratios):
     assert not bad, (tag, bad)
 
 
-def _newton_engine(n, m, d, chord):
+def _newton_engine(n, m, d, chord, residual=False):
     """As test_gpu_dispatch_classes._logistic_engine, with exact local solves. ``chord`` None: the
     engine's defaults, 0.02 for the phase kernel and 0.3 for the persistent ones."""
     from gadmm_amd.engine.chain_engine import NativeChainEngine
     from gadmm_amd.parallel.topology import Placement
     ref = H.newton_case(n, m, d)
     eng = NativeChainEngine(_dev(ref.X), _dev(ref.y), list(range(n)), n, "logistic", rho=ref.rho, obj0=0.0, tol=0.0,
-                            max_iter=K, lam=ref.lam, local_solver="newton", chord=chord, block=BLOCK)
+                            max_iter=K, lam=ref.lam, local_solver="newton", chord=chord, block=BLOCK,
+                            residual=residual)
     eng.set_path(list(range(n)), Placement.contiguous(n, 1), 0)
     eng.reset()
     return eng
@@ -113,32 +117,36 @@ def _check_inner(eng, ref, last, tag, bg=None):
     return inner
 
 
-def run_graph(n, m, d, chord, use_graph=True, eng=None):
-    """The phase kernel, replayed as a graph or launched eagerly: K iterations."""
+def run_graph(n, m, d, chord, use_graph=True, eng=None, residual=False):
+    """The phase kernel, replayed as a graph or launched eagerly: K iterations. ``residual``: the engine
+    also emits the K4 primal residual, and its ratios join the returned ones."""
     c = CHORD_GRAPH if chord is None else chord
     ref = H.newton_case(n, m, d, K, c)
     own = eng is None
     if own:
-        eng = _newton_engine(n, m, d, chord)
+        eng = _newton_engine(n, m, d, chord, residual=residual)
     assert eng.chord == c
     r = eng.run(stop_iter=K, use_graph=use_graph)
     assert r.iters == K and eng.ctl_state()["iter"] == K + 1, (r.iters, r.done, eng.ctl_state())
     assert r.replays == K // BLOCK and (eng.graph_ok() or not use_graph)
     _check_inner(eng, ref, K, "newton graph c=%g %s" % (c, (n, m, d)))
     st = _state(eng)
+    out = _ratios(st, ref, K)
+    if residual:
+        out.update(_residual_ratios(eng, ref))  # sums and per-worker rows; heads exactly 0
     if own:
         eng.close()
-    return _ratios(st, ref, K), st
+    return out, st
 
 
-def run_persistent(n, m, d, chord, kernel, eng=None, bg=None):
+def run_persistent(n, m, d, chord, kernel, eng=None, bg=None, residual=False):
     """One persistent launch; ``kernel``: "one-wave" or "pipeline", chosen by the environment the caller
     set. The kernel learns the cap's stop decision ``lag`` iterations late and stops after iteration
     ctl.iter - 1: theta and mu are compared with the reference run that far."""
     c = CHORD_PERSISTENT if chord is None else chord
     own = eng is None
     if own:
-        eng = _newton_engine(n, m, d, chord)
+        eng = _newton_engine(n, m, d, chord, residual=residual)
     assert eng.chord_persistent == c and eng.persistent_eligible()
     r = eng.run_persistent()
     assert eng.last_kernel == "per-worker-newton(%s)" % kernel, eng.last_kernel
@@ -147,9 +155,12 @@ def run_persistent(n, m, d, chord, kernel, eng=None, bg=None):
     ref = H.newton_case(n, m, d, last, c)
     _check_inner(eng, ref, last, "newton %s c=%g %s" % (kernel, c, (n, m, d)), BG_STEPS[kernel] if bg is None else bg)
     st = _state(eng)
+    out = _ratios(st, ref, last)
+    if residual:
+        out.update(_residual_ratios(eng, ref))  # sums and per-worker rows; heads exactly 0
     if own:
         eng.close()
-    return _ratios(st, ref, last), st, last
+    return out, st, last
 
 
 # ------------------------------------------------------------------------------------------------
@@ -219,6 +230,25 @@ def test_newton_persistent_kernel(n, m, d, rec, chord, monkeypatch):
     monkeypatch.setenv("GADMM_NEWTON_REC", rec)
     out, _, last = run_persistent(n, m, d, chord, KERNEL_OF_REC[rec])
     _report("newton %s chord=%s %s (stopped after %d)" % (KERNEL_OF_REC[rec], chord, (n, m, d), last), out)
+
+
+# ------------------------------------------------------------------------------------------------
+# K4 primal residual (residual=True, what every solve a user runs has on): the tails' branch of the phase
+# kernel and of both persistent kernels, the K sums and the per-worker rows against
+# hp_reference.chain_residual of the long-double theta history (tests/test_gpu_dispatch_classes.py, "K4
+# primal residual"). At chord = 0 only: the bound of a DIFFERENCE of thetas under the chord rule's
+# admitted truncation is not derived, and the residual branch does not depend on the chord.
+@pytest.mark.parametrize("n,m,d", NEWTON_GRAPH)
+def test_residual_newton_graph_engine(n, m, d):
+    _report("K4 newton graph %s" % ((n, m, d),), run_graph(n, m, d, 0.0, residual=True)[0])
+
+
+@pytest.mark.parametrize("rec", ["0", "1"])
+@pytest.mark.parametrize("n,m,d", NEWTON_PERSISTENT)
+def test_residual_newton_persistent_kernel(n, m, d, rec, monkeypatch):
+    monkeypatch.setenv("GADMM_NEWTON_REC", rec)
+    out, _, last = run_persistent(n, m, d, 0.0, KERNEL_OF_REC[rec], residual=True)
+    _report("K4 newton %s %s (stopped after %d)" % (KERNEL_OF_REC[rec], (n, m, d), last), out)
 
 
 # The pipeline kernel's schedule and arithmetic switches (read per launch), one per test, at the default

@@ -977,3 +977,134 @@ def test_qgadmm_bound_rejects_a_missing_clamp(n, m, d, bits, path):
     assert max(out[None][:2]) <= 1.0 / 8 and np.array_equal(out[None][2], ref.codes)
     assert out["no-clamp"][2][0, w, i] == L + 1   # the clamp is what the float64 recurrence relied on
     assert max(out["no-clamp"][:2]) >= QGADMM_POWER, out["no-clamp"][:2]
+
+
+# ------------------------------------------------------------------------------------------------
+# K4 primal residual (the "K4 primal residual" sections of tests/test_gpu_dispatch_classes.py and
+# tests/test_gpu_newton_classes.py, and every solve of tests/test_gpu_dgadmm_classes.py): a function of
+# the theta history the references already hold (``chain_residual``). The condition that entitles the
+# GPU tests to their bound, the power of that bound against six wrong residual branches, and the torch
+# path, the yardstick of the suite's older d = 50 residual test, held to the same reference.
+RES_OVER = K + H.PERSISTENT_OVERRUN   # the longest run a persistent kernel's test may ask for
+RES_BLOCKED_MULTI = (13, 20, 8)       # the static blocked kernel with several owned positions per workgroup
+RES_POWER = 100.0
+RES_CASES = (
+    [("linear", s, None, RES_OVER if s[2] <= 128 else K) for s in H.LINEAR_SHAPES + [RES_BLOCKED_MULTI]]
+    + [("path", s, p, RES_OVER) for s, p in H.RESIDUAL_PATHS.items()]
+    + [("logistic", s, None, RES_OVER if max(s[1:]) <= 64 else K) for s in H.LOGISTIC_SHAPES]
+    + [("live-stop", H.LIVE_STOP[0], H.LIVE_STOP[1], K)]
+    + [("newton", s, None, RES_OVER if s in H.NEWTON_PERSISTENT_SHAPES else K) for s in H.NEWTON_SHAPES]
+    + [("dgadmm", c[:3], c[3], RES_OVER if c[2] <= 99 else K) for c in DGADMM_CASES])
+
+
+def _res_reference(kind, shape, arg, run):
+    n, m, d = shape
+    if kind == "linear":
+        return H.linear_case(n, m, d, run)[3]
+    if kind == "path":
+        return H.linear_path_case(n, m, d, arg, run)[3]
+    if kind == "logistic":
+        return H.logistic_case(n, m, d, run)[5]
+    if kind == "live-stop":
+        return H.logistic_case(n, m, d, run, inner_tol=arg)[5]
+    if kind == "newton":
+        return H.newton_case(n, m, d, run, 0.0)
+    return H.dgadmm_case(n, m, d, arg, run)[4]
+
+
+def _res_ratios(ref, mutant=None):
+    """(rows, sum) err / bound of ``chain_residual`` of the float64 history in float64."""
+    rows = H.chain_residual(ref.theta64, ref.chains, np.float64, mutant)
+    return ref.err_res_w(rows) / ref.b_res_w, ref.err_res(rows.sum(axis=1)) / ref.b_res
+
+
+def _roles_change(chains):
+    """Some re-chain gives a worker another role or another set of neighbours."""
+    tabs = H.chain_tables(chains)
+    view = [{w: (p % 2, frozenset((l, r))) for w, (p, l, r) in tab.items()} for _, tab in tabs]
+    return any(a != b for a, b in zip(view, view[1:]))
+
+
+def _res_live_mutants(ref):
+    n, d = ref.theta.shape[1:]
+    chains = [(1, list(range(n)))] if ref.chains is None else ref.chains
+    live = ["stale-head", "pre-update"]
+    if n > 2:
+        live.append("one-edge")
+    if d > 64:
+        live.append("lanes-64")
+    if _roles_change(chains):
+        live.append("old-chain")
+    if any(list(p) != list(range(n)) for _, p in chains):
+        live.append("by-position")
+    return live
+
+
+@pytest.mark.parametrize("kind,shape,arg,run", RES_CASES)
+def test_residual_reference_condition_and_power(kind, shape, arg, run):
+    """On every case a GPU test compares a K4 residual on, over the longest run it may ask for: the
+    bounds are finite, the trace is positive on the tails and exactly 0 on the heads, the float64 history
+    sits within 1/8 of them (by construction; this guards the plumbing), and every wrong residual branch
+    that changes the value at the case -- a dropped right edge (n > 2), the heads' or the tail's own
+    theta of the iteration before, the first 64 coordinates only (d > 64), the chain of the iteration
+    before (where a re-chain changes roles or neighbours), the row indexed by chain position (any chain
+    but the identity) -- sits at least 100 bounds away in the rows or in their sum. An inert variant IS
+    the function. Measured: profiles/residual_classes/README.md."""
+    ref = _res_reference(kind, shape, arg, run)
+    n = shape[0]
+    assert ref.res_w.shape == (run, n) and ref.res.shape == (run,) and ref.res_w.dtype == H.LD
+    assert np.isfinite(ref.b_res_w) and np.isfinite(ref.b_res) and ref.b_res_w > 0 and ref.b_res > 0
+    assert np.all(ref.res_w[~ref.tails] == 0) and np.all(ref.res_w[ref.tails] > 0)
+    assert np.all(ref.tails.sum(axis=1) == n // 2)
+    own = _res_ratios(ref)
+    live = _res_live_mutants(ref)
+    print("residual %s %s %s run %d: e64 rows %.2e sum %.2e; float64 err/bound rows %.3f sum %.3f; "
+          "smallest/largest %.1e" % (kind, shape, arg, run, ref.e_res_w, ref.e_res, own[0], own[1],
+                                     float(ref.res.min() / ref.res.max())))
+    assert max(own) <= 1.0 / 8
+    for mutant in H.RESIDUAL_MUTANTS:
+        if mutant in live:
+            r = _res_ratios(ref, mutant)
+            print("   mutant %-11s: err/bound rows %.2e sum %.2e" % (mutant, *r))
+            assert max(r) >= RES_POWER, (mutant, r)
+        else:
+            assert np.array_equal(H.chain_residual(ref.theta, ref.chains, H.LD, mutant), ref.res_w), mutant
+
+
+def test_residual_reference_api():
+    """``chain_residual`` by hand on a tiny history, the identity default, and prefixes."""
+    th = np.zeros((2, 3, 2))
+    th[0] = [[1.0, 0.0], [3.0, 0.0], [0.0, 4.0]]
+    th[1] = [[1.0, 1.0], [1.0, 2.0], [2.0, 2.0]]
+    r = H.chain_residual(th, None, np.float64)
+    assert r.dtype == np.float64 and np.array_equal(r, [[0.0, 4.0 + 25.0, 0.0], [0.0, 1.0 + 1.0, 0.0]])
+    assert np.array_equal(H.chain_residual(th, [(1, [0, 1, 2])], np.float64), r)
+    assert np.array_equal(H.chain_residual(th, None, np.float64, "one-edge"), [[0.0, 4.0, 0.0], [0.0, 1.0, 0.0]])
+    # re-chained at iteration 2 to (1, 0, 2): worker 0 is the tail, its neighbours 1 and 2
+    r2 = H.chain_residual(th, [(1, [0, 1, 2]), (2, [1, 0, 2])], H.LD)
+    assert r2.dtype == H.LD and np.array_equal(r2, [[0.0, 29.0, 0.0], [1.0 + 2.0, 0.0, 0.0]])
+    assert np.array_equal(H.chain_residual(th, [(1, [0, 1, 2]), (2, [1, 0, 2])], H.LD, "old-chain"), r)
+    assert np.array_equal(H.chain_residual(th, [(1, [1, 0, 2])], H.LD, "by-position")[1], [0.0, 3.0, 0.0])
+    mask = H.tail_mask([(1, [0, 1, 2]), (2, [1, 0, 2])], 2, 3)
+    assert np.array_equal(mask, [[False, True, False], [True, False, False]])
+    a, b = H.linear_case(3, 7, 3, K + 3)[3], H.linear_case(3, 7, 3)[3]
+    assert np.array_equal(a.res_w[:K], b.res_w) and np.array_equal(a.res[:K], b.res) and a.err_res(b.res) == 0.0
+    assert a.err_res_w(np.asarray(b.res_w, dtype=np.float64)) <= 2.0 ** -52
+    q = H.qgadmm_case(3, 7, 3, 8, K)[3]   # the quantized reference keeps its own residual, on the public models
+    assert q.res.shape == (K,) and not hasattr(q, "res_w")
+
+
+@pytest.mark.parametrize("n,m,d", [(3, 7, 3), (4, 40, 33), (3, 80, 65)])
+def test_residual_of_the_torch_path(n, m, d):
+    """``chain_admm(backend="torch")`` is what tests/test_gpu.py holds the native residual to at d = 50;
+    here its ``primal_res`` is held to the reference under the case's bound."""
+    import torch
+    from gadmm_amd.algorithms import chain_admm
+    from gadmm_amd.models import LinearRegression
+    X, y, rho, ref = H.linear_case(n, m, d)
+    model = LinearRegression(torch.from_numpy(np.array(X)), torch.from_numpy(np.array(y)))
+    a = chain_admm(model, list(range(n)), n, rho, 0.0, 0.0, K, backend="torch")
+    assert a.extra["backend"] == "torch" and a.iters == K and len(a.primal_res) == K
+    ratio = ref.err_res(np.asarray(a.primal_res)) / ref.b_res
+    print("torch path %s: residual err/bound %.3f (e64 %.2e)" % ((n, m, d), ratio, ref.e_res))
+    assert ratio <= 1.0
