@@ -1,7 +1,8 @@
 // Device helpers shared by the persistent (single-launch) kernels: data-is-flag granules
 // (cdna_hip_programming.md §6 Guideline 16, R2), wall-clock deadlines, LDS-resident GEMV, and the
-// protocol every engine wraps around its worker loop: the placement prologue (place_block) and the
-// stop-rule monitor (monitor_loop). Host side of the protocol: persist_launch.h.
+// protocol every engine wraps around its worker loop: the placement prologue (place_block), the
+// stop-rule monitor (monitor_loop) and, on the worker side, the phase wait and the stop epilogue
+// (wait_decision, post_outcome). Host side of the protocol: persist_launch.h.
 #pragma once
 #include "gadmm_common.h"
 #include "stop_rule.h"
@@ -17,8 +18,8 @@
 #include "gadmm_chain.h"
 #include "quad_gemv.h"
 
-// The fence-free LDS ring posts (chain_persistent_logistic.hip: zr_post, chain_persistent_newton.hip:
-// lds_post) rely on one hardware property: the LDS instructions of ONE wave are performed in issue order
+// The fence-free LDS ring post (lds_post below: the s ring of the two-wave logistic kernel, the pipeline
+// rings of the Newton kernel) relies on one hardware property: the LDS instructions of ONE wave are performed in issue order
 // (CDNA3 / CDNA4: the property every counted `s_waitcnt lgkmcnt(N)` on a wave's LDS traffic relies on,
 // cdna_hip_programming.md §5). The HIP / LLVM memory model does not promise it, so it is enabled only
 // for the architectures whose ISA documents it; any other target compiles the fenced (release) post.
@@ -30,6 +31,34 @@
 #endif
 
 namespace persist {
+
+// Hand-offs between the waves of one workgroup through LDS words. LDS-only ordering: the fences name the
+// "local" address space, so they wait for LDS operations only (lgkmcnt). A plain workgroup fence would
+// also wait for the wave's outstanding GLOBAL stores (vmcnt): the write-through theta granules it has
+// just published (~1 us each).
+__device__ __forceinline__ int lds_load_acq(const int* p) {
+  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  return v;
+}
+__device__ __forceinline__ void lds_store_rel(int* p, int v) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// A per-step ring post without the release fence: a wave's LDS operations are performed in order
+// (GADMM_LDS_IN_ORDER), so a flag written after the ring data it announces (or after the reads of a
+// slot it frees) cannot become visible before them; the fence's s_waitcnt only held the flag back by
+// one LDS round trip. The compiler barrier keeps the data accesses first. `fenced` (PersistArgs::dbg
+// bit 17: GADMM_LOGISTIC_POSTFENCE / GADMM_NEWTON_POSTFENCE = 1) restores the fenced post (A/B).
+__device__ __forceinline__ void lds_post(int* p, int v, bool fenced) {
+  if (fenced || !GADMM_LDS_IN_ORDER) {  // fence-free only where in-order LDS is documented
+    lds_store_rel(p, v);
+    return;
+  }
+  asm volatile("" ::: "memory");
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p) {
@@ -380,6 +409,67 @@ __device__ __forceinline__ void monitor_loop(const PA& a, double* vals, __amdgpu
     }
     if (__shfl((int)code, 0, 64)) return;
   }
+}
+
+struct NoPollHook {
+  __device__ __forceinline__ void operator()(bool, bool) const {}
+};
+
+// The worker side of the same protocol: one wave's wait before iteration `it`, for what its neighbours
+// publish and for the monitor's decision of iteration it - lag (needed once it - start_iter >= lag), in
+// ONE loop, so both cost one round trip. A stop decision abandons the wait (a neighbour that saw it
+// publishes no more). Returns 1 go, 2 stop (code / stop_iter: the decision and its iteration it - lag),
+// 3 deadline passed (tested every 8th poll). Wave-uniform.
+//   poll   () -> bool: issues the site's neighbour loads, this lane's "all arrived" bit
+//   dslot  (it - lag) % ring as the site computes it (read only when a decision is needed)
+//   PAUSE  s_sleep units between two polls, 0 = back to back (each engine's measured choice)
+//   hook   (arrived, decided) after the loads of every poll, before the tests (timeline stamps)
+template <bool SYS, int PAUSE, class PA, class Poll, class Hook = NoPollHook>
+__device__ __forceinline__ int wait_decision(const PA& a, int it, int start_iter, int dslot, unsigned long long deadline,
+                                             Poll poll, int& code, int& stop_iter, Hook hook = Hook()) {
+  const int jdec = it - a.lag;
+  const unsigned tj = make_tag(a.epoch, jdec);
+  bool decided = !(it - start_iter >= a.lag);
+  unsigned long long dv = 0;
+  for (int spin = 0;; ++spin) {
+    const bool nb = poll();
+    if (!decided) {
+      dv = __shfl(load_dec<SYS>(&a.decg[dslot]), 0, 64);
+      decided = (unsigned)(dv >> 32) == tj;
+    }
+    hook(nb, decided);
+    if (decided && (unsigned)(dv & 0xffffffffu) != 0u) {
+      code = (int)(unsigned)(dv & 0xffffffffu);
+      stop_iter = jdec;
+      return 2;
+    }
+    if (decided && __all(nb)) return 1;
+    if ((spin & 7) == 7 && now_ticks() > deadline) return 3;
+    if (PAUSE > 0) __builtin_amdgcn_s_sleep(PAUSE);
+  }
+}
+
+// How a launch ended, into ctl (by one thread of each worker workgroup): done = 4 if this workgroup
+// gave up on a deadline, else block 0 records the stop decision the workers left on. CHAIN: the chain
+// engines' resume state (pending dual, monitored iteration); the star engine has neither. Returns
+// whether anything was recorded.
+template <bool CHAIN = true>
+__device__ __forceinline__ bool post_outcome(ChainCtl* ctl, int abort, int bid, int stop_code, int stop_iter, int it) {
+  if (abort) {
+    ctl->done = 4;
+    return true;
+  }
+  if (bid == 0 && stop_code) {
+    ctl->done = stop_code;
+    ctl->conv_iter = stop_iter;
+    ctl->iter = it;
+    if (CHAIN) {
+      ctl->pending = 1;
+      ctl->monitored = stop_iter;
+    }
+    return true;
+  }
+  return false;
 }
 
 }  // namespace persist

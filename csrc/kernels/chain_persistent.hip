@@ -223,15 +223,9 @@ __global__ void __launch_bounds__(REG ? 64 : NT) chain_persistent_kernel(Persist
       }
     }
     long long t_ready = 0, t_pub = 0, t_bar = 0, t_gemv = 0;
-    // -- stop rule: decision of iteration it - lag (all workers leave at the same boundary). Its
-    // load is issued here and resolved after the neighbour wait, so its latency overlaps the wait;
-    // nothing is committed before the barrier that publishes the decision.
-    const bool check = it - a.start_iter >= a.lag;
-    const int jdec = it - a.lag;
-
     // -- neighbours' theta, the stop decision, and the rhs (wave 0). The decision of iteration
-    // it - lag is polled in the same loop as the neighbours' granules (one round trip for both);
-    // a stop decision abandons the wait, since a neighbour that already saw it publishes no more.
+    // it - lag (all workers leave at the same boundary) is polled in the same loop as the neighbours'
+    // granules (wait_decision: one round trip for both); a stop decision abandons the wait.
     // Nothing is committed before the barrier that publishes the outcome.
     double mun[NC];
     double rv = 0.0;  // REG: this lane's rhs element (the quad GEMV's input)
@@ -241,37 +235,30 @@ __global__ void __launch_bounds__(REG ? 64 : NT) chain_persistent_kernel(Persist
       const unsigned tnb = make_tag(a.epoch, jnb);
       const int ra = need_nb ? left : -1, rb = need_nb ? right : -1;
       const int row_nb = head ? row_prev : row_it;  // table rows of theta^jnb
-      int dslot = rs - a.lag;  // == jdec % ring
+      int dslot = rs - a.lag;  // == (it - lag) % ring
       if (dslot < 0) dslot += a.ring;
-      const unsigned tj = make_tag(a.epoch, jdec);
-      bool decided = !check;
-      unsigned long long dv = 0;
-      int outcome = 0;  // 1 go, 2 stop, 3 timeout
-      for (int spin = 0;; ++spin) {
-        bool nb = true;
+      int code = 0, jdec = 0;
+      const int outcome = wait_decision<SYS, GADMM_POLL_SLEEP>(
+          a, it, a.start_iter, dslot, deadline,
+          [&] {
+            bool nb = true;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int i = lane + 64 * c;
-          if (i < d) {
-            if (ra >= 0) nb &= load_granule<SYS>(rth, ((row_nb + ra) * d + i) * 16, tnb, &tl[c]);
-            if (rb >= 0) nb &= load_granule<SYS>(rth, ((row_nb + rb) * d + i) * 16, tnb, &tr[c]);
-          }
-        }
-        if (!decided) {
-          dv = __shfl(load_dec<SYS>(&a.decg[dslot]), 0, 64);
-          decided = (unsigned)(dv >> 32) == tj;
-        }
-        if (decided && (unsigned)(dv & 0xffffffffu) != 0u) { outcome = 2; break; }
-        if (decided && __all(nb)) { outcome = 1; break; }
-        if ((spin & 7) == 7 && now_ticks() > deadline) { outcome = 3; break; }
-        GADMM_POLL_PAUSE();
-      }
+            for (int c = 0; c < NC; ++c) {
+              const int i = lane + 64 * c;
+              if (i < d) {
+                if (ra >= 0) nb &= load_granule<SYS>(rth, ((row_nb + ra) * d + i) * 16, tnb, &tl[c]);
+                if (rb >= 0) nb &= load_granule<SYS>(rth, ((row_nb + rb) * d + i) * 16, tnb, &tr[c]);
+              }
+            }
+            return nb;
+          },
+          code, jdec);
       if (lane == 0) {
         if (TL) t_ready = (long long)now_ticks();
         if (outcome == 3) abort_lds = 1;
         if (outcome == 2) {
           stop_lds = 1;
-          stop_code = (int)(unsigned)(dv & 0xffffffffu);
+          stop_code = code;
           stop_iter = jdec;
         }
       }
@@ -426,16 +413,8 @@ __global__ void __launch_bounds__(REG ? 64 : NT) chain_persistent_kernel(Persist
     }
   }
   if (threadIdx.x == 0) {
-    if (abort_lds) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    } else if (bid == 0 && hard_stopped) {  // done / conv_iter come from the monitor (rank 0)
-      a.ctl->iter = it;
+    if (!post_outcome(a.ctl, abort_lds, bid, stop_code, stop_iter, it) && bid == 0 && hard_stopped) {
+      a.ctl->iter = it;  // done / conv_iter come from the monitor (rank 0)
       a.ctl->pending = 1;
     }
   }

@@ -28,18 +28,11 @@
 #include "persist_device.h"
 #include "persist_launch.h"
 #include "chain_device.h"
+#include "chain_worker.h"
+#include "gadmm_logi.h"
 #include "fast_sigm.h"
 #include <cstddef>
 #include <stdlib.h>
-
-struct LogiArgs {
-  const double* X;  // [n_local][m][d]
-  const double* Y;  // [n_local][m]
-  int m, max_inner;
-  double lam, step, inner_tol;
-  int* inner_iters;  // [n_local] optional: GD steps of the worker's last local solve
-  double* scratch;   // Newton pipeline only (chain_persistent_newton.hip): per-worker refresh images
-};
 
 template <int T, bool SYS>
 __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistArgs a, LogiArgs g) {
@@ -65,12 +58,10 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
   const PhaseSlot sl = a.slots[bid];
   const int li = sl.li, w = sl.gid, left = sl.left, right = sl.right;
   const bool head = (a.pos[bid] % 2) == 0;
+  const LaneSlot ls = lane_slot(sl, lane, d);
   const double rho = a.rho, lam = g.lam, step = g.step;
   double* st = lds;  // QSTAGE doubles: quad GEMV staging
-  u32x4* const p0 = a.push ? a.push[2 * bid] : nullptr;
-  u32x4* const p1 = a.push ? a.push[2 * bid + 1] : nullptr;
-  const __amdgpu_buffer_rsrc_t rp0 = rsrc_of(p0 ? (const void*)p0 : (const void*)a.thg);
-  const __amdgpu_buffer_rsrc_t rp1 = rsrc_of(p1 ? (const void*)p1 : (const void*)a.thg);
+  const ThetaPush push = push_targets(a, bid);
   const double* Xg = g.X + (long)li * m * d;
   double Xq[4][T], XTq[4][T];
 #pragma unroll
@@ -83,6 +74,11 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
     }
   const bool inj = lane < d, ini = lane < m;
   const double yv = ini ? g.Y[(long)li * m + lane] : 0.0;
+  // The worker's state, wait and dual steps below are load_state / wait_decision / head_lazy_dual /
+  // tail_dual_residual (chain_worker.h, persist_device.h) written out: through the helpers this kernel's
+  // register allocation changes, and through load_state or head_lazy_dual the compiler contracts one
+  // multiply-add of the shift differently, so the trace is no longer the graph engine's bit for bit
+  // (profiles/worker_protocol)
   double th = inj ? a.theta[(long)w * d + lane] : 0.0;  // theta_n^{i-1}
   double mu = inj ? a.mu[(long)li * d + lane] : 0.0;
   double tl = (inj && left >= 0) ? a.theta[(long)left * d + lane] : 0.0;
@@ -160,11 +156,7 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
     }
     // -- publish theta^it: own table + the remote neighbours' tables
     const unsigned tag = make_tag(a.epoch, it);
-    if (inj) {
-      put_granule<SYS>(local, rth, (w * d + lane) * 16, tag, x);
-      if (p0) store_granule<SYS>(rp0, (w * d + lane) * 16, tag, x);
-      if (p1) store_granule<SYS>(rp1, (w * d + lane) * 16, tag, x);
-    }
+    publish_theta<SYS>(local, rth, push, ls, tag, x);
     if (!head) {  // tails: both neighbours are this iteration's heads -> dual update now
       double rp = 0.0;
       if (inj) {
@@ -189,22 +181,10 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
     const double xx = wave_sum_f64(inj ? x * x : 0.0);
     if (lane == 0) put_granule<SYS>(local, rob, ((it % a.ring) * n + w) * 16, tag, lam * 0.5 * xx + part);
   }
-  // final state (plain stores; visible to the host after the kernel)
-  if (inj) {
-    a.theta[(long)w * d + lane] = th;
-    a.mu[(long)li * d + lane] = mu;
-  }
+  store_state(a, ls, th, mu);
   if (lane == 0) {
     if (g.inner_iters) g.inner_iters[li] = used;
-    if (abort) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    }
+    post_outcome(a.ctl, abort, bid, stop_code, stop_iter, it);
   }
 }
 
@@ -225,29 +205,6 @@ constexpr int ZR_SLOTS = 64;  // s ring depth; the margins wave checks it every 
 // (same-box A/B, E3 bench: 8/4 5.34, 16/4 5.34, 16/8 5.17, 32/8 5.11, 64/8 4.93 ms; 128/8 with an early-end
 // check every 8 steps 5.41, 32/16 with one every step 5.43: profiles/r06_logistic)
 constexpr int ZR_CHK = 8;
-
-__device__ __forceinline__ int zr_load_acq(const int* p) {
-  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  return v;
-}
-__device__ __forceinline__ void zr_store_rel(int* p, int v) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// The per-step ring posts (s produced, s consumed) without the release fence: a wave's LDS operations
-// are performed in order, so the flag cannot become visible before the slot data written (or read)
-// before it; the fence only held the flag back by one LDS round trip on the margins wave's chain.
-// GADMM_LOGISTIC_POSTFENCE=1 (PersistArgs::dbg bit 17) restores the fenced posts (A/B).
-__device__ __forceinline__ void zr_post(int* p, int v, bool fenced) {
-  if (fenced || !GADMM_LDS_IN_ORDER) {  // fence-free only where in-order LDS is documented
-    zr_store_rel(p, v);
-    return;
-  }
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // s = y / (1 + e^{y z}) on the margins wave's critical path: inv1pexp_fast (fast_sigm.h). Measured 5.64 ->
 // 5.21 ms on E3, one box (profiles/r05_j/r5jf); the default (GADMM_LOGISTIC_FASTSIGM=0: libm exp and
@@ -289,6 +246,7 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
   const PhaseSlot sl = a.slots[bid];
   const int li = sl.li, w = sl.gid, left = sl.left, right = sl.right;
   const bool head = (a.pos[bid] % 2) == 0;
+  const LaneSlot ls = lane_slot(sl, lane, d);
   const double rho = a.rho, lam = g.lam, step = g.step;
   const double* Xg = g.X + (long)li * m * d;
   const bool inj = lane < d, ini = lane < m;
@@ -304,8 +262,8 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
     for (;;) {  // one local solve per start
       int s0 = 0;
       for (int spin = 0;; ++spin) {
-        s0 = zr_load_acq(&ctl[0]);
-        if (s0 > sid || zr_load_acq(&ctl[4])) break;
+        s0 = lds_load_acq(&ctl[0]);
+        if (s0 > sid || lds_load_acq(&ctl[4])) break;
         if ((spin & 63) == 63 && now_ticks() > deadline) return;
         __builtin_amdgcn_s_sleep(1);
       }
@@ -329,19 +287,19 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
           // slots of steps k .. k + ZR_CHK - 1 are free once steps <= k + ZR_CHK - 1 - ZR_SLOTS were read;
           // the iterate wave's end of the solve also ends this run-ahead
           for (int spin = 0;; ++spin) {
-            if (zr_load_acq(&ctl[3]) == sid) { ended = true; break; }
-            if (zr_load_acq(&ctl[2]) >= sid * 1024 + k + ZR_CHK - ZR_SLOTS) break;
+            if (lds_load_acq(&ctl[3]) == sid) { ended = true; break; }
+            if (lds_load_acq(&ctl[2]) >= sid * 1024 + k + ZR_CHK - ZR_SLOTS) break;
             if ((spin & 63) == 63 && now_ticks() > deadline) return;
           }
           if (ended) break;
         }
         double* slot = sring + (k % ZR_SLOTS) * 4 * QX;
         slot[(lane & 3) * QX + (lane >> 2)] = sv;  // quad_gemv's x layout: both waves' GEMVs read it in place
-        zr_post(&ctl[1], sid * 1024 + k + 1, post_fence);
+        lds_post(&ctl[1], sid * 1024 + k + 1, post_fence);
         const double u = quad_gemv_staged<T>(Kq, slot);  // (K s)_i
         if (k == 0) {  // c = X sh arrives after z_0 (the iterate wave posts z_0 first)
           for (int spin = 0;; ++spin) {
-            if (zr_load_acq(&ctl[5]) == sid) break;
+            if (lds_load_acq(&ctl[5]) == sid) break;
             if ((spin & 63) == 63 && now_ticks() > deadline) return;
           }
           cc = zc[64 + lane];
@@ -353,10 +311,7 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
   }
 
   // ------------------------------------------------------------------ iterate wave (wave 0)
-  u32x4* const p0 = a.push ? a.push[2 * bid] : nullptr;
-  u32x4* const p1 = a.push ? a.push[2 * bid + 1] : nullptr;
-  const __amdgpu_buffer_rsrc_t rp0 = rsrc_of(p0 ? (const void*)p0 : (const void*)a.thg);
-  const __amdgpu_buffer_rsrc_t rp1 = rsrc_of(p1 ? (const void*)p1 : (const void*)a.thg);
+  const ThetaPush push = push_targets(a, bid);
   double Xq[4][T], XTq[4][T];
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -373,6 +328,9 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
     Kb[lane * 64 + j] = ini ? kc : 0.0;
   }
   for (int j = m; j < 64; ++j) Kb[lane * 64 + j] = 0.0;
+  // The worker's state, wait and dual steps below are load_state / wait_decision / head_lazy_dual /
+  // tail_dual_residual (chain_worker.h, persist_device.h) written out: through any of the helpers this
+  // kernel's register allocation changes (20 to 50 more values parked in AGPRs, profiles/worker_protocol)
   double th = inj ? a.theta[(long)w * d + lane] : 0.0;
   double mu = inj ? a.mu[(long)li * d + lane] : 0.0;
   double tl = (inj && left >= 0) ? a.theta[(long)left * d + lane] : 0.0;
@@ -434,21 +392,21 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
     const double z0 = quad_gemv<T>(Xq, x, st);
     zc[lane] = ini ? z0 : 0.0;
     ++sid;
-    zr_store_rel(&ctl[0], sid);  // the margins wave starts from z_0 ...
+    lds_store_rel(&ctl[0], sid);  // the margins wave starts from z_0 ...
     const double c0 = quad_gemv<T>(Xq, sh, st);
     zc[64 + lane] = ini ? c0 : 0.0;
-    zr_store_rel(&ctl[5], sid);  // ... and needs c only after its first K s
+    lds_store_rel(&ctl[5], sid);  // ... and needs c only after its first K s
     used = 0;
     for (int k = 0; k < g.max_inner; ++k) {
       const int want = sid * 1024 + k + 1;
       bool got = false;
       for (int spin = 0;; ++spin) {
-        if (zr_load_acq(&ctl[1]) >= want) { got = true; break; }
+        if (lds_load_acq(&ctl[1]) >= want) { got = true; break; }
         if ((spin & 63) == 63 && now_ticks() > deadline) break;
       }
       if (!got) { abort = 1; break; }
       const double gx = quad_gemv_staged<T>(XTq, sring + (k % ZR_SLOTS) * 4 * QX);
-      zr_post(&ctl[2], want, post_fence);  // (after this GEMV's reads of the slot, LDS in order)
+      lds_post(&ctl[2], want, post_fence);  // (after this GEMV's reads of the slot, LDS in order)
       bool conv = true;
       if (inj) {
         const double gr = -gx + lam * x + sh;
@@ -459,14 +417,10 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
       used = k + 1;
       if (__all(conv)) break;
     }
-    zr_store_rel(&ctl[3], sid);  // this solve is over: the margins wave stops its run-ahead
+    lds_store_rel(&ctl[3], sid);  // this solve is over: the margins wave stops its run-ahead
     if (abort) break;
     const unsigned tag = make_tag(a.epoch, it);
-    if (inj) {
-      put_granule<SYS>(local, rth, (w * d + lane) * 16, tag, x);
-      if (p0) store_granule<SYS>(rp0, (w * d + lane) * 16, tag, x);
-      if (p1) store_granule<SYS>(rp1, (w * d + lane) * 16, tag, x);
-    }
+    publish_theta<SYS>(local, rth, push, ls, tag, x);
     if (!head) {
       double rp = 0.0;
       if (inj) {
@@ -490,22 +444,11 @@ __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(P
     const double xx = wave_sum_f64(inj ? x * x : 0.0);
     if (lane == 0) put_granule<SYS>(local, rob, ((it % a.ring) * n + w) * 16, tag, lam * 0.5 * xx + part);
   }
-  zr_store_rel(&ctl[4], 1);  // the margins wave leaves
-  if (inj) {
-    a.theta[(long)w * d + lane] = th;
-    a.mu[(long)li * d + lane] = mu;
-  }
+  lds_store_rel(&ctl[4], 1);  // the margins wave leaves
+  store_state(a, ls, th, mu);
   if (lane == 0) {
     if (g.inner_iters) g.inner_iters[li] = used;
-    if (abort) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    }
+    post_outcome(a.ctl, abort, bid, stop_code, stop_iter, it);
   }
 }
 

@@ -22,24 +22,18 @@
 //
 // Cross-worker protocol (heads / tails, lazy head dual, tagged theta granules, a monitor workgroup
 // that sums f_n in worker order and posts the lagged stop decision into every rank's ring, deadlines
-// on every spin, the xGMI fabric across GPUs): as chain_persistent_logistic.hip.
+// on every spin, the xGMI fabric across GPUs): the shared worker protocol, wait_decision / post_outcome
+// (persist_device.h) around the lane-per-coordinate chain worker (chain_worker.h).
 #include "gadmm_common.h"
 #include "gadmm_chain.h"
 #include "persist_device.h"
 #include "persist_launch.h"
 #include "chain_device.h"
+#include "chain_worker.h"
+#include "gadmm_logi.h"
 #include "fast_sigm.h"
 #include <cstddef>
 #include <cstdlib>
-
-struct LogiArgs {  // == chain_persistent_logistic.hip (one ABI for both persistent logistic kernels)
-  const double* X;  // [n_local][m][d]
-  const double* Y;  // [n_local][m]
-  int m, max_inner;
-  double lam, step, inner_tol;  // Newton: step = chord threshold (<= 0: a fresh inverse every step)
-  int* inner_iters;             // [n_local] optional: Newton steps of the worker's last local solve
-  double* scratch;              // pipeline kernel: [n_local][RSLOTS][4 QB] refresh images (P | B | XP | XB)
-};
 
 namespace {
 
@@ -86,25 +80,18 @@ struct NCtl {        // LDS words of the solver <-> crew protocol
   int quit;          // the solve is over: the crew leaves once it has served every request posted before
 };
 
-// LDS-only ordering: the fences name the "local" address space, so they wait for LDS operations only
-// (lgkmcnt). A plain workgroup fence would also wait for this wave's outstanding GLOBAL stores
-// (vmcnt) -- for the solver, the write-through theta granules it has just published (~1 us each).
-__device__ __forceinline__ int lds_load_acq(const int* p) {
-  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  return v;
-}
-__device__ __forceinline__ void lds_store_rel(int* p, int v) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// barrier among the 4 crew waves only (the solver wave never joins): an LDS arrival counter
-__device__ __forceinline__ void crew_sync(int* cnt, int& gen) {
+// barrier among the 4 crew waves only (the solver / pipeline waves never join): an LDS arrival counter.
+// DL: the wait is given up once `dl` has passed (tested every 256th poll), so the pipeline kernel ends
+// even if a crew wave is gone; the one-wave kernel's crew has no deadline.
+template <bool DL = false>
+__device__ __forceinline__ void crew_sync(int* cnt, int& gen, unsigned long long dl = 0) {
   gen += CREW;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < gen) __builtin_amdgcn_s_sleep(1);
+  for (int spin = 0; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < gen; ++spin) {
+    __builtin_amdgcn_s_sleep(1);
+    if (DL && (spin & 255) == 255 && __builtin_amdgcn_s_memrealtime() > dl) break;
+  }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
@@ -126,6 +113,67 @@ __device__ __forceinline__ int qidx(int row, int col) {
   return ((t >> 1) * 4 + r) * 128 + 2 * (iq + 16 * c4) + (t & 1);
 }
 constexpr int QCOLS = 4 * (QT + (QT & 1));
+
+// In-place block Gauss-Jordan inverse (SPD, no pivoting) of the 64 x 64 matrix (d x d, identity padded)
+// that the 4 crew waves hold in registers: lane i of crew wave cw keeps row i's columns j = cw + 4c in
+// h[c]. 4 x 4 pivot blocks. Block K = p..p+3: P = A_KK, non-pivot rows L_i = A_iK P^-1, A_ij -= L_i A_Kj,
+// A_iK = -L_i; pivot rows A_Kj = P^-1 A_Kj, A_KK = P^-1. Only column K is published (slabs: [2][4][64]
+// doubles of LDS, `sync`: the crew barrier); the pivot rows follow from the symmetric structure
+// (processed / unprocessed cross blocks are antisymmetric), as in chain_newton.hip.
+template <class Sync>
+__device__ __forceinline__ void crew_gauss_jordan(double (&h)[NCW], double* slabs, int d, int cw, Sync sync) {
+  const int i = threadIdx.x & 63;
+  const int nb = (d + 3) >> 2;
+  for (int bb = 0; bb < nb; ++bb) {
+    const int p = 4 * bb;
+    double* slab = slabs + (bb & 1) * 256;  // [4][64]: column p + q of the current matrix
+    {  // the block's column p + q is register c = p / 4 of crew wave q
+      double hv = 0.0;
+#pragma unroll
+      for (int c = 0; c < NCW; ++c) hv = (c == bb) ? h[c] : hv;
+      slab[cw * 64 + i] = hv;
+    }
+    sync();
+    double P[4][4], Rr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      Rr[q] = slab[q * 64 + i];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) P[q][r] = slab[q * 64 + p + r];
+    }
+    const bool pivrow = (i >> 2) == bb;
+    if (pivrow) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Rr[q] = (q == (i & 3)) ? 1.0 : 0.0;
+    }
+    const double a00 = P[0][0], a01 = P[1][0], a11 = P[1][1];
+    const double ia = rcp_nr(fma(a00, a11, -a01 * a01));
+    const double A00 = a11 * ia, A01 = -a01 * ia, A11 = a00 * ia;
+    const double b00 = P[2][0], b01 = P[3][0], b10 = P[2][1], b11 = P[3][1];
+    const double w00 = fma(A00, b00, A01 * b10), w01 = fma(A00, b01, A01 * b11);
+    const double w10 = fma(A01, b00, A11 * b10), w11 = fma(A01, b01, A11 * b11);
+    const double s00 = P[2][2] - fma(b00, w00, b10 * w10);
+    const double s01 = P[3][2] - fma(b00, w01, b10 * w11);
+    const double s11 = P[3][3] - fma(b01, w01, b11 * w11);
+    const double is = rcp_nr(fma(s00, s11, -s01 * s01));
+    const double y0 = fma(A00, Rr[0], A01 * Rr[1]), y1 = fma(A01, Rr[0], A11 * Rr[1]);
+    const double z2 = Rr[2] - fma(b00, y0, b10 * y1), z3 = Rr[3] - fma(b01, y0, b11 * y1);
+    const double l2 = fma(s11, z2, -s01 * z3) * is, l3 = fma(s00, z3, -s01 * z2) * is;
+    const double l0 = y0 - fma(w00, l2, w01 * l3), l1 = y1 - fma(w10, l2, w11 * l3);
+    const double lw = cw == 0 ? l0 : (cw == 1 ? l1 : (cw == 2 ? l2 : l3));  // l[j - p] for j = p + cw
+#pragma unroll
+    for (int c = 0; c < NCW; ++c) {
+      const int j = cw + CREW * c;
+      const double tq = fma(l0, slab[j], fma(l1, slab[64 + j], fma(l2, slab[128 + j], l3 * slab[192 + j])));
+      const bool inK = c == bb;
+      const double sg = j < p ? -1.0 : 1.0;
+      double v;
+      if (inK) v = pivrow ? lw : -lw;
+      else v = pivrow ? sg * tq : fma(-sg, tq, h[c]);
+      h[c] = v;
+    }
+  }
+}
 
 // One refresh by the crew (crew index cw = 0..3): Hs = X^T diag(wq) X + shift I (MFMA), then the inverse
 // into the quad-LDS buffer `qb`, either
@@ -218,66 +266,11 @@ __device__ void crew_refresh(double* lds, const NLds& L, int m, int d, double sh
     crew_sync(cnt, gen);
     return;
   }
-  // in-place block Gauss-Jordan (SPD, no pivoting), 4 x 4 pivot blocks; lane i of crew wave cw keeps row
-  // i's columns j = cw + 4c. Block K = p..p+3: P = A_KK, non-pivot rows L_i = A_iK P^-1, A_ij -= L_i A_Kj,
-  // A_iK = -L_i; pivot rows A_Kj = P^-1 A_Kj, A_KK = P^-1. Only column K is published; the pivot rows
-  // follow from the symmetric structure (processed / unprocessed cross blocks are antisymmetric), as in
-  // chain_newton.hip.
   const int i = lane;
   double h[NCW];
 #pragma unroll
   for (int c = 0; c < NCW; ++c) h[c] = Hs[i * HS + cw + CREW * c];
-  const int nb = (d + 3) >> 2;
-  double* slabs = lds + L.slab;
-  for (int bb = 0; bb < nb; ++bb) {
-    const int p = 4 * bb;
-    double* slab = slabs + (bb & 1) * 256;  // [4][64]: column p + q of the current matrix
-    {  // the block's column p + q is register c = p / 4 of crew wave q
-      double hv = 0.0;
-#pragma unroll
-      for (int c = 0; c < NCW; ++c) hv = (c == bb) ? h[c] : hv;
-      slab[cw * 64 + i] = hv;
-    }
-    crew_sync(cnt, gen);
-    double P[4][4], Rr[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      Rr[q] = slab[q * 64 + i];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) P[q][r] = slab[q * 64 + p + r];
-    }
-    const bool pivrow = (i >> 2) == bb;
-    if (pivrow) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Rr[q] = (q == (i & 3)) ? 1.0 : 0.0;
-    }
-    const double a00 = P[0][0], a01 = P[1][0], a11 = P[1][1];
-    const double ia = rcp_nr(fma(a00, a11, -a01 * a01));
-    const double A00 = a11 * ia, A01 = -a01 * ia, A11 = a00 * ia;
-    const double b00 = P[2][0], b01 = P[3][0], b10 = P[2][1], b11 = P[3][1];
-    const double w00 = fma(A00, b00, A01 * b10), w01 = fma(A00, b01, A01 * b11);
-    const double w10 = fma(A01, b00, A11 * b10), w11 = fma(A01, b01, A11 * b11);
-    const double s00 = P[2][2] - fma(b00, w00, b10 * w10);
-    const double s01 = P[3][2] - fma(b00, w01, b10 * w11);
-    const double s11 = P[3][3] - fma(b01, w01, b11 * w11);
-    const double is = rcp_nr(fma(s00, s11, -s01 * s01));
-    const double y0 = fma(A00, Rr[0], A01 * Rr[1]), y1 = fma(A01, Rr[0], A11 * Rr[1]);
-    const double z2 = Rr[2] - fma(b00, y0, b10 * y1), z3 = Rr[3] - fma(b01, y0, b11 * y1);
-    const double l2 = fma(s11, z2, -s01 * z3) * is, l3 = fma(s00, z3, -s01 * z2) * is;
-    const double l0 = y0 - fma(w00, l2, w01 * l3), l1 = y1 - fma(w10, l2, w11 * l3);
-    const double lw = cw == 0 ? l0 : (cw == 1 ? l1 : (cw == 2 ? l2 : l3));  // l[j - p] for j = p + cw
-#pragma unroll
-    for (int c = 0; c < NCW; ++c) {
-      const int j = cw + CREW * c;
-      const double tq = fma(l0, slab[j], fma(l1, slab[64 + j], fma(l2, slab[128 + j], l3 * slab[192 + j])));
-      const bool inK = c == bb;
-      const double sg = j < p ? -1.0 : 1.0;
-      double v;
-      if (inK) v = pivrow ? lw : -lw;
-      else v = pivrow ? sg * tq : fma(-sg, tq, h[c]);
-      h[c] = v;
-    }
-  }
+  crew_gauss_jordan(h, lds + L.slab, d, cw, [&] { crew_sync(cnt, gen); });
   if (tl && cw == 0 && lane == 0) tl[2] = (long long)__builtin_amdgcn_s_memrealtime();
   // the inverse into the quad-LDS layout of quad_gemv_lds<QT>: element (row, col) at
   // ((t >> 1) * 4 + r) * 128 + 2 lq + (t & 1), row = iq + 16 r, col = c4 + 4 t, lq = iq + 16 c4; padding 0
@@ -396,17 +389,13 @@ __global__ void __launch_bounds__(NT) chain_persistent_newton_kernel(PersistArgs
       const int row = qi + 16 * r, col = qc + 4 * t;
       Xq[r][t] = (row < m && col < d) ? Xg[(long)row * d + col] : 0.0;
     }
-  u32x4* const p0 = a.push ? a.push[2 * bid] : nullptr;
-  u32x4* const p1 = a.push ? a.push[2 * bid + 1] : nullptr;
-  const __amdgpu_buffer_rsrc_t rp0 = rsrc_of(p0 ? (const void*)p0 : (const void*)a.thg);
-  const __amdgpu_buffer_rsrc_t rp1 = rsrc_of(p1 ? (const void*)p1 : (const void*)a.thg);
+  const LaneSlot ls = lane_slot(sl, lane, d);
+  const ThetaPush push = push_targets(a, bid);
   const bool inj = lane < d, ini = lane < m;
   const double yv = ini ? g.Y[(long)li * m + lane] : 0.0;
-  double th = inj ? a.theta[(long)w * d + lane] : 0.0;
   const bool fast_sig = (a.dbg & 32) == 0;
-  double mu = inj ? a.mu[(long)li * d + lane] : 0.0;
-  double tl = (inj && left >= 0) ? a.theta[(long)left * d + lane] : 0.0;
-  double tr = (inj && right >= 0) ? a.theta[(long)right * d + lane] : 0.0;
+  double th, mu, tl, tr;
+  load_state(a, ls, th, mu, tl, tr);
   int pending = a.pending_in;
   int stop_code = 0, stop_iter = 0, abort = 0, used = 0, nfail = 0;
   // Inverse bookkeeping (refresh ids are consecutive; refresh r lives in buffer r % 3):
@@ -433,49 +422,19 @@ __global__ void __launch_bounds__(NT) chain_persistent_newton_kernel(PersistArgs
   int it = a.start_iter;
   for (;; ++it) {
     if (it > a.max_iter + a.lag) break;
-    const bool check = it - a.start_iter >= a.lag;
-    const int jdec = it - a.lag;
-    const bool need_nb = head ? it > a.start_iter : true;
-    const int jnb = head ? it - 1 : it;
-    const unsigned tnb = make_tag(a.epoch, jnb), tj = make_tag(a.epoch, jdec);
-    const int ra = need_nb ? left : -1, rb = need_nb ? right : -1;
-    bool decided = !check;
-    unsigned long long dv = 0;
-    int outcome = 0;  // 1 go, 2 stop, 3 timeout
-    for (int spin = 0;; ++spin) {
-      bool nb = true;
-      if (inj) {
-        if (ra >= 0) nb &= load_granule<SYS>(rth, (ra * d + lane) * 16, tnb, &tl);
-        if (rb >= 0) nb &= load_granule<SYS>(rth, (rb * d + lane) * 16, tnb, &tr);
-      }
-      if (!decided) {
-        dv = __shfl(load_dec<SYS>(&a.decg[jdec % a.ring]), 0, 64);
-        decided = (unsigned)(dv >> 32) == tj;
-      }
-      if (decided && (unsigned)(dv & 0xffffffffu) != 0u) { outcome = 2; break; }
-      if (decided && __all(nb)) { outcome = 1; break; }
-      if ((spin & 7) == 7 && now_ticks() > deadline) { outcome = 3; break; }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    const NbWait nw = nb_wait(a, ls, head, it);
+    const int outcome = wait_decision<SYS, 1>(
+        a, it, a.start_iter, (it - a.lag) % a.ring, deadline, [&] { return load_neighbours<SYS>(rth, ls, nw, tl, tr); },
+        stop_code, stop_iter);
     if (outcome != 1) {
-      if (outcome == 2) {
-        stop_code = (int)(unsigned)(dv & 0xffffffffu);
-        stop_iter = jdec;
-      } else {
-        abort = 1;
-      }
+      if (outcome != 2) abort = 1;
       break;
     }
     // -- lazy dual (heads); x-independent gradient part cv = mu - rho (th_l + th_r)
     double cv = 0.0, x = 0.0;
     if (inj) {
-      double mm = mu;
-      if (head && pending) {
-        if (left >= 0) mm = mm - rho * (tl - th);
-        if (right >= 0) mm = mm + rho * (th - tr);
-        mu = mm;
-      }
-      cv = mm;
+      if (head && pending) head_lazy_dual(ls, rho, th, tl, tr, mu);
+      cv = mu;
       if (left >= 0) cv = cv - rho * tl;
       if (right >= 0) cv = cv - rho * tr;
       x = th;
@@ -542,28 +501,10 @@ __global__ void __launch_bounds__(NT) chain_persistent_newton_kernel(PersistArgs
     }
     // -- publish theta^it: own table + the remote neighbours' tables (first: the neighbours wait)
     const unsigned tag = make_tag(a.epoch, it);
-    if (inj) {
-      store_granule<SYS>(rth, (w * d + lane) * 16, tag, x);
-      if (p0) store_granule<SYS>(rp0, (w * d + lane) * 16, tag, x);
-      if (p1) store_granule<SYS>(rp1, (w * d + lane) * 16, tag, x);
-    }
-    if (!head) {  // tails: both neighbours are this iteration's heads -> dual update now
-      double rp = 0.0;
-      if (inj) {
-        double mm = mu;
-        if (left >= 0) mm = mm - rho * (tl - x);
-        if (right >= 0) mm = mm + rho * (x - tr);
-        mu = mm;
-        if (left >= 0) rp = fma(tl - x, tl - x, rp);
-        if (right >= 0) rp = fma(x - tr, x - tr, rp);
-      }
-      if (a.rres) {
-        const double rs = wave_sum_f64(rp);
-        if (lane == 0 && it - 1 < a.max_iter) a.rres[(long)(it - 1) * n + w] = rs;
-      }
-    } else {
-      pending = 1;
-    }
+    publish_theta<SYS>(false, rth, push, ls, tag, x);  // (this kernel has no placement prologue)
+    // tails: both neighbours are this iteration's heads -> dual update now
+    if (!head) tail_dual_residual(a, ls, rho, it, x, tl, tr, mu);
+    else pending = 1;
     th = x;
     // -- f_n(theta^it) -> monitor; the same margins give the crew its next refresh point (this worker's
     // new iterate), built while the other group solves
@@ -584,22 +525,11 @@ __global__ void __launch_bounds__(NT) chain_persistent_newton_kernel(PersistArgs
     }
   }
   lds_store_rel(&nc.quit, 1);  // crew: quit (after its current refresh, if any)
-  if (inj) {
-    a.theta[(long)w * d + lane] = th;
-    a.mu[(long)li * d + lane] = mu;
-  }
+  store_state(a, ls, th, mu);
   if (lane == 0) {
     if (g.inner_iters) g.inner_iters[li] = used;
     if (nfail) atomicAdd(&a.ctl->inner_fail, nfail);  // read by the host after the launch
-    if (abort) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    }
+    post_outcome(a.ctl, abort, bid, stop_code, stop_iter, it);
   }
 }
 
@@ -692,19 +622,6 @@ __device__ __forceinline__ double wave_max_abs_dpp(double v) {
   return fmax(a, b);
 }
 
-// A pipeline hand-off post without the release fence: a wave's LDS operations are performed in order,
-// so a flag written after the ring data cannot become visible before it (the fence's s_waitcnt only
-// held the flag back by one LDS round trip). The compiler barrier keeps the data stores first.
-// GADMM_NEWTON_POSTFENCE=1 (PersistArgs::dbg bit 17) restores the fenced post (A/B).
-__device__ __forceinline__ void lds_post(int* p, int v, bool fenced) {
-  if (fenced || !GADMM_LDS_IN_ORDER) {  // fence-free only where in-order LDS is documented
-    lds_store_rel(p, v);
-    return;
-  }
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 // C (64 x 64 tile column cw) = A B over k < 4 QT (operands zero beyond d / m): acc[R][reg] =
 // C[16R + k4 + 4 reg][16 cw + c16]. The k loop is unrolled (a fixed 13 steps), so the operand LDS
 // reads of later steps are issued ahead of the MFMAs.
@@ -735,18 +652,6 @@ __device__ __forceinline__ void load_img(double (&M)[4][QT], const double* img) 
       M[r][t] = __longlong_as_double((long long)(((unsigned long long)g.y << 32) | g.x));
       if (t + 1 < QT) M[r][t + 1] = __longlong_as_double((long long)(((unsigned long long)g.w << 32) | g.z));
     }
-}
-
-// crew_sync with a deadline (the pipeline kernel ends even if a crew wave is gone)
-__device__ __forceinline__ void crew_sync_dl(int* cnt, int& gen, unsigned long long dl) {
-  gen += CREW;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  for (int spin = 0; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < gen; ++spin) {
-    __builtin_amdgcn_s_sleep(1);
-    if ((spin & 255) == 255 && __builtin_amdgcn_s_memrealtime() > dl) break;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // Coalesced write of a quad-LDS-layout image from a row-major LDS matrix M ([64][HS], element (row, col);
@@ -799,19 +704,19 @@ __device__ __attribute__((noinline)) void crew_refresh_rec(double* lds, const RL
     }
     for (int e = (int)threadIdx.x - 256; e < 64 * 8; e += 256) Hp[(e >> 3) * HS + QCOLS + (e & 7)] = 0.0;
   }
-  crew_sync_dl(cnt, gen, dl);
+  crew_sync<true>(cnt, gen, dl);
   if (tl && cw == 0 && lane == 0) tl[1] = (long long)__builtin_amdgcn_s_memrealtime();
   if (src) {
     // T = H X0 -> Hs;  U = X0 T;  X1 = 2 X0 - U -> Hp
     crew_mm(acc, cw, [&](int row, int kk) { return Hs[row * HS + kk]; }, [&](int kk, int col) { return Hp[kk * HS + col]; });
-    crew_sync_dl(cnt, gen, dl);
+    crew_sync<true>(cnt, gen, dl);
 #pragma unroll
     for (int R = 0; R < 4; ++R)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) Hs[(16 * R + k4 + 4 * reg) * HS + cc] = acc[R][reg];
-    crew_sync_dl(cnt, gen, dl);
+    crew_sync<true>(cnt, gen, dl);
     crew_mm(acc, cw, [&](int row, int kk) { return Hp[row * HS + kk]; }, [&](int kk, int col) { return Hs[kk * HS + col]; });
-    crew_sync_dl(cnt, gen, dl);  // every wave is done reading X0
+    crew_sync<true>(cnt, gen, dl);  // every wave is done reading X0
 #pragma unroll
     for (int R = 0; R < 4; ++R)
 #pragma unroll
@@ -820,69 +725,18 @@ __device__ __attribute__((noinline)) void crew_refresh_rec(double* lds, const RL
         Hp[row * HS + cc] = (row < d && cc < d) ? 2.0 * Hp[row * HS + cc] - acc[R][reg] : 0.0;
       }
   } else {
-    // in-place block Gauss-Jordan (the one-wave kernel's crew_refresh, same arithmetic)
     const int i = lane;
     double h[NCW];
 #pragma unroll
     for (int c = 0; c < NCW; ++c) h[c] = Hs[i * HS + cw + CREW * c];
-    const int nb = (d + 3) >> 2;
-    double* slabs = lds + L.slab;
-    for (int bb = 0; bb < nb; ++bb) {
-      const int p = 4 * bb;
-      double* slab = slabs + (bb & 1) * 256;
-      {
-        double hv = 0.0;
-#pragma unroll
-        for (int c = 0; c < NCW; ++c) hv = (c == bb) ? h[c] : hv;
-        slab[cw * 64 + i] = hv;
-      }
-      crew_sync_dl(cnt, gen, dl);
-      double P[4][4], Rr[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        Rr[q] = slab[q * 64 + i];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) P[q][r] = slab[q * 64 + p + r];
-      }
-      const bool pivrow = (i >> 2) == bb;
-      if (pivrow) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Rr[q] = (q == (i & 3)) ? 1.0 : 0.0;
-      }
-      const double a00 = P[0][0], a01 = P[1][0], a11 = P[1][1];
-      const double ia = rcp_nr(fma(a00, a11, -a01 * a01));
-      const double A00 = a11 * ia, A01 = -a01 * ia, A11 = a00 * ia;
-      const double b00 = P[2][0], b01 = P[3][0], b10 = P[2][1], b11 = P[3][1];
-      const double w00 = fma(A00, b00, A01 * b10), w01 = fma(A00, b01, A01 * b11);
-      const double w10 = fma(A01, b00, A11 * b10), w11 = fma(A01, b01, A11 * b11);
-      const double s00 = P[2][2] - fma(b00, w00, b10 * w10);
-      const double s01 = P[3][2] - fma(b00, w01, b10 * w11);
-      const double s11 = P[3][3] - fma(b01, w01, b11 * w11);
-      const double is = rcp_nr(fma(s00, s11, -s01 * s01));
-      const double y0 = fma(A00, Rr[0], A01 * Rr[1]), y1 = fma(A01, Rr[0], A11 * Rr[1]);
-      const double z2 = Rr[2] - fma(b00, y0, b10 * y1), z3 = Rr[3] - fma(b01, y0, b11 * y1);
-      const double l2 = fma(s11, z2, -s01 * z3) * is, l3 = fma(s00, z3, -s01 * z2) * is;
-      const double l0 = y0 - fma(w00, l2, w01 * l3), l1 = y1 - fma(w10, l2, w11 * l3);
-      const double lw = cw == 0 ? l0 : (cw == 1 ? l1 : (cw == 2 ? l2 : l3));
-#pragma unroll
-      for (int c = 0; c < NCW; ++c) {
-        const int j = cw + CREW * c;
-        const double tq = fma(l0, slab[j], fma(l1, slab[64 + j], fma(l2, slab[128 + j], l3 * slab[192 + j])));
-        const bool inK = c == bb;
-        const double sg = j < p ? -1.0 : 1.0;
-        double v;
-        if (inK) v = pivrow ? lw : -lw;
-        else v = pivrow ? sg * tq : fma(-sg, tq, h[c]);
-        h[c] = v;
-      }
-    }
+    crew_gauss_jordan(h, lds + L.slab, d, cw, [&] { crew_sync<true>(cnt, gen, dl); });
 #pragma unroll
     for (int c = 0; c < NCW; ++c) {
       const int col = cw + CREW * c;
       Hp[i * HS + col] = (i < d && col < d) ? h[c] : 0.0;
     }
   }
-  crew_sync_dl(cnt, gen, dl);
+  crew_sync<true>(cnt, gen, dl);
   if (tl && cw == 0 && lane == 0) tl[2] = (long long)__builtin_amdgcn_s_memrealtime();
   crew_copy_out(out, Hp, false);  // image 0: P
   // B = P X^T (rows: features, cols: samples) -> Hs row-major -> image 1, its transpose XP -> image 2
@@ -895,7 +749,7 @@ __device__ __attribute__((noinline)) void crew_refresh_rec(double* lds, const RL
       const int row = 16 * R + k4 + 4 * reg;
       Hs[row * HS + cc] = (row < d && cc < m) ? acc[R][reg] : 0.0;
     }
-  crew_sync_dl(cnt, gen, dl);  // B complete in Hs; every read of P in Hp done
+  crew_sync<true>(cnt, gen, dl);  // B complete in Hs; every read of P in Hp done
   crew_copy_out(out + QB, Hs, false);
   crew_copy_out(out + 2 * QB, Hs, true);
   // XB = X B (m x m) -> image 3
@@ -908,10 +762,10 @@ __device__ __attribute__((noinline)) void crew_refresh_rec(double* lds, const RL
       const int row = 16 * R + k4 + 4 * reg;
       Hp[row * HS + cc] = (row < m && cc < m) ? acc[R][reg] : 0.0;
     }
-  crew_sync_dl(cnt, gen, dl);
+  crew_sync<true>(cnt, gen, dl);
   crew_copy_out(out + 3 * QB, Hp, false);
   wg_release();  // the image's global stores complete before `ready` is posted
-  crew_sync_dl(cnt, gen, dl);
+  crew_sync<true>(cnt, gen, dl);
 }
 
 }  // namespace
@@ -1148,14 +1002,10 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
   }
 
   // ------------------------------------------------------------------ T (wave 1): iterate + protocol
-  u32x4* const p0 = a.push ? a.push[2 * bid] : nullptr;
-  u32x4* const p1 = a.push ? a.push[2 * bid + 1] : nullptr;
-  const __amdgpu_buffer_rsrc_t rp0 = rsrc_of(p0 ? (const void*)p0 : (const void*)a.thg);
-  const __amdgpu_buffer_rsrc_t rp1 = rsrc_of(p1 ? (const void*)p1 : (const void*)a.thg);
-  double th = inj ? a.theta[(long)w * d + lane] : 0.0;
-  double mu = inj ? a.mu[(long)li * d + lane] : 0.0;
-  double tl = (inj && left >= 0) ? a.theta[(long)left * d + lane] : 0.0;
-  double tr = (inj && right >= 0) ? a.theta[(long)right * d + lane] : 0.0;
+  const LaneSlot ls = lane_slot(sl, lane, d);
+  const ThetaPush push = push_targets(a, bid);
+  double th, mu, tl, tr;
+  load_state(a, ls, th, mu, tl, tr);
   int pending = a.pending_in;
   int stop_code = 0, stop_iter = 0, abort = 0, used = 0, nfail = 0;
   // a background refresh requested at iteration i is adopted at i + RLAG; one is requested when a solve
@@ -1185,49 +1035,27 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
   int it = a.start_iter;
   for (; !abort; ++it) {
     if (it > a.max_iter + a.lag) break;
-    const bool check = it - a.start_iter >= a.lag;
-    const int jdec = it - a.lag;
-    const bool need_nb = head ? it > a.start_iter : true;
-    const int jnb = head ? it - 1 : it;
-    const unsigned tnb = make_tag(a.epoch, jnb), tj = make_tag(a.epoch, jdec);
-    const int ra = need_nb ? left : -1, rb = need_nb ? right : -1;
-    bool decided = !check;
-    unsigned long long dv = 0;
-    int outcome = 0;
+    const NbWait nw = nb_wait(a, ls, head, it);
     const int kk_tl = it - a.start_iter;
     long long* tls = (a.timeline && kk_tl < 64) ? a.timeline + ((long)li * a.timeline_iters + 64 + kk_tl) * 8 : nullptr;
     long long t_nb = 0, t_dec = 0;  // (instrumented runs) when the neighbours' theta / the decision arrived
-    for (int spin = 0;; ++spin) {
-      bool nb = true;
-      if (inj) {
-        if (ra >= 0) nb &= load_granule<SYS>(rth, (ra * d + lane) * 16, tnb, &tl);
-        if (rb >= 0) nb &= load_granule<SYS>(rth, (rb * d + lane) * 16, tnb, &tr);
-      }
-      if (!decided) {
-        dv = __shfl(load_dec<SYS>(&a.decg[jdec % a.ring]), 0, 64);
-        decided = (unsigned)(dv >> 32) == tj;
-      }
-      if (tls) {
-        const long long now = (long long)__builtin_amdgcn_s_memrealtime();
-        if (!t_nb && __all(nb)) t_nb = now;
-        if (!t_dec && decided) t_dec = now;
-      }
-      if (decided && (unsigned)(dv & 0xffffffffu) != 0u) { outcome = 2; break; }
-      if (decided && __all(nb)) { outcome = 1; break; }
-      if ((spin & 7) == 7 && now_ticks() > deadline) { outcome = 3; break; }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    const int outcome = wait_decision<SYS, 1>(
+        a, it, a.start_iter, (it - a.lag) % a.ring, deadline, [&] { return load_neighbours<SYS>(rth, ls, nw, tl, tr); },
+        stop_code, stop_iter, [&](bool nb, bool decided) {
+          if (tls) {
+            const long long now = (long long)__builtin_amdgcn_s_memrealtime();
+            if (!t_nb && __all(nb)) t_nb = now;
+            if (!t_dec && decided) t_dec = now;
+          }
+        });
     if (outcome != 1) {
-      if (outcome == 2) {
-        stop_code = (int)(unsigned)(dv & 0xffffffffu);
-        stop_iter = jdec;
-      } else {
-        abort = 1;
-      }
+      if (outcome != 2) abort = 1;
       break;
     }
     double cv = 0.0, x = 0.0;
     if (inj) {
+      // head_lazy_dual (chain_worker.h) written out: through the helper the SYS instantiation takes 16
+      // more bytes of scratch per lane (profiles/worker_protocol)
       double mm = mu;
       if (head && pending) {
         if (left >= 0) mm = mm - rho * (tl - th);
@@ -1327,11 +1155,7 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
     }
     // publish theta^it first (the neighbours wait for it)
     const unsigned tag = make_tag(a.epoch, it);
-    if (inj) {
-      put_granule<SYS>(local, rth, (w * d + lane) * 16, tag, x);
-      if (p0) store_granule<SYS>(rp0, (w * d + lane) * 16, tag, x);
-      if (p1) store_granule<SYS>(rp1, (w * d + lane) * 16, tag, x);
-    }
+    publish_theta<SYS>(local, rth, push, ls, tag, x);
     // end of the solve: W takes f_n, the exact margins and (maybe) a background refresh request from here
     int req = -1, src = -1;
     if ((used > bg_steps || urgent) && pend < 0) {
@@ -1346,23 +1170,8 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
     pc[PC_ENEXT] = nx;
     pc[PC_EIT] = it;
     lds_store_rel(&pc[PC_END], sg);
-    if (!head) {
-      double rp = 0.0;
-      if (inj) {
-        double mm = mu;
-        if (left >= 0) mm = mm - rho * (tl - x);
-        if (right >= 0) mm = mm + rho * (x - tr);
-        mu = mm;
-        if (left >= 0) rp = fma(tl - x, tl - x, rp);
-        if (right >= 0) rp = fma(x - tr, x - tr, rp);
-      }
-      if (a.rres) {
-        const double rs = wave_sum_f64(rp);
-        if (lane == 0 && it - 1 < a.max_iter) a.rres[(long)(it - 1) * n + w] = rs;
-      }
-    } else {
-      pending = 1;
-    }
+    if (!head) tail_dual_residual(a, ls, rho, it, x, tl, tr, mu);
+    else pending = 1;
     th = x;
     if (!wait_ready(nx)) { abort = 1; break; }
     load_img(Mq, mimg + (long)(nx % RSLOTS) * RIMG);
@@ -1377,22 +1186,11 @@ __global__ void __launch_bounds__(RT) chain_persistent_newton_rec_kernel(Persist
   }
   lds_store_rel(&pc[PC_QUIT], 1);  // S, H, W leave
   lds_store_rel(&nc.quit, 1);      // the crew leaves after serving every request
-  if (inj) {
-    a.theta[(long)w * d + lane] = th;
-    a.mu[(long)li * d + lane] = mu;
-  }
+  store_state(a, ls, th, mu);
   if (lane == 0) {
     if (g.inner_iters) g.inner_iters[li] = used;
     if (nfail) atomicAdd(&a.ctl->inner_fail, nfail);  // read by the host after the launch
-    if (abort) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    }
+    post_outcome(a.ctl, abort, bid, stop_code, stop_iter, it);
   }
 }
 

@@ -23,6 +23,7 @@
 #include "gadmm_chain.h"
 #include "chain_device.h"
 #include "persist_device.h"
+#include "chain_worker.h"
 #include "persist_launch.h"
 #include "quad_gemv.h"
 #include "quant_device.h"
@@ -279,6 +280,7 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
   const int li = sl.li, w = sl.gid;
   const int left = sl.left, right = sl.right;
   const bool head = (pos % 2) == 0;
+  const LaneSlot ls = lane_slot(sl, lane, d);
   const int deg = (left >= 0) + (right >= 0);
   const double rho = a.rho;
   const int bits = a.q_bits, lp = q_log2_per(bits);
@@ -313,6 +315,9 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
     const double u = q_u01(a.q_seed, it, n, w, d, lane);  // this iteration's draw: ready before the wait ends
     // -- stop rule: the decision of iteration it - lag, polled in the same loop as the neighbours'
     // messages; a stop decision abandons the wait (a neighbour that saw it publishes no more)
+    // (wait_decision of persist_device.h written out, as are the dual steps of chain_worker.h below:
+    // through the helpers two more values of this kernel are parked in AGPRs, and the single solve
+    // measured 2 % slower, profiles/worker_protocol)
     const bool check = it - a.start_iter >= a.lag;
     const int jdec = it - a.lag;
     const bool need_nb = head ? it > a.start_iter : true;
@@ -412,22 +417,9 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
   }
 
   // write back the final state (plain stores; visible to the host after the kernel)
-  if (in) {
-    a.theta[(long)w * d + lane] = hat;
-    a.mu[(long)li * d + lane] = mu;
-    if (a.q_true) a.q_true[(long)li * d + lane] = th;
-  }
-  if (lane == 0) {
-    if (abort_lds) {
-      a.ctl->done = 4;
-    } else if (bid == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-      a.ctl->pending = 1;
-      a.ctl->monitored = stop_iter;
-    }
-  }
+  store_state(a, ls, hat, mu);
+  if (in && a.q_true) a.q_true[(long)li * d + lane] = th;
+  if (lane == 0) post_outcome(a.ctl, abort_lds, bid, stop_code, stop_iter, it);
 }
 
 template <int QT>

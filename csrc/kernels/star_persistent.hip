@@ -96,6 +96,8 @@ __global__ void __launch_bounds__(64 * HW) star_persistent_kernel(StarArgs a) {
     const unsigned tj = make_tag(a.epoch, jdec);
     bool decided = !check;
     unsigned long long dv = 0;
+    // The waits below are wait_decision (persist_device.h) written out: through the helper the QT = 13
+    // instantiations park four or five more values in AGPRs (profiles/worker_protocol)
     int outcome = 0;  // 1 go, 2 stop, 3 timeout
     if (!is_hub) {
       // theta_hub^{it-1} (the broadcast) and the decision of it - lag, polled together
@@ -244,14 +246,7 @@ __global__ void __launch_bounds__(64 * HW) star_persistent_kernel(StarArgs a) {
   }
   if (is_hub && in && wv > 0)  // each helper its own rows
     for (int q = wv - 1; q < hub; q += HW - 1) a.lam_hub[(long)q * d + lane] = lamS[q * 64 + lane];
-  if (lane == 0 && wv == 0) {
-    if (abort) a.ctl->done = 4;
-    else if (b == 0 && stop_code) {
-      a.ctl->done = stop_code;
-      a.ctl->conv_iter = stop_iter;
-      a.ctl->iter = it;
-    }
-  }
+  if (lane == 0 && wv == 0) post_outcome<false>(a.ctl, abort, b, stop_code, stop_iter, it);
 }
 
 static const void* star_variant(const StarArgs& a) {

@@ -119,7 +119,7 @@ class PersistArgs(ctypes.Structure):
 
 
 class LogiArgs(ctypes.Structure):
-    """Mirror of LogiArgs in csrc/kernels/chain_persistent_logistic.hip (persistent logistic GADMM)."""
+    """Mirror of LogiArgs in csrc/include/gadmm_logi.h (persistent logistic GADMM, inner-GD and Newton)."""
     _fields_ = [("X", c_void_p), ("Y", c_void_p), ("m", c_int), ("max_inner", c_int),
                 ("lam", c_double), ("step", c_double), ("inner_tol", c_double), ("inner_iters", c_void_p),
                 ("scratch", c_void_p)]

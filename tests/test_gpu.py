@@ -1353,8 +1353,8 @@ def test_persistent_state_at_stop_equals_graph(lin24, lin_obj0, log24, log_obj0,
 
 @pytest.mark.parametrize("kernel", ["logistic", "newton"])
 def test_postfence_stress(log24, log_obj0, kernel, monkeypatch):
-    """the fence-free LDS ring posts (chain_persistent_logistic.hip zr_post,
-    chain_persistent_newton.hip lds_post) rely on a wave's LDS operations being performed in order, which
+    """the fence-free LDS ring posts (lds_post of persist_device.h, in the two-wave
+    logistic kernel and the Newton pipeline kernel) rely on a wave's LDS operations being performed in order, which
     gfx950 provides (persist_device.h: GADMM_LDS_IN_ORDER). Stress: many back-to-back solves with the
     fence-free posts and with the fenced ones (GADMM_*_POSTFENCE=1) give ONE bit-identical objective trace
     and primal residual -- a post seen before its ring data would change a margin or a chord step."""
