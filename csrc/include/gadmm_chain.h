@@ -85,6 +85,15 @@ struct PhaseArgs {
   // optional K4 primal residual: every tail writes ||th_l - th||^2 + ||th - th_r||^2 of iteration it
   // (its two chain edges; each edge has exactly one tail end) into rres[(it - 1) * n_total + gid]
   double* rres;        // [max_iter][n_total] or null
+  // CQ-GADMM (censoring on top of Q-GADMM, chain_phase_linear_cq): the worker of iteration `it` keeps
+  // its candidate th_hat only if s = sum_i (cand_i - th_hat_i)^2 >= c_thr2[it]; otherwise its row keeps
+  // the old public model, q_msg[gid][0] holds Q_CENSORED and nothing else of the message is written.
+  // c_thr2 = null (a zeroed PhaseArgs): off, every kernel as without these fields. (In front of the
+  // Q-GADMM fields, which stay the last four of the struct: the offsets of q_true / q_msg / q_bits /
+  // q_seed moved by 16 bytes with this pair, here and in PersistArgs; a library built before them takes
+  // its arguments in the old layout, as tools/cqgadmm_bench.py re-marshals them.)
+  const double* c_thr2;         // [max_iter + lag + 2] squared thresholds by iteration, computed on the host
+  unsigned char* c_sent;        // [max_iter][n_total] 1: the worker transmitted in that iteration, 0: censored
   // Q-GADMM (csrc/kernels/chain_quant.hip, q_bits > 0): the theta table holds the PUBLIC models
   // th_hat; a worker quantizes the difference of its solve to its own row at q_bits per coordinate
   // (quant_device.h) and stores the updated th_hat. Optional outputs: the true iterates of the local
@@ -95,6 +104,10 @@ struct PhaseArgs {
   int q_bits;
   unsigned long long q_seed;
 };
+
+// Header word of a censored message (where the bits of R travel otherwise): the sign bit, which no
+// R = max |diff| >= 0 carries.
+constexpr unsigned long long Q_CENSORED = 0x8000000000000000ull;
 
 // Engine construction arguments (Python mirrors it in gadmm_amd/ops/native.py).
 struct EngineDesc {
@@ -211,6 +224,11 @@ struct PersistArgs {
   // with them at the re-chain), as int pairs [n_epochs][n][2]. Built on the host, so a re-chain
   // issues two independent table loads instead of a chain of three dependent ones.
   const int* ep_flush;
+  // CQ-GADMM in one launch (chain_persistent_cq_kernel): as PhaseArgs::c_thr2 / c_sent. The header
+  // granule is published EVERY iteration; a censored one carries Q_CENSORED and no code granule follows.
+  // (In front of the Q-GADMM fields, which stay the last four of the struct.)
+  const double* c_thr2;     // [max_iter + lag + 2], null: off (the Q kernels never read it)
+  unsigned char* c_sent;    // [max_iter][n]
   // Q-GADMM in one launch (csrc/kernels/chain_quant.hip: chain_persistent_q_kernel). qg: the packed
   // hand-off table, [n][G] tagged granules with G = ceil(d * q_bits / 64) + 1: granule 0 carries the
   // bits of R, granule 1 + k code word k. q_true: the true iterates at the end of the launch.

@@ -15,6 +15,19 @@
 //   chain_persistent_q_kernel  the whole solve in one launch, d <= 64, one wave per worker, static
 //                            chain, one GPU: the hand-off is the packed message itself.
 //   chain_persistent_q_sweep_kernel  up to 8 such solves in one launch, one per XCD (the same body).
+//
+// CQ-GADMM (censoring, Ben Issaid et al., arXiv:2009.06459, on top of the quantizer): a worker transmits
+// only when its public model would move by at least a geometrically decaying threshold,
+// s = sum_i (cand_i - th_hat_i)^2 >= c_thr2[it] (the table comes from the host: no powers here; s is
+// summed in the order of wave_sum_f64 / block_sum_f64, which the specification's sum64 reproduces; the
+// persistent kernel runs that butterfly through permlane swaps and DPP, wave_sum_f64_dpp).
+// A censored worker keeps its public model and its neighbours keep their copies. Every body below has a
+// compile-time CENS parameter; CENS = false are the Q kernels above, their code untouched, CENS = true
+// the entry points
+//   chain_phase_linear_cq, chain_persistent_cq_kernel, chain_persistent_cq_sweep_kernel
+// with their own launchers and capacity functions, instantiated in a translation unit of their own
+// (chain_cquant.hip includes this file). With an all-zero threshold table they compute Q-GADMM bit for
+// bit (a mixed sweep runs its uncensored members that way).
 #define GADMM_POLL_SLEEP 0  // one hand-off wait per phase on the critical path: poll back to back
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,12 +99,41 @@ __device__ __forceinline__ double block_max_f64(double v, double* scratch) {
   return t;
 }
 
+// One term of the censoring sum: (cand - hat)^2 as two separately rounded operations (the
+// specification's step and sq lines; no FMA may form with the additions of the sum that follows).
+__device__ __forceinline__ double c_step_sq(double cand, double hat) {
+#pragma clang fp contract(off)
+  const double step = cand - hat;
+  return step * step;
+}
+
+// wave_sum_f64's butterfly, x <- x + x[i ^ off] for off = 32, 16, 8, 4, 2, 1 (the specification's sum64;
+// an addition gives the same bits with its operands either way round), without its six ds_bpermute round
+// trips: the halves and the rows meet through the permlane swaps, lanes inside a row through DPP
+// (0x128 = row_ror:8 = i ^ 8; row_half_mirror then quad_perm [3,2,1,0] = i ^ 4; 0x4E, 0xB1 = i ^ 2, i ^ 1).
+// Every lane must be active.
+__device__ __forceinline__ double wave_sum_f64_dpp(double v) {
+  double a = v, b = v;
+  swap32_f64(a, b);  // a = (lanes 0-31 twice), b = (lanes 32-63 twice)
+  v = a + b;
+  a = v;
+  b = v;
+  swap16_f64(a, b);  // a = (r0, r0, r2, r2), b = (r1, r1, r3, r3)
+  v = a + b;
+  v = v + dpp_f64<0x128>(v);
+  v = v + dpp_f64<0x1B>(dpp_f64<0x141>(v));
+  v = v + dpp_f64<0x4E>(v);
+  v = v + dpp_f64<0xB1>(v);
+  return v;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// Graph engine: one GADMM phase with quantized publication.
-template <int NC>
-__global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
+// Graph engine: one GADMM phase with quantized publication. CENS: the censoring decision after the
+// quantize stage (chain_phase_linear_cq); false: the Q kernel.
+template <int NC, bool CENS>
+__device__ __forceinline__ void phase_linear_q_body(const PhaseArgs& a) {
   __shared__ __attribute__((aligned(16))) double sh_r[64 * NC];
   __shared__ __attribute__((aligned(16))) double sh_t[64 * NC];  // the true theta of this solve
   __shared__ __attribute__((aligned(16))) double sh_q[64 * NC];
@@ -143,8 +185,22 @@ __global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
     sh_c[j] = q;
     sh_h[j] = q_apply(hat, R, L, q);
   }
+  [[maybe_unused]] bool send = true;
+  if constexpr (CENS) {
+    // d <= 256 = NT: one coordinate per thread, so wave w holds the 64-chunk w of sq and block_sum_f64
+    // adds the chunks' butterfly sums in order (the specification's sum64)
+    const int j = threadIdx.x;
+    const double sq = j < d ? c_step_sq(sh_h[j], thw[j]) : 0.0;
+    const double s = block_sum_f64(sq, scratch);
+    send = s >= a.c_thr2[it];
+    if (!send && j < d) sh_h[j] = thw[j];  // censored: the old public row goes back (own entry, own write)
+    if (threadIdx.x == 0 && it - 1 < a.max_iter) a.c_sent[(long)(it - 1) * a.n_total + sl.gid] = send ? 1 : 0;
+  }
   __syncthreads();
-  if (a.q_msg) {  // the message as it would travel: the bits of R, then 64 / bits codes per word
+  if constexpr (CENS) {  // a censored message is its header alone
+    if (!send && a.q_msg && threadIdx.x == 0) a.q_msg[(long)sl.gid * (q_words(d, bits) + 1)] = Q_CENSORED;
+  }
+  if (CENS ? (send && a.q_msg) : (a.q_msg != nullptr)) {  // the message as it would travel: the bits of R, then 64 / bits codes per word
     const int lp = q_log2_per(bits), nw = q_words(d, bits);
     unsigned long long* msg = a.q_msg + (long)sl.gid * (nw + 1);
     if (threadIdx.x == 0) msg[0] = (unsigned long long)__double_as_longlong(R);
@@ -191,6 +247,18 @@ __global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
   }
 }
 
+template <int NC>
+__global__ void __launch_bounds__(NT) chain_phase_linear_q(PhaseArgs a) {
+  phase_linear_q_body<NC, false>(a);
+}
+
+template <int NC>
+__global__ void __launch_bounds__(NT) chain_phase_linear_cq(PhaseArgs a) {
+  phase_linear_q_body<NC, true>(a);
+}
+
+#ifndef GADMM_CQ_TU
+extern "C" int gadmm_chain_phase_cquant(const PhaseArgs* args, hipStream_t st);
 extern "C" int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st) {
   const PhaseArgs& a = *args;
   if (a.n_slots <= 0) return 0;
@@ -202,6 +270,7 @@ extern "C" int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st) {
     gadmm_set_error("chain_phase (quantized): q_bits must be 4, 8 or 16, got %d", a.q_bits);
     return -1;
   }
+  if (a.c_thr2) return gadmm_chain_phase_cquant(args, st);  // CQ-GADMM: the censored kernel (chain_cquant.hip)
   const int nc = (a.d + 63) / 64;
   switch (nc) {
     case 1: hipLaunchKernelGGL(chain_phase_linear_q<1>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
@@ -211,6 +280,23 @@ extern "C" int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st) {
   GADMM_CHECK(hipGetLastError());
   return 0;
 }
+#else
+extern "C" int gadmm_chain_phase_cquant(const PhaseArgs* args, hipStream_t st) {  // checked by gadmm_chain_phase_quant
+  const PhaseArgs& a = *args;
+  if (!a.c_thr2 || !a.c_sent) {
+    gadmm_set_error("chain_phase (censored): needs a threshold table (c_thr2) and a c_sent buffer");
+    return -1;
+  }
+  const int nc = (a.d + 63) / 64;
+  switch (nc) {
+    case 1: hipLaunchKernelGGL(chain_phase_linear_cq<1>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(chain_phase_linear_cq<2>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+    default: hipLaunchKernelGGL(chain_phase_linear_cq<4>, dim3(a.n_slots), dim3(NT), 0, st, a); break;
+  }
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Persistent single-launch Q-GADMM: static chain, one GPU, d <= 64, one wave per worker (+ the
@@ -229,6 +315,17 @@ extern "C" int gadmm_chain_phase_quant(const PhaseArgs* args, hipStream_t st) {
 // consumer publishes that message only after it has left the wait in which it read -- and kept in
 // registers -- the producer's message `it`. The granules are applied once, after the wait (a poll
 // that sees one neighbour's message early reloads it unchanged).
+//
+// CENS (chain_persistent_cq_kernel): the header granule is published EVERY iteration with that
+// iteration's tag; a censored header carries Q_CENSORED (the sign bit: no R >= 0 has it) and the worker
+// writes no code granule. A receiver leaves its wait when the header's tag matches AND either the header
+// says censored or its code granule's tag matches too: it never waits on a code granule of a censored
+// message and never applies one (those granules still hold an older tag and older codes); hl / hr then
+// stay as they are. The one-slot argument above still holds, because a header IS a message: a producer
+// cannot publish the header of iteration it + 1 before it has read the consumer's next header, which
+// the consumer publishes only after it has left the wait in which it read the producer's header `it`
+// (and, when that was not censored, the code granules of the same tag). A protocol mistake would end
+// at the deadline (outcome 3, done = 4), not in an endless spin.
 __device__ __forceinline__ void put_raw(bool local, __amdgpu_buffer_rsrc_t rs, int byte_off, unsigned tag,
                                         unsigned long long bits) {
   u32x4 g = {tag, (unsigned)(bits & 0xffffffffull), tag, (unsigned)(bits >> 32)};
@@ -246,7 +343,9 @@ __device__ __forceinline__ unsigned long long raw_bits(const u32x4& g) {
 // named by the slot's own arguments.
 // PA: PersistArgs (the kernel's own argument) or SweepArgs (a slot's entry, read through the constant
 // address space: wave-uniform scalar loads, like the kernarg segment).
-template <int QT, bool SWEEP, class PA>
+__device__ __forceinline__ bool hdr_censored(const u32x4& g) { return (g.w >> 31) != 0u; }
+
+template <int QT, bool SWEEP, bool CENS, class PA>
 __device__ __forceinline__ void q_persistent_body(const PA& a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int abort_lds;
@@ -313,6 +412,8 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
   for (;; ++it, rs = rs + 1 == a.ring ? 0 : rs + 1) {
     if (it > a.max_iter + a.lag) break;
     const double u = q_u01(a.q_seed, it, n, w, d, lane);  // this iteration's draw: ready before the wait ends
+    double thr2 = 0.0;
+    if constexpr (CENS) thr2 = a.c_thr2[it];  // wave-uniform, issued here: off the dependent chain after the GEMV
     // -- stop rule: the decision of iteration it - lag, polled in the same loop as the neighbours'
     // messages; a stop decision abandons the wait (a neighbour that saw it publishes no more)
     // (wait_decision of persist_device.h written out, as are the dual steps of chain_worker.h below:
@@ -337,12 +438,14 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
         if (ra >= 0) {
           gRa = load_raw<false>(rq, (ra * G) * 16);
           gWa = load_raw<false>(rq, (ra * G + my_g) * 16);
-          nb &= granule_ok(gRa, tnb) && granule_ok(gWa, tnb);
+          if constexpr (CENS) nb &= granule_ok(gRa, tnb) && (hdr_censored(gRa) || granule_ok(gWa, tnb));
+          else nb &= granule_ok(gRa, tnb) && granule_ok(gWa, tnb);
         }
         if (rb >= 0) {
           gRb = load_raw<false>(rq, (rb * G) * 16);
           gWb = load_raw<false>(rq, (rb * G + my_g) * 16);
-          nb &= granule_ok(gRb, tnb) && granule_ok(gWb, tnb);
+          if constexpr (CENS) nb &= granule_ok(gRb, tnb) && (hdr_censored(gRb) || granule_ok(gWb, tnb));
+          else nb &= granule_ok(gRb, tnb) && granule_ok(gWb, tnb);
         }
       }
       if (!decided) {
@@ -365,9 +468,10 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
     lds_barrier();
     if (abort_lds || stop_lds) break;
     // -- the neighbours' messages, consumed once: their public models move by the dequantized step
-    if (in && ra >= 0)
+    // (CENS: a censored message moves nothing, and its code granule is an older one: never applied)
+    if (in && ra >= 0 && !(CENS && hdr_censored(gRa)))
       hl = q_apply(hl, __longlong_as_double((long long)raw_bits(gRa)), L, (unsigned)(raw_bits(gWa) >> my_sh) & qmask);
-    if (in && rb >= 0)
+    if (in && rb >= 0 && !(CENS && hdr_censored(gRb)))
       hr = q_apply(hr, __longlong_as_double((long long)raw_bits(gRb)), L, (unsigned)(raw_bits(gWb) >> my_sh) & qmask);
     if (head && pending) {  // lazy end-of-iteration dual (reference order), on public models
       double m = mu;
@@ -387,11 +491,22 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
     const double diff = in ? tn - hat : 0.0;
     const double R = wave_max_f64(fabs(diff));
     const unsigned q = in ? q_code(diff, R, L, u) : 0u;
-    const double hat_new = in ? q_apply(hat, R, L, q) : 0.0;
+    double hat_new = in ? q_apply(hat, R, L, q) : 0.0;
     const unsigned long long word = group_or_u64((unsigned long long)q << my_sh, lp);  // the word of this lane's group
     const unsigned tag = make_tag(a.epoch, it);
-    if (in && (lane & ((1 << lp) - 1)) == 0) put_raw(local, rq, (w * G + my_g) * 16, tag, word);
-    if (lane == 0) put_raw(local, rq, (w * G) * 16, tag, (unsigned long long)__double_as_longlong(R));
+    if constexpr (CENS) {
+      // the censoring decision: would the public model move by at least this iteration's threshold?
+      const bool send = wave_sum_f64_dpp(in ? c_step_sq(hat_new, hat) : 0.0) >= thr2;
+      if (send && in && (lane & ((1 << lp) - 1)) == 0) put_raw(local, rq, (w * G + my_g) * 16, tag, word);
+      if (lane == 0) {  // the header travels every iteration: R, or the censored notice
+        put_raw(local, rq, (w * G) * 16, tag, send ? (unsigned long long)__double_as_longlong(R) : Q_CENSORED);
+        if (it - 1 < a.max_iter) a.c_sent[(long)(it - 1) * n + w] = send ? 1 : 0;
+      }
+      if (!send) hat_new = hat;
+    } else {
+      if (in && (lane & ((1 << lp) - 1)) == 0) put_raw(local, rq, (w * G + my_g) * 16, tag, word);
+      if (lane == 0) put_raw(local, rq, (w * G) * 16, tag, (unsigned long long)__double_as_longlong(R));
+    }
     if (!head) {  // tails: both neighbours are this iteration's heads -> dual update now
       double m = mu;
       if (left >= 0) m = m - rho * (hl - hat_new);
@@ -424,7 +539,12 @@ __device__ __forceinline__ void q_persistent_body(const PA& a) {
 
 template <int QT>
 __global__ void __launch_bounds__(64) chain_persistent_q_kernel(PersistArgs a) {
-  q_persistent_body<QT, false>(a);
+  q_persistent_body<QT, false, false>(a);
+}
+
+template <int QT>
+__global__ void __launch_bounds__(64) chain_persistent_cq_kernel(PersistArgs a) {
+  q_persistent_body<QT, false, true>(a);
 }
 
 // Up to 8 independent Q-GADMM solves in one launch, one per XCD: slot j = blockIdx.x & 7 runs solve j
@@ -439,8 +559,34 @@ template <int QT>
 __global__ void __launch_bounds__(64) chain_persistent_q_sweep_kernel(const PersistArgs* __restrict__ batch, int nb) {
   const int j = (int)(blockIdx.x & 7u);
   if (j >= nb) return;
-  q_persistent_body<QT, true>(*(const SweepArgs*)(batch + j));
+  q_persistent_body<QT, true, false>(*(const SweepArgs*)(batch + j));
 }
+
+// The same launch shape on the censored body: a batch that mixes censored and uncensored members runs
+// here, the uncensored ones under an all-zero threshold table (every worker always sends: Q-GADMM bit
+// for bit); a batch without a censored member keeps the kernel above.
+template <int QT>
+__global__ void __launch_bounds__(64) chain_persistent_cq_sweep_kernel(const PersistArgs* __restrict__ batch, int nb) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  q_persistent_body<QT, true, true>(*(const SweepArgs*)(batch + j));
+}
+
+// The launchers below are compiled once per translation unit: here for the Q kernels, and in
+// chain_cquant.hip (which includes this file with GADMM_CQ_TU defined) for the censored ones. Two units,
+// so that the Q kernels are compiled exactly as before the censored instantiations existed.
+#ifdef GADMM_CQ_TU
+#define Q_KERNEL chain_persistent_cq_kernel
+#define Q_SWEEP_KERNEL chain_persistent_cq_sweep_kernel
+#define Q_NAME "CQ"
+constexpr bool CENS_TU = true;
+#else
+#define Q_KERNEL chain_persistent_q_kernel
+#define Q_SWEEP_KERNEL chain_persistent_q_sweep_kernel
+#define Q_NAME "Q"
+constexpr bool CENS_TU = false;
+#endif
+#define Q_SWEEP_CAPACITY 8
 
 namespace {
 
@@ -453,7 +599,7 @@ QVariant pick_q_variant(const PersistArgs& a) {
   QVariant v;
   if (a.d < 1 || a.d > 64) return v;
   // register kernel: QT = 13 covers d <= 52, 16 covers d <= 64 (as chain_persistent_kernel)
-  v.fn = a.d <= 52 ? (const void*)chain_persistent_q_kernel<13> : (const void*)chain_persistent_q_kernel<16>;
+  v.fn = a.d <= 52 ? (const void*)Q_KERNEL<13> : (const void*)Q_KERNEL<16>;
   const size_t mon = (size_t)a.n * 8, stg = (size_t)QSTAGE * 8;
   v.shm = mon > stg ? mon : stg;
   return v;
@@ -470,6 +616,10 @@ bool q_entry_ok(const PersistArgs& a, const char* who) {
     gadmm_set_error("%s: q_bits must be 4, 8 or 16, got %d", who, a.q_bits);
     return false;
   }
+  if (CENS_TU && (!a.c_thr2 || !a.c_sent)) {
+    gadmm_set_error("%s: the censored kernel needs a threshold table (c_thr2) and a c_sent buffer", who);
+    return false;
+  }
   if (!a.qg || !a.slots || !a.pos || !a.objg || !a.decg || !a.dec_push || !a.theta || !a.mu || !a.Minv || !a.A ||
       !a.ctl) {
     gadmm_set_error("%s: a required buffer is null", who);
@@ -483,8 +633,103 @@ bool q_entry_ok(const PersistArgs& a, const char* who) {
   return true;
 }
 
+// nb <= 8 independent Q-GADMM solves (one GPU each, one QT class: d <= 52 or 53..64) in ONE launch, solve j
+// on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its own ctl,
+// trace, theta, mu, true theta, message table, objective / decision rings and xchk (per-XCD L2s are not
+// coherent: two slots never write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each,
+// owned by the caller and left alone until the stream has drained; the entries go up in one async copy
+// ahead of the kernel. -1: refused before any HIP call; -2: the workgroups cannot all be resident.
+int q_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st) {
+  if (nb < 1 || nb > Q_SWEEP_CAPACITY) {
+    gadmm_set_error("persistent " Q_NAME " sweep: %d solves, one launch takes 1..%d", nb,
+                    Q_SWEEP_CAPACITY);
+    return -1;
+  }
+  if (!batch || !host_stage || !dev_stage) {
+    gadmm_set_error("persistent " Q_NAME " sweep: null batch or staging buffer");
+    return -1;
+  }
+  for (int j = 1; j < nb; ++j)
+    if ((batch[j].d <= 52) != (batch[0].d <= 52)) {
+      gadmm_set_error("persistent " Q_NAME " sweep: solves of different register classes (d = %d and %d; d <= 52 or 53..64)",
+                      batch[0].d, batch[j].d);
+      return -1;
+    }
+  int blocks[8], max_blocks = 0, sum_blocks = 0;
+  size_t shm = 0;
+  for (int j = 0; j < nb; ++j) {
+    const PersistArgs& a = batch[j];
+    char who[48];
+    snprintf(who, sizeof(who), "persistent " Q_NAME " sweep: solve %d", j);
+    if (!q_entry_ok(a, who)) return -1;
+    if (!a.trace || !a.b || !a.yy) {  // (the single launch leaves these to its one caller)
+      gadmm_set_error("%s: a required buffer is null", who);
+      return -1;
+    }
+    if (!a.xchk) {
+      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
+      return -1;
+    }
+    blocks[j] = a.n_local + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i) {
+      const PersistArgs& o = batch[i];
+      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.qg == a.qg ||
+          (a.q_true && o.q_true == a.q_true) || o.objg == a.objg || o.decg == a.decg || o.dec_push == a.dec_push ||
+          o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres) ||
+          (CENS_TU && o.c_sent == a.c_sent)) {
+        gadmm_set_error("persistent " Q_NAME " sweep: solves %d and %d share a buffer that both write", i, j);
+        return -1;
+      }
+    }
+    // the ranges gadmm_persist_launch checks for the single launch
+    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+      gadmm_set_error("%s: ring/lag/tag range", who);
+      return -1;
+    }
+    sum_blocks += blocks[j];
+    if (blocks[j] > max_blocks) max_blocks = blocks[j];
+    const size_t need = pick_q_variant(a).shm;
+    if (need > shm) shm = need;
+  }
+  const void* fn = batch[0].d <= 52 ? (const void*)Q_SWEEP_KERNEL<13> : (const void*)Q_SWEEP_KERNEL<16>;
+  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
+  // its 8-strided blocks are dealt to
+  const long cap = gadmm_resident_capacity(fn, 64, shm);
+  const long cus_xcd = gadmm_cu_count() / 8;
+  if (sum_blocks > cap) {
+    gadmm_set_error("persistent " Q_NAME " sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
+    return -2;
+  }
+  for (int j = 0; j < nb; ++j)
+    if (blocks[j] > cus_xcd) {
+      gadmm_set_error("persistent " Q_NAME " sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
+      return -2;
+    }
+  int xenv = -1;
+  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
+  for (int j = 0; j < nb; ++j) {
+    PersistArgs& ka = host_stage[j];
+    ka = batch[j];
+    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
+    const int x = xenv >= 0 ? xenv : ka.xcd;
+    ka.xcd = x >= 2 ? 2 : 1;
+    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
+  const PersistArgs* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb};
+  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64), kargs, shm, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
+#ifndef GADMM_CQ_TU
 extern "C" {
 
 // ABI self-description of the Q-GADMM fields appended to PhaseArgs / PersistArgs (ctypes mirrors in
@@ -517,101 +762,52 @@ int gadmm_chain_persistent_q_launch(const PersistArgs* args, hipStream_t st) {
 }
 
 // Solves one launch of chain_persistent_q_sweep_kernel can run side by side (one per XCD).
-int gadmm_chain_persistent_q_sweep_capacity() { return 8; }
+int gadmm_chain_persistent_q_sweep_capacity() { return Q_SWEEP_CAPACITY; }
 
-// nb <= 8 independent Q-GADMM solves (one GPU each, one QT class: d <= 52 or 53..64) in ONE launch, solve j
-// on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its own ctl,
-// trace, theta, mu, true theta, message table, objective / decision rings and xchk (per-XCD L2s are not
-// coherent: two slots never write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each,
-// owned by the caller and left alone until the stream has drained; the entries go up in one async copy
-// ahead of the kernel. -1: refused before any HIP call; -2: the workgroups cannot all be resident.
+// The sweep launch (q_sweep_launch above) on chain_persistent_q_sweep_kernel.
 int gadmm_chain_persistent_q_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage,
                                           PersistArgs* dev_stage, hipStream_t st) {
-  if (nb < 1 || nb > gadmm_chain_persistent_q_sweep_capacity()) {
-    gadmm_set_error("persistent Q sweep: %d solves, one launch takes 1..%d", nb,
-                    gadmm_chain_persistent_q_sweep_capacity());
-    return -1;
-  }
-  if (!batch || !host_stage || !dev_stage) {
-    gadmm_set_error("persistent Q sweep: null batch or staging buffer");
-    return -1;
-  }
-  for (int j = 1; j < nb; ++j)
-    if ((batch[j].d <= 52) != (batch[0].d <= 52)) {
-      gadmm_set_error("persistent Q sweep: solves of different register classes (d = %d and %d; d <= 52 or 53..64)",
-                      batch[0].d, batch[j].d);
-      return -1;
-    }
-  int blocks[8], max_blocks = 0, sum_blocks = 0;
-  size_t shm = 0;
-  for (int j = 0; j < nb; ++j) {
-    const PersistArgs& a = batch[j];
-    char who[48];
-    snprintf(who, sizeof(who), "persistent Q sweep: solve %d", j);
-    if (!q_entry_ok(a, who)) return -1;
-    if (!a.trace || !a.b || !a.yy) {  // (the single launch leaves these to its one caller)
-      gadmm_set_error("%s: a required buffer is null", who);
-      return -1;
-    }
-    if (!a.xchk) {
-      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
-      return -1;
-    }
-    blocks[j] = a.n_local + 1;
-    if (blocks[j] > XCHK) {
-      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
-      return -1;
-    }
-    for (int i = 0; i < j; ++i) {
-      const PersistArgs& o = batch[i];
-      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.qg == a.qg ||
-          (a.q_true && o.q_true == a.q_true) || o.objg == a.objg || o.decg == a.decg || o.dec_push == a.dec_push ||
-          o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres)) {
-        gadmm_set_error("persistent Q sweep: solves %d and %d share a buffer that both write", i, j);
-        return -1;
-      }
-    }
-    // the ranges gadmm_persist_launch checks for the single launch
-    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-      gadmm_set_error("%s: ring/lag/tag range", who);
-      return -1;
-    }
-    sum_blocks += blocks[j];
-    if (blocks[j] > max_blocks) max_blocks = blocks[j];
-    const size_t need = pick_q_variant(a).shm;
-    if (need > shm) shm = need;
-  }
-  const void* fn = batch[0].d <= 52 ? (const void*)chain_persistent_q_sweep_kernel<13>
-                                    : (const void*)chain_persistent_q_sweep_kernel<16>;
-  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
-  // its 8-strided blocks are dealt to
-  const long cap = gadmm_resident_capacity(fn, 64, shm);
-  const long cus_xcd = gadmm_cu_count() / 8;
-  if (sum_blocks > cap) {
-    gadmm_set_error("persistent Q sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
-    return -2;
-  }
-  for (int j = 0; j < nb; ++j)
-    if (blocks[j] > cus_xcd) {
-      gadmm_set_error("persistent Q sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
-      return -2;
-    }
-  int xenv = -1;
-  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
-  for (int j = 0; j < nb; ++j) {
-    PersistArgs& ka = host_stage[j];
-    ka = batch[j];
-    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
-    const int x = xenv >= 0 ? xenv : ka.xcd;
-    ka.xcd = x >= 2 ? 2 : 1;
-    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
-  }
-  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
-  const PersistArgs* dbatch = dev_stage;
-  void* kargs[] = {&dbatch, &nb};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64), kargs, shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return q_sweep_launch(batch, nb, host_stage, dev_stage, st);
 }
 
 }  // extern "C"
+#else
+extern "C" {
+
+// ABI self-description of the CQ-GADMM fields of PhaseArgs / PersistArgs (they sit directly in front of
+// the Q-GADMM fields; ctypes mirrors in gadmm_amd/ops/native.py).
+int gadmm_censor_abi_layout(long long* out, int n) {
+  long long v[] = {(long long)offsetof(PhaseArgs, c_thr2),   (long long)offsetof(PhaseArgs, c_sent),
+                   (long long)sizeof(PhaseArgs),             (long long)offsetof(PersistArgs, c_thr2),
+                   (long long)offsetof(PersistArgs, c_sent), (long long)sizeof(PersistArgs)};
+  const int k = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < k; ++i) out[i] = v[i];
+  return k;
+}
+
+// Workgroups the persistent CQ kernel for `args` can keep resident (0: shape not eligible).
+long gadmm_chain_persistent_cq_capacity(const PersistArgs* args) {
+  const QVariant v = pick_q_variant(*args);
+  if (!v.fn || v.shm > 65536) return 0;
+  return gadmm_resident_capacity(v.fn, 64, v.shm);
+}
+
+// CQ-GADMM, the whole solve in one launch: as gadmm_chain_persistent_q_launch, plus c_thr2 / c_sent.
+int gadmm_chain_persistent_cq_launch(const PersistArgs* args, hipStream_t st) {
+  const PersistArgs& a = *args;
+  if (!q_entry_ok(a, "persistent CQ kernel")) return -1;
+  const QVariant v = pick_q_variant(a);
+  PersistArgs ka = a;
+  void* kargs[] = {&ka};
+  return gadmm_persist_launch({v.fn, 64, v.shm, a.n_local + 1, "persistent CQ kernel", true}, &ka, kargs, st);
+}
+
+// The sweep launch on chain_persistent_cq_sweep_kernel: every entry names a threshold table (all zero
+// for an uncensored member, which then computes Q-GADMM bit for bit) and its own c_sent buffer.
+int gadmm_chain_persistent_cq_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage,
+                                           PersistArgs* dev_stage, hipStream_t st) {
+  return q_sweep_launch(batch, nb, host_stage, dev_stage, st);
+}
+
+}  // extern "C"
+#endif

@@ -12,6 +12,7 @@ from __future__ import annotations
 import argparse
 import glob
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -48,6 +49,9 @@ def _obj_for(src: str) -> str:
 def _compile(src: str, force: bool) -> str:
     obj = _obj_for(src)
     newest_dep = max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in headers()])
+    with open(src) as f:  # a unit that instantiates another one's kernels (#include "x.hip") follows that file too
+        for inc in re.findall(r'^#include "([^"]+\.hip)"', f.read(), flags=re.M):
+            newest_dep = max(newest_dep, os.path.getmtime(os.path.join(os.path.dirname(src), inc)))
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= newest_dep:
         return obj
     cmd = [hipcc(), "-c", src, "-o", obj, "-fPIC", "-O3", "-std=c++17", "-I", os.path.join(CSRC, "include"),

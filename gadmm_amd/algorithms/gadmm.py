@@ -49,7 +49,8 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
                inner_tol: float = 1e-4, cost_quirk: bool = True, backend: str = "auto",
                name: str = "GADMM", record_theta: bool = False, engine_opts: Optional[dict] = None,
                state=None, check_exchange: Optional[bool] = None,
-               failures: Optional[dict] = None, quantize: Optional[Sequence] = None) -> RunResult:
+               failures: Optional[dict] = None, quantize: Optional[Sequence] = None,
+               censor: Optional[Sequence] = None) -> RunResult:
     """Run one chain-ADMM solve on this rank. ``model`` holds this rank's shards (local order =
     ``local_ids``). ``schedule`` (D-GADMM) overrides ``path``; ``cost_quirk`` reproduces the
     reference's per-head-worker accumulation of ``sum(pathCost)`` (dynamic_group_ADMM_closedForm.m:51-55).
@@ -65,13 +66,19 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
     ``quantize``: ``(bits, seed)`` - Q-GADMM (algorithms/quantize.py): every worker publishes a
     stochastically quantized difference to its last transmitted model, ``bits`` in {4, 8, 16} per
     coordinate; the chain runs on those public models, the objective and the stop rule on the true
-    iterates (``_chain_admm_quantized`` documents the dispatch). None: every path as without it."""
+    iterates (``_chain_admm_quantized`` documents the dispatch). None: every path as without it.
+    ``censor``: ``(tau0, xi)`` with ``quantize`` - CQ-GADMM (arXiv:2009.06459; the specification is in
+    algorithms/quantize.py): at iteration k a worker transmits only if its public model would move by
+    at least ``tau0 * xi^k``, else its neighbours keep the model they have. ``tau0 = 0`` is Q-GADMM
+    bit for bit. Censoring without quantization is not offered (ValueError)."""
 
     comm = comm if comm is not None else LocalComm()
+    if censor is not None and quantize is None:
+        raise ValueError("censor=(tau0, xi) needs quantize=(bits, seed): censoring without quantization is not offered")
     if quantize is not None:
         return _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, path,
                                      schedule, local_solver, step, max_inner, inner_tol, cost_quirk, backend, name,
-                                     record_theta, engine_opts, state, check_exchange, failures, quantize)
+                                     record_theta, engine_opts, state, check_exchange, failures, quantize, censor)
     if check_exchange is None:
         check_exchange = getenv("GADMM_CHECK_EXCHANGE", "0") == "1"
     placement = placement if placement is not None else Placement.contiguous(n_total, comm.nranks)
@@ -243,7 +250,7 @@ def chain_admm_sweep(model, local_ids: Sequence[int], n_total: int, rhos: Sequen
 
 def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
                       local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
-                      check_exchange=False, failures=None, quantize=None):
+                      check_exchange=False, failures=None, quantize=None, censor=None):
     rank = comm.rank
     checker = None
     if check_exchange:
@@ -272,6 +279,12 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
         from . import quantize as Q
         q_bits, q_seed = Q.check_bits(quantize[0]), int(quantize[1])
         th_true = theta.index_select(0, torch.tensor(local_ids, dtype=torch.long, device=dev)).clone()
+    thr2 = None
+    sent_rows: List[np.ndarray] = []   # per iteration: who transmitted (this rank's workers; made global at the end)
+    alive_rows: List[np.ndarray] = []  # per iteration: who took part (``failures``: a dropped worker is not censored)
+    min_cmargin = float("inf")
+    if censor is not None:  # CQ-GADMM: thr2[it], the squared threshold of iteration it
+        thr2 = Q.censor_thresholds(censor[0], censor[1], max_iter)
     stop = Stopper(obj0, tol, max_iter)
     snap = comm.stats.snapshot()
     alive = np.ones(n_total, dtype=bool)
@@ -301,6 +314,9 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
         n_heads = (n_total + 1) // 2
         cc += float(np.sum(schedule.cost)) * (n_heads if cost_quirk else 1)
         com_cost.append(cc)
+        if thr2 is not None:
+            sent_rows.append(np.zeros(n_total, dtype=bool))
+            alive_rows.append(alive.copy())
         for slots, xchg in ((plan.head, plan.xchg_head), (plan.tail, plan.xchg_tail)):
             if slots:
                 li = torch.tensor([s.li for s in slots], dtype=torch.long, device=dev)
@@ -327,9 +343,14 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
                 gix = torch.tensor(gid, dtype=torch.long, device=dev)
                 if q_bits:
                     th_true[li] = new
-                    _, _, hat, mg = Q.quantize_rows(new.cpu().numpy(), theta.index_select(0, gix).cpu().numpy(),
-                                                    q_bits, Q.u01(q_seed, it, n_total, gid, d))
+                    old = theta.index_select(0, gix).cpu().numpy()
+                    _, _, hat, mg = Q.quantize_rows(new.cpu().numpy(), old, q_bits, Q.u01(q_seed, it, n_total, gid, d))
                     min_margin = min(min_margin, mg)
+                    if thr2 is not None:  # a censored worker keeps its public model: nothing travels
+                        send, _, cm = Q.censor_rows(hat, old, thr2[it])
+                        hat = np.where(send[:, None], hat, old)
+                        sent_rows[-1][gid] = send
+                        min_cmargin = min(min_cmargin, cm)
                     new = torch.from_numpy(hat).to(dev)
                 theta[gix] = new
             comm.exchange_rows(theta, xchg)
@@ -377,7 +398,23 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
                     primal_res=np.asarray(primal))
     res.extra["state"] = (theta, mu, (iters if converged else start - 1 + n_it) + 1)
     if q_bits:
-        _quant_accounting(res, q_bits, q_seed, n_total, d, start)
+        sent = active = None
+        if thr2 is not None:
+            sent = np.asarray(sent_rows, dtype=bool).reshape(-1, n_total)[:n_it]
+            active = np.asarray(alive_rows, dtype=bool).reshape(-1, n_total)[:n_it]
+            if comm.nranks > 1:
+                # every rank decided for its own workers only (and all stopped at the same iteration): one
+                # all-reduce makes the trace, and with it every figure of the accounting, the same on all
+                # ranks and equal to the one-rank run's; the smallest margin likewise
+                t = torch.from_numpy(sent.astype(np.float64)).to(dev)
+                comm.allreduce_sum(t)
+                nb = t.numel() * t.element_size()
+                comm.stats.coll_bytes -= nb  # diagnostics, not algorithm traffic
+                comm.stats.monitor_bytes += nb
+                sent = t.cpu().numpy() > 0.5
+                min_cmargin = -comm.allreduce_max_scalar(-min_cmargin)
+            res.extra["min_censor_margin"] = min_cmargin
+        _quant_accounting(res, q_bits, q_seed, n_total, d, start, sent=sent, censor=censor, active=active)
         res.extra["min_flip_margin"] = min_margin
         res.extra["theta_true"] = th_true
     if record_theta:
@@ -385,19 +422,37 @@ def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm,
     return res
 
 
-def _quant_accounting(res: RunResult, bits: int, seed: int, n_total: int, d: int, start: int = 1) -> None:
+def _quant_accounting(res: RunResult, bits: int, seed: int, n_total: int, d: int, start: int = 1,
+                      sent: Optional[np.ndarray] = None, censor=None, active: Optional[np.ndarray] = None) -> None:
     """Q-GADMM communication of a result: ``comm_units`` in equivalent full-precision transmissions
-    (a message is ``bits * d + 64`` payload bits instead of ``64 * d``) and the totals in ``extra``."""
+    (a message is ``bits * d + 64`` payload bits instead of ``64 * d``) and the totals in ``extra``.
+    ``sent`` (CQ-GADMM): the (iterations, N) bool trace of who transmitted; ``comm_units[k]`` is then
+    the cumulative number of transmissions up to iteration k + 1 in the same unit (the paper's
+    convention: a censored worker sends nothing), and ``extra`` carries ``transmissions``, ``censored``,
+    ``sent_trace`` and ``payload_bits = transmissions * payload_bits(d, bits)``. Rows of ``sent`` past
+    the result's trace (the persistent kernel's ``lag`` iterations past the stop) are dropped.
+    ``active`` (same shape, default all): who took part in each iteration -- a worker dropped by
+    ``failures=`` neither sends nor counts as censored. A resumed run (``state=``, ``start > 1``) counts
+    the transmissions of ITS iterations only: what was sent before the checkpoint is not known here, so
+    its ``comm_units`` start from 0 where Q-GADMM's continue from ``(start - 1) * N`` messages."""
     from .quantize import payload_bits
     pb = payload_bits(d, bits)
     n_it = len(res.obj)
-    res.comm_units = np.arange(start, start + n_it, dtype=np.float64) * n_total * pb / (64.0 * d)
-    res.extra.update(q_bits=int(bits), q_seed=int(seed), payload_bits=int(res.iters) * n_total * pb)
+    if sent is None:
+        res.comm_units = np.arange(start, start + n_it, dtype=np.float64) * n_total * pb / (64.0 * d)
+        res.extra.update(q_bits=int(bits), q_seed=int(seed), payload_bits=int(res.iters) * n_total * pb)
+        return
+    sent = np.asarray(sent, dtype=bool).reshape(-1, n_total)[:n_it]
+    n_active = int(sent.size) if active is None else int(np.asarray(active, dtype=bool).reshape(-1, n_total)[:n_it].sum())
+    tx = int(sent.sum())
+    res.comm_units = np.cumsum(sent.sum(axis=1), dtype=np.float64) * pb / (64.0 * d)
+    res.extra.update(q_bits=int(bits), q_seed=int(seed), payload_bits=tx * pb, transmissions=tx,
+                     censored=n_active - tx, sent_trace=sent, censor=(float(censor[0]), float(censor[1])))
 
 
 def _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, path, schedule,
                           local_solver, step, max_inner, inner_tol, cost_quirk, backend, name, record_theta,
-                          engine_opts, state, check_exchange, failures, quantize) -> RunResult:
+                          engine_opts, state, check_exchange, failures, quantize, censor=None) -> RunResult:
     """Q-GADMM dispatch. Native (HIP device, ``backend`` auto / native): one rank, a static chain,
     the linear model with closed-form solves and every worker local -- the persistent Q kernel at
     d <= 64 (one launch; a residency refusal or a hand-off timeout falls back to the graph engine),
@@ -405,11 +460,15 @@ def _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, c
     exchange checker, a dynamic schedule, several ranks, logistic models, d > 256, CPU tensors -- runs
     the torch path, with the reason in ``extra['quant_fallback']``. Both compute the specification of
     algorithms/quantize.py; they differ in how the local solve rounds, which a quantizer can amplify
-    once a flip margin (``extra['min_flip_margin']`` of the torch path) is down at that level."""
+    once a flip margin (``extra['min_flip_margin']`` of the torch path) is down at that level.
+    ``censor`` (CQ-GADMM) takes the same dispatch on the censored kernels of chain_quant.hip and the same
+    fallback reasons; there the censor margin (``extra['min_censor_margin']``) bounds a comparison too."""
     from . import quantize as Q
     if len(quantize) != 2:
         raise ValueError("quantize: (bits, seed)")
     bits, seed = Q.check_bits(quantize[0]), int(quantize[1])
+    if censor is not None:
+        censor = Q.check_censor(censor)
     if check_exchange is None:
         check_exchange = getenv("GADMM_CHECK_EXCHANGE", "0") == "1"
     placement = placement if placement is not None else Placement.contiguous(n_total, comm.nranks)
@@ -446,7 +505,7 @@ def _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, c
         if native.available():
             with roctx_range("%s native-Q N=%d b=%d" % (name, n_total, bits)):
                 return _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter, placement,
-                                                schedule, cost_quirk, name, engine_opts or {}, bits, seed)
+                                                schedule, cost_quirk, name, engine_opts or {}, bits, seed, censor)
         if backend == "native":
             raise RuntimeError("native backend requested but unavailable for this comm/device")
         why = "native library unavailable"
@@ -454,28 +513,30 @@ def _chain_admm_quantized(model, local_ids, n_total, rho, obj0, tol, max_iter, c
         raise RuntimeError("Q-GADMM: the native backend does not cover this case (%s)" % why)
     res = _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
                             local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
-                            check_exchange, failures, quantize=(bits, seed))
+                            check_exchange, failures, quantize=(bits, seed), censor=censor)
     res.extra["quant_fallback"] = why
     return res
 
 
 def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter, placement, schedule, cost_quirk,
-                             name, opts, bits, seed) -> RunResult:
+                             name, opts, bits, seed, censor=None) -> RunResult:
     """Q-GADMM on the native chain engine (one rank, static chain, linear closed form, d <= 256).
-    ``opts``: ``persistent`` (auto/True/False), ``graph``, ``cache``, ``block``, ``xcd``."""
+    ``opts``: ``persistent`` (auto/True/False), ``graph``, ``cache``, ``block``, ``xcd``.
+    ``censor`` (CQ-GADMM): ``q_wire_bytes = transmissions * G * 16 + censored * 16`` -- the device
+    hand-off still writes one 16-byte notice (the header granule) for a censored worker."""
     from ..engine.chain_engine import NativeChainEngine, ResidencyError, HandoffTimeout
     from . import quantize as Q
 
     d = model.d
     block = int(opts.get("block", 32))
     key = ("quant", n_total, tuple(map(int, local_ids)), float(rho), int(max_iter), block, bits, seed,
-           int(opts.get("xcd", 2)))
+           int(opts.get("xcd", 2)), censor)
     cache = getattr(model, "_chain_engines", None)
     eng = cache.get(key) if cache is not None else None
     if eng is None:
         eng = NativeChainEngine(model.X, model.y, local_ids, n_total, "linear", rho=rho, obj0=obj0, tol=tol,
                                 max_iter=max_iter, block=block, precomputed=(model.A, model.b, model.yy),
-                                xcd=int(opts.get("xcd", 2)), quant=(bits, seed))
+                                xcd=int(opts.get("xcd", 2)), quant=(bits, seed), censor=censor)
         if opts.get("cache", True):
             if cache is None:
                 cache = {}
@@ -499,7 +560,7 @@ def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter
             engine_kind = "graph(fallback: %s)" % type(e).__name__
     if r is None:
         r = eng.run(use_graph=opts.get("graph", True))
-        kernel = "graph-Q"
+        kernel = "graph-Q" if censor is None else "graph-CQ"
         if engine_kind is None:
             engine_kind = "graph" if eng.graph_ok() else "eager"
         eng.stream.synchronize()
@@ -516,7 +577,10 @@ def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter
                            "obj_mode": eng.obj_mode_name, "engine_obj": eng, "q_granules": G,
                            "q_wire_bytes": iters * n_total * G * 16,
                            "placed": int(getattr(eng, "last_placed", 0)) if engine_kind == "persistent" else 0})
-    _quant_accounting(res, bits, seed, n_total, d)
+    _quant_accounting(res, bits, seed, n_total, d, sent=eng.sent_trace(iters) if censor is not None else None,
+                      censor=censor)
+    if censor is not None:
+        res.extra["q_wire_bytes"] = res.extra["transmissions"] * G * 16 + res.extra["censored"] * 16
     return res
 
 
@@ -1125,6 +1189,27 @@ def quantized_group_admm(model, rho, obj0, acc, max_iter, bits, seed=1234, **kw)
     return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, quantize=(bits, seed), **kw)
 
 
+def censored_quantized_group_admm(model, rho, obj0, acc, max_iter, bits, tau0, xi, seed=1234, **kw) -> RunResult:
+    """CQ-GADMM (censoring, arXiv:2009.06459, on top of Q-GADMM) on a static chain: at iteration k a
+    worker transmits its quantized difference only when its public model would move by at least
+    ``tau0 * xi^k`` (``chain_admm(..., quantize=(bits, seed), censor=(tau0, xi))``)."""
+    n_total = kw.pop("n_total", model.n_local)
+    local_ids = kw.pop("local_ids", list(range(model.n_local)))
+    kw.setdefault("name", "CQ-GADMM(b=%d)" % int(bits))
+    return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, quantize=(bits, seed), censor=(tau0, xi), **kw)
+
+
+def _sweep_member(cfg):
+    """A sweep member ``(rho, bits, seed)`` or ``(rho, bits, seed, tau0, xi)`` as ``((rho, bits, seed),
+    censor or None)``."""
+    from .quantize import check_censor
+    if len(cfg) == 3:
+        return (float(cfg[0]), int(cfg[1]), int(cfg[2])), None
+    if len(cfg) == 5:
+        return (float(cfg[0]), int(cfg[1]), int(cfg[2])), check_censor(cfg[3:])
+    raise ValueError("a Q sweep member is (rho, bits, seed) or (rho, bits, seed, tau0, xi), got %r" % (tuple(cfg),))
+
+
 def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float, max_iter: int, *,
                                tols: Optional[Sequence[float]] = None, placement: Optional[Placement] = None,
                                backend: str = "auto", name: str = "Q-GADMM", engine_opts: Optional[dict] = None,
@@ -1141,8 +1226,14 @@ def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float
     Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, the exchange checker, no native
     library, a non-linear model, not every worker local, d > 64, or a device that cannot hold the
     group's workgroups -- it IS that loop, and every result records ``extra['sweep_fallback'] =
-    reason``. A hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``, as in ``chain_admm``."""
-    configs = [(float(r), int(b), int(s)) for r, b, s in configs]
+    reason``. A hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``, as in ``chain_admm``.
+    A member may also be ``(rho, bits, seed, tau0, xi)``: CQ-GADMM, equal to its own ``chain_admm(...,
+    quantize=(bits, seed), censor=(tau0, xi))``. A group with at least one censored member runs on the
+    censored sweep kernel, where an uncensored member gets an all-zero threshold table and so stays
+    Q-GADMM bit for bit; a group without one runs on the Q sweep kernel as before."""
+    members = [_sweep_member(c) for c in configs]
+    configs = [m[0] for m in members]
+    censors = [m[1] for m in members]
     opts = dict(engine_opts or {})
     n_total = model.n_local if n_total is None else int(n_total)
     local_ids = list(range(model.n_local)) if local_ids is None else [int(w) for w in local_ids]
@@ -1153,9 +1244,9 @@ def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float
 
     def sequential(reason: str) -> List[RunResult]:
         out = []
-        for (rho, bits, seed), t in zip(configs, tols):
+        for (rho, bits, seed), cen, t in zip(configs, censors, tols):
             r = chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
-                           backend=backend, name=name, engine_opts=engine_opts, quantize=(bits, seed))
+                           backend=backend, name=name, engine_opts=engine_opts, quantize=(bits, seed), censor=cen)
             r.extra["sweep_fallback"] = reason
             out.append(r)
         return out
@@ -1188,13 +1279,15 @@ def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float
     def run_group(g_cfgs, idx):
         t_begin = time.perf_counter()
         g_tols = [tols[i] for i in idx]
-        key = ("qsweep", n_total, tuple(local_ids), tuple(g_cfgs), int(max_iter), xcd)
+        g_cens = [censors[i] for i in idx]
+        key = ("qsweep", n_total, tuple(local_ids), tuple(g_cfgs), int(max_iter), xcd, tuple(g_cens))
         cache = getattr(model, "_chain_engines", None)
         sw = cache.get(key) if cache is not None else None
         if sw is None:
             sw = QuantSweepEngine.build(model.X, model.y, local_ids, n_total, g_cfgs, obj0=obj0, tols=g_tols,
                                         max_iters=max_iter, precomputed=(model.A, model.b, model.yy),
-                                        placement=placement, xcd=xcd)
+                                        placement=placement, xcd=xcd,
+                                        censors=g_cens)
             torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
             if opts.get("cache", True):
                 if cache is None:
@@ -1225,7 +1318,11 @@ def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float
                                    "sweep": {"width": len(g_cfgs), "slot": j, "kernel": sw.last_kernel,
                                              "placed": int(sw.last_placed[j]), "wall_ms_launch": sw.last_wall_ms},
                                    "sweep_kernel": sw.last_kernel, "sweep_slot": j})
-            _quant_accounting(res, bits, seed, n_total, model.d)
+            cen = g_cens[j]
+            _quant_accounting(res, bits, seed, n_total, model.d,
+                              sent=m.sent_trace(iters) if cen is not None else None, censor=cen)
+            if cen is not None:
+                res.extra["q_wire_bytes"] = res.extra["transmissions"] * G * 16 + res.extra["censored"] * 16
             out.append(res)
         return out
 

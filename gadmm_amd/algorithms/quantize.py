@@ -28,6 +28,25 @@ end of the range of ``min(frac(c + u), 1 - frac(c + u)) * delta / max|theta|`` -
 the iterate, the nearest rounding decision is from going the other way (the idiom of the LAG
 ``trigger_margin``). A comparison of two implementations of a quantized run means something only while
 it stays well above their rounding differences.
+
+Censoring (C-GADMM / CQ-GGADMM, Ben Issaid et al., arXiv:2009.06459) sits on top of the quantizer and
+changes nothing in it: a worker transmits only when its public model would move by at least a
+geometrically decaying threshold. With ``cand`` the new public model ``quantize_rows`` proposes for
+worker ``w`` at iteration ``it`` (1-based), every line one rounded IEEE f64 operation (no FMA)::
+
+    step_i = cand_i - th_hat_i           sq_i = step_i * step_i           s = sum64(sq)
+    thr_0  = tau0;  thr_k = thr_{k-1} * xi                                thr2[k] = thr_k * thr_k
+    send   = s >= thr2[it]
+    send:      th_hat <- cand, the message (R, codes) as above
+    not send:  th_hat unchanged, nothing travels but a one-word "censored" notice
+
+``sum64`` is the order the kernels sum in: pad with zeros to a multiple of 64, on each 64-chunk run
+the butterfly ``x <- x + x[i ^ off]`` for ``off = 32, 16, 8, 4, 2, 1`` and take element 0, then add
+the chunks' results in order, starting from 0.0. ``tau0 = 0`` gives ``thr2 == 0``: every worker always
+sends, and the run is Q-GADMM bit for bit. ``R == 0`` gives ``s = 0``: censored whenever
+``thr2 > 0``. The *censor margin* is the minimum over the decisions with ``thr2 > 0`` of
+``|s - thr2| / thr2``: two implementations can be compared only while it stays well above their
+rounding differences (the idiom of the flip margin).
 """
 from __future__ import annotations
 
@@ -40,6 +59,9 @@ _GOLDEN = 0x9e3779b97f4a7c15
 _M1 = 0xbf58476d1ce4e5b9
 _M2 = 0x94d049bb133111eb
 _MASK = (1 << 64) - 1
+# header word of a censored message where a message's first word holds the bits of R: the sign bit,
+# which no R = max |diff| >= 0 carries
+CENSORED_HEADER = 1 << 63
 
 
 def check_bits(bits) -> int:
@@ -147,3 +169,60 @@ def unpack_codes(words: np.ndarray, bits: int, d: int) -> np.ndarray:
     sh = (np.arange(per, dtype=np.uint64) * np.uint64(bits))
     q = (w[..., None] >> sh) & np.uint64((1 << bits) - 1)
     return q.reshape(w.shape[:-1] + (-1,))[..., :int(d)].astype(np.int64)
+
+
+def check_censor(censor) -> Tuple[float, float]:
+    """``(tau0, xi)`` as floats if they are a censoring rule: ``tau0 >= 0`` and ``0 < xi < 1``."""
+    if censor is None or len(censor) != 2:
+        raise ValueError("censor: (tau0, xi)")
+    tau0, xi = float(censor[0]), float(censor[1])
+    if not tau0 >= 0.0 or not np.isfinite(tau0):
+        raise ValueError("censor: tau0 must be finite and >= 0, got %r" % (censor[0],))
+    if not 0.0 < xi < 1.0:
+        raise ValueError("censor: xi must lie in (0, 1), got %r" % (censor[1],))
+    return tau0, xi
+
+
+def censor_thresholds(tau0: float, xi: float, n_iter: int) -> np.ndarray:
+    """The table ``thr2[0 .. n_iter]`` of squared thresholds: ``thr_0 = tau0``, ``thr_k = thr_{k-1} *
+    xi`` (one rounded multiply per iteration), ``thr2[k] = thr_k * thr_k``. Iteration ``it`` (1-based)
+    compares with ``thr2[it]``. Computed once on the host and handed to the kernels."""
+    tau0, xi = check_censor((tau0, xi))
+    thr = np.empty(int(n_iter) + 1, dtype=np.float64)
+    t = np.float64(tau0)
+    for k in range(thr.size):
+        thr[k] = t
+        t = t * np.float64(xi)
+    return thr * thr
+
+
+def sum64(v: np.ndarray) -> np.ndarray:
+    """Sum over the last axis in the order of the kernels' ``wave_sum_f64`` / ``block_sum_f64``."""
+    v = np.asarray(v, dtype=np.float64)
+    n = v.shape[-1]
+    nc = max((n + 63) // 64, 1)
+    x = np.zeros(v.shape[:-1] + (nc * 64,), dtype=np.float64)
+    x[..., :n] = v
+    x = x.reshape(v.shape[:-1] + (nc, 64))
+    idx = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        x = x + x[..., idx ^ off]
+    total = np.zeros(v.shape[:-1], dtype=np.float64)
+    for c in range(nc):
+        total = total + x[..., c, 0]
+    return total
+
+
+def censor_rows(cand: np.ndarray, th_hat: np.ndarray, thr2) -> Tuple[np.ndarray, np.ndarray, float]:
+    """The censoring decision of rows ``cand`` (k, d), the public models ``quantize_rows`` proposes,
+    against the current ones ``th_hat`` (k, d) under the squared threshold(s) ``thr2`` (a scalar or
+    (k,)): ``(send (k,) bool, s (k,), censor margin)``; the margin is ``inf`` where ``thr2 == 0``."""
+    cand = np.asarray(cand, dtype=np.float64)
+    th_hat = np.asarray(th_hat, dtype=np.float64)
+    step = cand - th_hat
+    s = sum64(step * step)
+    t2 = np.broadcast_to(np.asarray(thr2, dtype=np.float64), s.shape)
+    send = s >= t2
+    live = t2 > 0.0
+    margin = float(np.min(np.abs(s[live] - t2[live]) / t2[live])) if np.any(live) else float("inf")
+    return send, s, margin

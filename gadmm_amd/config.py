@@ -52,8 +52,13 @@ class ExperimentConfig:
     # ``Q-GADMM_b{bits}_rho{rho}`` run per (bits, rho), bits in {4, 8, 16}; empty = none
     quant_bits: List[float] = field(default_factory=list)
     quant_seed: int = 1234
+    # CQ-GADMM (censoring on top of Q-GADMM): ``censor=tau0,xi`` with ``quant_bits`` adds one
+    # ``CQ-GADMM_b{bits}_rho{rho}`` run next to every Q run; empty = none
+    censor: List[float] = field(default_factory=list)
 
     def override(self, **kw) -> "ExperimentConfig":
+        if len(kw.get("censor", [])) not in (0, 2):
+            raise ValueError("censor must be 'tau0,xi', not %r" % (kw["censor"],))
         if kw.get("sweep", "sequential") not in ("sequential", "concurrent"):
             raise ValueError("sweep must be 'sequential' or 'concurrent', not %r" % kw["sweep"])
         return dataclasses.replace(self, **kw)

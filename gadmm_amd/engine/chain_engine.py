@@ -138,7 +138,7 @@ class NativeChainEngine:
                  inner_tol: float = 1e-4, comm=None, block: int = 16, stream: Optional[torch.cuda.Stream] = None,
                  precomputed=None, force_monitor: bool = False, obj_mode: str = "auto", local_solver: str = "gd",
                  chord: Optional[float] = None, residual: bool = False, xcd: int = 2, inverses=None,
-                 quant: Optional[Sequence[int]] = None):
+                 quant: Optional[Sequence[int]] = None, censor: Optional[Sequence[float]] = None):
         """``local_solver`` (logistic): "gd" = the reference's inexact inner GD (logReg_GD.m, step /
         max_inner / inner_tol), "newton" = exact local solves (group_ADMM_logistic.m semantics,
         csrc/kernels/chain_newton.hip; d, m <= 64). ``chord`` (newton): a worker reuses its last
@@ -162,7 +162,11 @@ class NativeChainEngine:
         the theta table holds the public models th_hat, ``theta_true`` the true iterates of the last
         phases, ``q_msg`` (n_total, 1 + words) the last message of each worker (the bits of R, then the
         packed code words). ``run()`` uses the graph engine's Q phase kernel, ``run_persistent()`` the
-        persistent Q kernel (``persistent_q_eligible``); the blocked plan is never used."""
+        persistent Q kernel (``persistent_q_eligible``); the blocked plan is never used.
+        ``censor``: ``(tau0, xi)`` with ``quant`` -- CQ-GADMM on the censored kernels of chain_quant.hip:
+        the engine owns the table of squared thresholds (``c_thr2``, algorithms/quantize.py:
+        censor_thresholds) and the ``c_sent`` buffer (max_iter, n_total; ``sent_trace``), zero-filled by
+        ``reset`` on the engine's stream."""
         if not X_loc.is_cuda:
             raise ValueError("NativeChainEngine runs on a HIP device; use the torch algorithms on CPU")
         # the kernels read raw f64 pointers: anything else (e.g. float32 labels from torch.where) would be
@@ -190,6 +194,13 @@ class NativeChainEngine:
             if model != "linear" or self.d > 256 or comm is not None:
                 raise ValueError("native Q-GADMM: the linear model on one rank with d <= 256")
             self.q_words = words_per_row(self.d, self.quant[0])
+        self.censor = None
+        self.c_thr2 = self.c_sent = None
+        if censor is not None:
+            from ..algorithms.quantize import check_censor
+            if self.quant is None:
+                raise ValueError("censor=(tau0, xi) needs quant=(bits, seed)")
+            self.censor = check_censor(censor)
         if local_solver == "newton" and (model != "logistic" or self.d > 64 or self.m > 64):
             raise ValueError("native Newton local solves need the logistic model with d, m <= 64")
         self.local_solver = local_solver
@@ -246,6 +257,8 @@ class NativeChainEngine:
             if self.quant is not None:
                 self.theta_true = torch.zeros((nl, d), dtype=f64, device=dev)
                 self.q_msg = torch.zeros((self.n_total, 1 + self.q_words), dtype=torch.int64, device=dev)
+            if self.censor is not None:
+                self._censor_buffers()
             if d > 256:
                 stride = int(native.require().gadmm_chain_big_rbuf_stride(d))
                 self.rbuf = torch.zeros((max(nl, 1) * stride,), dtype=f64, device=dev)
@@ -311,6 +324,8 @@ class NativeChainEngine:
         if self.quant is not None:
             args.q_bits, args.q_seed = self.quant
             args.q_true, args.q_msg = self.theta_true.data_ptr(), self.q_msg.data_ptr()
+        if self.censor is not None:
+            args.c_thr2, args.c_sent = self.c_thr2.data_ptr(), self.c_sent.data_ptr()
         desc = native.EngineDesc()
         desc.base = args
         desc.d_slots = self.slots.data_ptr()
@@ -326,6 +341,32 @@ class NativeChainEngine:
         self.plan: Optional[RankPlan] = None
         self.path: Optional[List[int]] = None
         self._pbuf = None
+
+    _CENSOR_PAD = 64  # thresholds past max_iter: the persistent kernel runs up to `lag` (< 64) iterations on
+
+    def _censor_buffers(self):
+        """The threshold table and the sent buffer of the censored kernels, on the engine's stream. An
+        engine without ``censor`` gets an all-zero table: every worker always sends, Q-GADMM bit for bit
+        (an uncensored member of a sweep that runs on the censored kernel)."""
+        if self.c_thr2 is not None:
+            return
+        from ..algorithms.quantize import censor_thresholds
+        n_thr = self.max_iter + self._CENSOR_PAD + 2
+        with torch.cuda.stream(self.stream):
+            if self.censor is not None:
+                thr2 = torch.from_numpy(censor_thresholds(self.censor[0], self.censor[1], n_thr - 1))
+                self.c_thr2 = thr2.to(self.device)
+            else:
+                self.c_thr2 = torch.zeros((n_thr,), dtype=torch.float64, device=self.device)
+            self.c_sent = torch.zeros((self.max_iter * self.n_total,), dtype=torch.uint8, device=self.device)
+
+    def sent_trace(self, upto: int) -> np.ndarray:
+        """(upto, n_total) bool: who transmitted in iterations 1..upto of the last censored solve."""
+        if self.c_sent is None:
+            raise RuntimeError("sent_trace: not a censored solve")
+        self.stream.synchronize()
+        k = max(0, min(int(upto), self.max_iter))
+        return self.c_sent[:k * self.n_total].cpu().numpy().reshape(k, self.n_total).astype(bool)
 
     # ---------------------------------------------------------------------------------------------
     def _build_inverses(self, in_place: bool = False, check: bool = True):
@@ -504,6 +545,9 @@ class NativeChainEngine:
         if self.rres is not None and zero_state:  # a row's non-tail entries stay 0
             with torch.cuda.stream(self.stream):
                 self.rres.zero_()
+        if self.c_sent is not None and zero_state:  # rows past the stop stay 0
+            with torch.cuda.stream(self.stream):
+                self.c_sent.zero_()
         if zero_state:  # theta = mu = part = 0, trace = NaN, the control block and the clock start: one launch
             native.check(self.lib.gadmm_chain_reset_state_stamp(
                 self.ctl.data_ptr(), int(start_iter), int(pending), self.theta.data_ptr(), self.theta.numel(),
@@ -568,29 +612,40 @@ class NativeChainEngine:
         g.scratch = self.newton_img.data_ptr() if self.newton_img is not None else None
         return g
 
-    def persistent_q_eligible(self) -> bool:
-        """The persistent Q kernel takes this engine: one rank, every worker local, d <= 64 and all
-        n + 1 workgroups resident at once (``GADMM_CU_BUDGET`` shrinks the CU count)."""
+    def persistent_q_eligible(self, censored: Optional[bool] = None) -> bool:
+        """The persistent Q kernel (``censored``: the CQ kernel; None: the one this engine runs) takes this
+        engine: one rank, every worker local, d <= 64 and all n + 1 workgroups resident at once
+        (``GADMM_CU_BUDGET`` shrinks the CU count)."""
         if self.quant is None or self.plan is None or self.path is None or self.model != "linear":
             return False
         if self.nranks != 1 or self.n_local != self.n_total or self.d > 64:
             return False
-        key = ("q", getenv("GADMM_CU_BUDGET"))
+        censored = self.censor is not None if censored is None else bool(censored)
+        key = ("cq" if censored else "q", getenv("GADMM_CU_BUDGET"))
         memo = self.__dict__.setdefault("_cap_memo", {})
         if key not in memo:
             pa = native.PersistArgs()
             pa.d, pa.n = self.d, self.n_total
-            memo[key] = int(self.lib.gadmm_chain_persistent_q_capacity(ctypes.byref(pa)))
+            cap = self.lib.gadmm_chain_persistent_cq_capacity if censored else self.lib.gadmm_chain_persistent_q_capacity
+            memo[key] = int(cap(ctypes.byref(pa)))
         return self.n_local + 1 <= memo[key]
 
     # ---- a persistent Q solve in two halves, for launches that carry several solves (quant_sweep.py)
-    def prepare_persistent_q(self, lag: int = 4, timeout_s: float = 20.0) -> native.PersistArgs:
+    def prepare_persistent_q(self, lag: int = 4, timeout_s: float = 20.0,
+                             censored: Optional[bool] = None) -> native.PersistArgs:
         """The ``PersistArgs`` of a fresh Q-GADMM solve on the persistent Q body, without launching:
         state must be reset by the caller. The message table is allocated and zeroed here, on the stream
         the engine runs on NOW, so an engine that joins a sweep prepares after ``adopt_stream`` and the
-        launch must use that stream. Raises ValueError when the engine is not eligible."""
-        if not self.persistent_q_eligible():
+        launch must use that stream. Raises ValueError when the engine is not eligible.
+        ``censored``: for the CQ kernels (None: as the engine was built); an engine without ``censor`` then
+        brings an all-zero threshold table."""
+        censored = self.censor is not None if censored is None else bool(censored)
+        if self.censor is not None and not censored:
+            raise ValueError("a censored engine runs on the censored kernels")
+        if not self.persistent_q_eligible(censored):
             raise ValueError("persistent Q kernel not eligible for this engine/config")
+        if censored and not 1 <= lag < self._CENSOR_PAD:  # the threshold table ends _CENSOR_PAD past max_iter
+            raise ValueError("censored kernels: lag must be in 1..%d" % (self._CENSOR_PAD - 1))
         ring = lag + 4
         pa, slots, pos, _ = self._persist_args(lag, ring, timeout_s, 1, 0, None, False, 0, False)
         G = self.q_words + 1
@@ -600,6 +655,9 @@ class NativeChainEngine:
         pa.obj_mode = 0
         pa.qg, pa.q_true = self._qg.data_ptr(), self.theta_true.data_ptr()
         pa.q_bits, pa.q_seed = self.quant
+        if censored:
+            self._censor_buffers()
+            pa.c_thr2, pa.c_sent = self.c_thr2.data_ptr(), self.c_sent.data_ptr()
         return pa
 
     def finish_persistent_q(self, wall_ms: float, fetch: bool, what: str) -> EngineRun:
@@ -617,12 +675,14 @@ class NativeChainEngine:
         if start_iter != 1:
             raise ValueError("persistent Q kernel: a fresh solve only (start_iter 1)")
         pa = self.prepare_persistent_q(lag, timeout_s)
-        self.last_kernel = "persistent-Q(b=%d,G=%d)" % (self.quant[0], self.q_words + 1)
+        cens = self.censor is not None
+        self.last_kernel = "persistent-%s(b=%d,G=%d)" % ("CQ" if cens else "Q", self.quant[0], self.q_words + 1)
+        launch = self.lib.gadmm_chain_persistent_cq_launch if cens else self.lib.gadmm_chain_persistent_q_launch
         t0 = _time.perf_counter()
-        rc = int(self.lib.gadmm_chain_persistent_q_launch(ctypes.byref(pa), self.stream.cuda_stream))
+        rc = int(launch(ctypes.byref(pa), self.stream.cuda_stream))
         if rc == -2:
             raise ResidencyError(self.lib.gadmm_last_error().decode())
-        native.check(rc, "chain_persistent_q_launch")
+        native.check(rc, "chain_persistent_cq_launch" if cens else "chain_persistent_q_launch")
         fetch = self._queue_readback(fetch_trace)
         self.stream.synchronize()
         return self.finish_persistent_q((_time.perf_counter() - t0) * 1e3, fetch, "persistent Q kernel")

@@ -18,6 +18,10 @@ Two ways to build one:
   ``refresh(X, y)`` recomputes both in place;
 * ``QuantSweepEngine(members)``: already-built engines (different data, N, d within one register class
   of the kernel -- d <= 52 or 53..64 -- and bits); they are moved onto the sweep's stream.
+
+CQ-GADMM members (``censor=(tau0, xi)``): a sweep with at least one censored member runs on
+``chain_persistent_cq_sweep_kernel``; its uncensored members bring an all-zero threshold table, under
+which the censored body computes Q-GADMM bit for bit. A sweep without one keeps the Q kernel.
 """
 from __future__ import annotations
 
@@ -80,14 +84,18 @@ class QuantSweepEngine:
     @classmethod
     def build(cls, X: torch.Tensor, y: torch.Tensor, local_ids: Sequence[int], n_total: int, configs: Sequence,
               obj0: float = 0.0, tols=1e-4, max_iters=1000, precomputed=None,
-              placement: Optional[Placement] = None, xcd: int = 2) -> "QuantSweepEngine":
+              placement: Optional[Placement] = None, xcd: int = 2, censors: Optional[Sequence] = None
+              ) -> "QuantSweepEngine":
         """Members = the same shards under every ``(rho, bits, seed)`` of ``configs``. ``tols`` /
         ``max_iters``: one value or one per member. ``precomputed``: an ``(A, b, yy)`` Gram to share (else
-        computed here, once)."""
+        computed here, once). ``censors``: one ``(tau0, xi)`` or None per config (CQ-GADMM members)."""
         if not X.is_cuda:
             raise ValueError("QuantSweepEngine runs on a HIP device")
         configs = [(float(r), int(b), int(s)) for r, b, s in configs]
         K = len(configs)
+        censors = [None] * K if censors is None else list(censors)
+        if len(censors) != K:
+            raise ValueError("censors: one (tau0, xi) or None per config")
         if K < 1 or K > quant_sweep_capacity():
             raise ValueError("%d configs: one sweep launch takes 1..%d" % (K, quant_sweep_capacity()))
         tols = [float(tols)] * K if not isinstance(tols, (list, tuple)) else [float(t) for t in tols]
@@ -122,7 +130,7 @@ class QuantSweepEngine:
             dtv = (i * V, i * V, i * V + V - 1)
             m = NativeChainEngine(X, y, local_ids, n_total, "linear", rho=rho, obj0=obj0, tol=tols[j],
                                   max_iter=max_iters[j], stream=stream, precomputed=(A, b, yy), xcd=xcd,
-                                  inverses=(Minv, len(rhos) * V, dtv), quant=(bits, seed))
+                                  inverses=(Minv, len(rhos) * V, dtv), quant=(bits, seed), censor=censors[j])
             m.set_path(list(range(n_total)), pl, 0)
             members.append(m)
         self = cls(members, stream=stream)
@@ -162,17 +170,18 @@ class QuantSweepEngine:
         for m in self.members:
             m.reset()
         batch = (native.PersistArgs * K)()
+        cens = any(m.censor is not None for m in self.members)  # one censored member: the censored kernel for all
         for j, m in enumerate(self.members):
             try:
-                batch[j] = m.prepare_persistent_q(lag=lag, timeout_s=timeout_s)
+                batch[j] = m.prepare_persistent_q(lag=lag, timeout_s=timeout_s, censored=cens)
             except ValueError as e:
                 raise ValueError("sweep member %d: %s" % (j, e))
-        self.last_kernel = "persistent-Q-sweep(K=%d)" % K
+        self.last_kernel = "persistent-%s-sweep(K=%d)" % ("CQ" if cens else "Q", K)
         for m in self.members:
             m.last_kernel = self.last_kernel
+        launch = self.lib.gadmm_chain_persistent_cq_sweep_launch if cens else self.lib.gadmm_chain_persistent_q_sweep_launch
         t0 = time.perf_counter()
-        rc = int(self.lib.gadmm_chain_persistent_q_sweep_launch(batch, K, self._stage_host.data_ptr(),
-                                                                self._stage_dev.data_ptr(), self.stream.cuda_stream))
+        rc = int(launch(batch, K, self._stage_host.data_ptr(), self._stage_dev.data_ptr(), self.stream.cuda_stream))
         if rc == -2:
             raise ResidencyError(self.lib.gadmm_last_error().decode())
         if rc == -1:

@@ -315,7 +315,8 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
     is torch or a run must keep its state; each run's summary then names the sweep kernel and its slot.
     With ``quant_bits`` set, the same switch sends the Q-GADMM ``quant_bits x rhos`` list through
     ``quantized_group_admm_sweep`` (same run keys and names; where that call is the sequential loop,
-    the summaries carry ``sweep_fallback``)."""
+    the summaries carry ``sweep_fallback``). With ``censor`` (and ``quant_bits``) every Q run gets a
+    CQ-GADMM run ``CQ-GADMM_b{bits}_rho{rho}`` next to it, through the same calls."""
     from ..utils.timing import roctx_range
 
     cfg = prob.cfg
@@ -343,19 +344,29 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
     # the sweep call decides by itself where it is the sequential loop (CPU tensors, the torch backend,
     # several ranks, ...) and says so in every result (extra['sweep_fallback'])
     q_concurrent = cfg.sweep == "concurrent" and cfg.model == "linear" and len(cfg.quant_bits) > 0 and len(cfg.rhos) > 0
+    if cfg.censor and not cfg.quant_bits:
+        raise ValueError("censor: CQ-GADMM censors quantized messages, set quant_bits too")
+    censor = (float(cfg.censor[0]), float(cfg.censor[1])) if cfg.censor else None
+
+    def q_name(bits, rho, cen):
+        return ("CQ-" if cen else "Q-") + "GADMM(b=%d,rho=%g)" % (bits, rho), \
+            ("CQ-" if cen else "Q-") + "GADMM_b%d_rho%g" % (bits, rho)
     if q_concurrent:  # the bits x rho list side by side, up to eight solves per launch, one per XCD
         from ..algorithms import quantized_group_admm_sweep
 
         q_cfgs = [(rho, int(bits), cfg.quant_seed) for bits in cfg.quant_bits for rho in cfg.rhos]
+        if censor is not None:
+            q_cfgs += [c + censor for c in q_cfgs]
         with roctx_range("qgadmm sweep concurrent"):
             rs = quantized_group_admm_sweep(prob.model, q_cfgs, prob.obj0, cfg.acc, cfg.gadmm_iters,
                                             placement=prob.placement, backend=backend, comm=sess.comm,
                                             n_total=prob.n_total, local_ids=prob.local_ids)
-        for (rho, bits, _), r in zip(q_cfgs, rs):
-            r.algorithm = "Q-GADMM(b=%d,rho=%g)" % (bits, rho)
-            for k in ("engine_obj", "theta_true", "state"):
+        for c, r in zip(q_cfgs, rs):
+            rho, bits = c[0], c[1]
+            r.algorithm, key = q_name(bits, rho, len(c) == 5)
+            for k in ("engine_obj", "theta_true", "state", "sent_trace"):
                 r.extra.pop(k, None)
-            out["Q-GADMM_b%d_rho%g" % (bits, rho)] = attach_modelled_clock(r, prob.model, rho, sess)
+            out[key] = attach_modelled_clock(r, prob.model, rho, sess)
     for bits in ([] if q_concurrent else cfg.quant_bits):  # Q-GADMM next to the sweep; comm_units counts equivalent full-precision messages
         from ..algorithms import chain_admm
 
@@ -367,6 +378,15 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
             for k in ("engine_obj", "theta_true", "state"):
                 r.extra.pop(k, None)
             out["Q-GADMM_b%d_rho%g" % (int(bits), rho)] = attach_modelled_clock(r, prob.model, rho, sess)
+            if censor is not None:
+                name, key = q_name(int(bits), rho, True)
+                with roctx_range("cqgadmm b=%g rho=%g" % (bits, rho)):
+                    r = chain_admm(prob.model, prob.local_ids, prob.n_total, rho, prob.obj0, cfg.acc, cfg.gadmm_iters,
+                                   comm=sess.comm, placement=prob.placement, backend=backend, name=name,
+                                   quantize=(int(bits), cfg.quant_seed), censor=censor)
+                for k in ("engine_obj", "theta_true", "state", "sent_trace"):
+                    r.extra.pop(k, None)
+                out[key] = attach_modelled_clock(r, prob.model, rho, sess)
     if cfg.model == "logistic":
         for rho in cfg.exact_rhos:  # exact local solves (D2 semantics), to the tighter exact_acc gap
             with roctx_range("gadmm_exact rho=%g" % rho):

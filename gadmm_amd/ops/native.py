@@ -56,6 +56,7 @@ class PhaseArgs(ctypes.Structure):
         ("rbuf", c_void_p), ("obj_mode", c_int), ("solver", c_int),
         ("n_total", c_int), ("pad_nt", c_int), ("lgid", c_void_p), ("tstamp", c_void_p),
         ("rres", c_void_p),
+        ("c_thr2", c_void_p), ("c_sent", c_void_p),
         ("q_true", c_void_p), ("q_msg", c_void_p), ("q_bits", c_int), ("q_seed", ctypes.c_ulonglong),
     ]
 
@@ -114,6 +115,7 @@ class PersistArgs(ctypes.Structure):
         ("xchk", c_void_p), ("xcd", c_int), ("xtag", c_int),
         ("blk_dl", c_int), ("dl_halo", c_int), ("dl_tab", c_void_p * 2), ("minv_pad", c_void_p),
         ("ep_flush", c_void_p),
+        ("c_thr2", c_void_p), ("c_sent", c_void_p),
         ("qg", c_void_p), ("q_true", c_void_p), ("q_bits", c_int), ("q_seed", ctypes.c_ulonglong),
     ]
 
@@ -193,6 +195,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_chain_persistent_q_sweep_launch": (c_int, [ctypes.POINTER(PersistArgs), c_int, c_void_p, c_void_p,
                                                           c_void_p]),
         "gadmm_quant_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_censor_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_chain_persistent_cq_launch": (c_int, [ctypes.POINTER(PersistArgs), c_void_p]),
+        "gadmm_chain_persistent_cq_capacity": (c_long, [ctypes.POINTER(PersistArgs)]),
+        "gadmm_chain_persistent_cq_sweep_launch": (c_int, [ctypes.POINTER(PersistArgs), c_int, c_void_p, c_void_p,
+                                                           c_void_p]),
         "gadmm_chain_persistent_logistic_capacity": (c_long, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
         "gadmm_chain_persistent_logistic_launch": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs),
                                                            c_void_p]),
