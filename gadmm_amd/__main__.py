@@ -2,7 +2,8 @@
 
 Entries: LinearRegression_Synthetic, LinearRegression_Real, LogisticRegression_Synthetic,
 LogisticRegression_Real, Dynamic_LinearRegression_Synthetic, Dynamic_LinearRegression_Real,
-LinearRegression_gadmm_vs_admm, LinearRegression_RealShaped (10M x 10k sharded, MI355X).
+LinearRegression_gadmm_vs_admm, LinearRegression_RealShaped (10M x 10k sharded, MI355X),
+LinearRegression_Topologies (GGADMM on bipartite graphs: chain, ring, grid, star, complete bipartite).
 ``python -m gadmm_amd list`` shows them; ``python -m gadmm_amd <Entry> -h`` the options.
 """
 import sys

@@ -55,6 +55,9 @@ class ExperimentConfig:
     # CQ-GADMM (censoring on top of Q-GADMM): ``censor=tau0,xi`` with ``quant_bits`` adds one
     # ``CQ-GADMM_b{bits}_rho{rho}`` run next to every Q run; empty = none
     censor: List[float] = field(default_factory=list)
+    # GGADMM (entry LinearRegression_Topologies): the bipartite graphs to solve on, as
+    # ``parallel.topology.parse_graph`` names them ("chain", "ring", "grid:RxC", "star[:hub]", "kbip")
+    graphs: List[str] = field(default_factory=list)
 
     def override(self, **kw) -> "ExperimentConfig":
         if len(kw.get("censor", [])) not in (0, 2):
@@ -101,6 +104,11 @@ PRESETS = {
         name="LinearRegression_gadmm_vs_admm", model="linear", data="linear_synthetic", num_workers=24,
         gadmm_iters=20000, rhos=[1.0], acc=1e-4, coherences=[1, 10, 50], run_baselines=False, run_dualavg=False,
         run_star=True, reference="LinearRegression_gadmm_vs_admm.m:78-119"),
+    "LinearRegression_Topologies": ExperimentConfig(
+        name="LinearRegression_Topologies", model="linear", data="linear_synthetic", num_workers=24,
+        gadmm_iters=3000, rhos=[3.0], acc=1e-4, graphs=["chain", "ring", "grid:4x6", "star:0", "kbip"],
+        run_baselines=False, run_dualavg=False,
+        reference="beyond the reference: GGADMM (arXiv:2009.06459) on the data of LinearRegression_Synthetic.m"),
 }
 
 
@@ -128,6 +136,8 @@ def parse_overrides(cfg: ExperimentConfig, items: List[str]) -> ExperimentConfig
             kw[k] = int(float(v))
         elif isinstance(cur, float):
             kw[k] = float(v)
+        elif k == "graphs":
+            kw[k] = [x for x in v.split(",") if x]
         elif isinstance(cur, list):
             kw[k] = [float(x) for x in v.split(",") if x]
         elif cur is None and k == "dualavg_iters":

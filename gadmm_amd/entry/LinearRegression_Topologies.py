@@ -1,0 +1,47 @@
+"""G1 (beyond the reference) -- GGADMM over bipartite graphs: the E1 data (N = 24 workers, 50 x 50
+shards), rho = 3, acc = 1e-4, one solve per graph of ``graphs`` (chain, ring, 4 x 6 grid, star around
+worker 0, complete bipartite even vs odd ids) and rho. The chain is GADMM; the other graphs reach the
+same gap in a fraction of its iterations (algorithms/ggadmm.py). Outputs one run per graph x rho,
+``GGADMM_<graph>_rho<rho>``, with the usual summary, per-iteration traces and the three panels (gap
+against iteration / cumulative communication / clock); each summary names its engine, kernel and graph.
+
+    python -m gadmm_amd LinearRegression_Topologies
+    python -m gadmm_amd LinearRegression_Topologies --quick --device cpu
+    python -m gadmm_amd LinearRegression_Topologies --set graphs=ring,grid:3x8 rhos=1,3
+"""
+from .common import Problem, attach_modelled_clock, run_entry
+
+ENTRY = "LinearRegression_Topologies"
+
+
+def body(cfg, sess, args, writer):
+    from ..algorithms import graph_admm
+    from ..parallel.topology import parse_graph
+    from ..utils.timing import roctx_range
+
+    if sess.world != 1:
+        raise NotImplementedError("%s: one process (graph_admm keeps every worker local)" % ENTRY)
+    prob = Problem(cfg, sess)
+    sess.log("  obj0 = %.13f (normal equations, opt_sol_closedForm.m)" % prob.obj0)
+    runs = {}
+    for spec in cfg.graphs:
+        graph = parse_graph(spec, prob.n_total)
+        for rho in cfg.rhos:
+            with roctx_range("ggadmm %s rho=%g" % (spec, rho)):
+                r = graph_admm(prob.model, graph, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, backend=args.backend,
+                               name="GGADMM(%s,rho=%g)" % (spec, rho))
+            r.extra.pop("engine_obj", None)
+            r.extra.pop("state", None)
+            r.extra.update(graph_name=str(spec), graph_edges=len(graph.edges), graph_max_degree=graph.max_degree,
+                           rho=float(rho))
+            runs["GGADMM_%s_rho%g" % (spec, rho)] = attach_modelled_clock(r, prob.model, rho, sess)
+    return {"runs": runs, "obj0": prob.obj0, "dataset": prob.dataset_meta,
+            "figure_groups": {"LinearRegression_Topologies": runs}}
+
+
+def main(argv=None):
+    return run_entry(ENTRY, body, argv)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,7 @@
 """Entry points named after the reference scripts."""
 ENTRIES = ["LinearRegression_Synthetic", "LinearRegression_Real", "LogisticRegression_Synthetic",
            "LogisticRegression_Real", "Dynamic_LinearRegression_Synthetic", "Dynamic_LinearRegression_Real",
-           "LinearRegression_gadmm_vs_admm", "LinearRegression_RealShaped"]
+           "LinearRegression_gadmm_vs_admm", "LinearRegression_RealShaped", "LinearRegression_Topologies"]
 
 
 def get(name: str):

@@ -142,6 +142,37 @@ class StarArgs(ctypes.Structure):
     ]
 
 
+class GraphArgs(ctypes.Structure):
+    """Mirror of csrc/include/gadmm_graph.h (persistent GGADMM on a bipartite graph)."""
+    _fields_ = [
+        ("d", c_int), ("n", c_int), ("n_local", c_int), ("start_iter", c_int),
+        ("max_iter", c_int), ("lag", c_int), ("ring", c_int), ("nranks", c_int),
+        ("epoch", ctypes.c_uint), ("max_degree", c_int), ("timeline_iters", c_int), ("pad0", c_int),
+        ("rho", c_double), ("obj0", c_double), ("tol", c_double), ("timeout_ticks", c_longlong),
+        ("nb_ptr", c_void_p), ("nb_idx", c_void_p), ("wid", c_void_p), ("is_head", c_void_p),
+        ("Minv", c_void_p), ("A", c_void_p), ("b", c_void_p), ("yy", c_void_p),
+        ("theta", c_void_p), ("mu", c_void_p), ("thg", c_void_p), ("objg", c_void_p), ("decg", c_void_p),
+        ("dec_push", c_void_p), ("trace", c_void_p), ("tstamp", c_void_p), ("rres", c_void_p), ("ctl", c_void_p),
+        ("xchk", c_void_p), ("xcd", c_int), ("xtag", c_int),
+    ]
+
+
+def graph_abi_expected() -> list:
+    """What ``gadmm_graph_abi_layout`` must report for the ``GraphArgs`` mirror above."""
+    G = GraphArgs
+    return [ctypes.sizeof(G), G.epoch.offset, G.rho.offset, G.timeout_ticks.offset, G.nb_ptr.offset, G.Minv.offset,
+            G.thg.offset, G.dec_push.offset, G.rres.offset, G.ctl.offset, G.xchk.offset, G.xtag.offset]
+
+
+def check_graph_abi(lib) -> None:
+    """ABI self-check of ``GraphArgs`` against the built library (raises on a mismatch: a stale build)."""
+    buf = (c_longlong * 16)()
+    k = lib.gadmm_graph_abi_layout(buf, 16)
+    if list(buf[:k]) != graph_abi_expected():
+        raise RuntimeError("GraphArgs layout mismatch between gadmm_amd/ops/native.py and the native library: "
+                           "%s vs %s" % (list(buf[:k]), graph_abi_expected()))
+
+
 MODEL_LINEAR, MODEL_LOGISTIC = 0, 1
 
 
@@ -214,6 +245,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_star_launch": (c_int, [ctypes.POINTER(StarArgs), c_void_p]),
         "gadmm_star_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
         "gadmm_star_big_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_graph_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_graph_persistent_lds": (c_long, [c_int, c_int]),
+        "gadmm_graph_persistent_class": (c_int, [ctypes.POINTER(GraphArgs)]),
+        "gadmm_graph_persistent_capacity": (c_long, [ctypes.POINTER(GraphArgs)]),
+        "gadmm_graph_persistent_launch": (c_int, [ctypes.POINTER(GraphArgs), c_void_p]),
         "gadmm_sym_pack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "gadmm_sym_packed_doubles": (c_long, [c_int]),
         "gadmm_ipc_box_bytes": (c_long, [c_int, c_int, c_int, c_int]),

@@ -459,3 +459,191 @@ def chain_message_count(path: Sequence[int], placement: Placement) -> int:
             nb.append(path[pos + 1])
         total += len({int(placement.owner[u]) for u in nb} - {int(placement.owner[w])})
     return total
+
+
+# -------------------------------------------------------------------------------------------------
+# Bipartite graphs (GGADMM, Ben Issaid et al., arXiv:2009.06459: heads and tails on any connected
+# bipartite graph, every edge joins a head to a tail)
+# -------------------------------------------------------------------------------------------------
+
+class BipartiteGraph:
+    """A connected two-colourable graph over workers ``0..n-1``.
+
+    ``edges``: pairs of worker ids (either orientation). Validated: ids in range, no self-loop, no
+    duplicate edge, connected, two-colourable (an odd cycle raises a ``ValueError`` that names the
+    cycle's workers). ``heads=None`` takes the colour class of worker 0 as the heads; an explicit
+    ``heads`` must be one of the two colour classes.
+
+    ``neighbours(w)`` lists a worker's neighbours in ASCENDING worker id: that order is the order of
+    every neighbour sum of the GGADMM specification (algorithms/ggadmm.py). ``edges`` is normalised
+    to ``(head, tail)`` pairs, sorted. ``order`` is the launch order (heads ascending, then tails
+    ascending) and ``csr()`` the neighbour lists in that order."""
+
+    def __init__(self, n: int, edges: Sequence[Sequence[int]], heads: Optional[Sequence[int]] = None):
+        n = int(n)
+        if n < 2:
+            raise ValueError("a bipartite graph needs at least two workers, got %d" % n)
+        adj: List[List[int]] = [[] for _ in range(n)]
+        seen = set()
+        for e in edges:
+            if len(e) != 2:
+                raise ValueError("an edge is a pair of worker ids, got %r" % (e,))
+            a, b = int(e[0]), int(e[1])
+            if not (0 <= a < n and 0 <= b < n):
+                raise ValueError("edge (%d, %d): worker ids must be in 0..%d" % (a, b, n - 1))
+            if a == b:
+                raise ValueError("edge (%d, %d) is a self-loop" % (a, b))
+            key = (min(a, b), max(a, b))
+            if key in seen:
+                raise ValueError("duplicate edge (%d, %d)" % key)
+            seen.add(key)
+            adj[a].append(b)
+            adj[b].append(a)
+        for lst in adj:
+            lst.sort()
+        # breadth-first two-colouring from worker 0; parents give the odd cycle of a conflict
+        colour = [-1] * n
+        parent = [-1] * n
+        colour[0] = 0
+        queue = [0]
+        for u in queue:
+            for v in adj[u]:
+                if colour[v] < 0:
+                    colour[v] = 1 - colour[u]
+                    parent[v] = u
+                    queue.append(v)
+                elif colour[v] == colour[u]:
+                    raise ValueError("not bipartite: odd cycle through workers %s" % _odd_cycle(parent, u, v))
+        if len(queue) != n:
+            missing = [w for w in range(n) if colour[w] < 0]
+            raise ValueError("not connected: workers %s cannot be reached from worker 0" % missing)
+        class0 = [w for w in range(n) if colour[w] == 0]
+        class1 = [w for w in range(n) if colour[w] == 1]
+        if heads is None:
+            hs = class0
+        else:
+            hs = sorted(int(w) for w in heads)
+            if hs != class0 and hs != class1:
+                raise ValueError("heads %s is not a colour class of the graph (%s or %s)" % (hs, class0, class1))
+        self.n = n
+        self.heads: List[int] = hs
+        self.tails: List[int] = class1 if hs == class0 else class0
+        hset = set(self.heads)
+        self._adj = adj
+        self.is_head = [w in hset for w in range(n)]
+        self.edges: List[Tuple[int, int]] = sorted((a, b) if a in hset else (b, a) for a, b in seen)
+        self.degree: List[int] = [len(lst) for lst in adj]
+        self.max_degree: int = max(self.degree)
+        self.order: List[int] = self.heads + self.tails
+
+    def neighbours(self, w: int) -> List[int]:
+        return list(self._adj[int(w)])
+
+    def csr(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(nb_ptr (n + 1,), nb_idx (2 |E|,))`` int32: the neighbours (worker ids, ascending) of
+        ``order[k]`` are ``nb_idx[nb_ptr[k]:nb_ptr[k + 1]]``."""
+        ptr = np.zeros(self.n + 1, dtype=np.int32)
+        idx: List[int] = []
+        for k, w in enumerate(self.order):
+            idx += self._adj[w]
+            ptr[k + 1] = len(idx)
+        return ptr, np.asarray(idx, dtype=np.int32)
+
+    @property
+    def nb_ptr(self) -> np.ndarray:
+        return self.csr()[0]
+
+    @property
+    def nb_idx(self) -> np.ndarray:
+        return self.csr()[1]
+
+    def key(self) -> tuple:
+        """Hashable identity of (graph, role assignment)."""
+        return (self.n, tuple(self.edges), tuple(self.heads))
+
+    def describe(self) -> dict:
+        return {"n": self.n, "edges": [list(e) for e in self.edges], "max_degree": self.max_degree,
+                "heads": list(self.heads)}
+
+
+def _odd_cycle(parent: List[int], u: int, v: int) -> List[int]:
+    """The cycle closed by the edge (u, v) between two equally coloured workers of a BFS tree."""
+    pu, pv = [u], [v]
+    while parent[pu[-1]] >= 0:
+        pu.append(parent[pu[-1]])
+    while parent[pv[-1]] >= 0:
+        pv.append(parent[pv[-1]])
+    su = set(pu)
+    meet = next(w for w in pv if w in su)
+    return pu[:pu.index(meet) + 1] + pv[:pv.index(meet)][::-1]
+
+
+def graph_from_edges(n: int, edges: Sequence[Sequence[int]], heads: Optional[Sequence[int]] = None) -> BipartiteGraph:
+    return BipartiteGraph(n, edges, heads)
+
+
+def chain_graph(n: int, path: Optional[Sequence[int]] = None) -> BipartiteGraph:
+    """The chain ``path`` (position -> worker; default the identity): heads at even positions, as GADMM."""
+    p = list(range(n)) if path is None else [int(w) for w in path]
+    if sorted(p) != list(range(n)):
+        raise ValueError("a chain is a permutation of the workers")
+    return BipartiteGraph(n, [(p[k], p[k + 1]) for k in range(n - 1)], heads=p[0::2])
+
+
+def ring_graph(n: int) -> BipartiteGraph:
+    if n < 4 or n % 2:
+        raise ValueError("a bipartite ring needs an even number of workers >= 4, got %d" % n)
+    return BipartiteGraph(n, [(k, (k + 1) % n) for k in range(n)])
+
+
+def grid_graph(rows: int, cols: int) -> BipartiteGraph:
+    """``rows x cols`` lattice, worker ``r * cols + c`` at (r, c)."""
+    edges = []
+    for r in range(rows):
+        for c in range(cols):
+            if c + 1 < cols:
+                edges.append((r * cols + c, r * cols + c + 1))
+            if r + 1 < rows:
+                edges.append((r * cols + c, (r + 1) * cols + c))
+    return BipartiteGraph(rows * cols, edges)
+
+
+def star_graph(n: int, hub: int = 0) -> BipartiteGraph:
+    """Every worker joined to ``hub``; the colour class of worker 0 are the heads."""
+    if not 0 <= hub < n:
+        raise ValueError("hub %d not in 0..%d" % (hub, n - 1))
+    return BipartiteGraph(n, [(hub, w) for w in range(n) if w != hub])
+
+
+def complete_bipartite_graph(h: int, t: int) -> BipartiteGraph:
+    """K(h, t) over ``h + t`` workers with the sides interleaved: even ids against odd ids while both
+    last, the rest of the larger side after them (``h == t``: even vs odd ids). Heads: worker 0's side."""
+    if h < 1 or t < 1:
+        raise ValueError("both sides need a worker")
+    n, k = h + t, min(h, t)
+    side_a = list(range(0, 2 * k, 2)) + (list(range(2 * k, n)) if h > t else [])
+    side_b = [w for w in range(n) if w not in set(side_a)]
+    return BipartiteGraph(n, [(a, b) for a in side_a for b in side_b])
+
+
+def parse_graph(spec: str, n: int) -> BipartiteGraph:
+    """``"chain" | "ring" | "grid:RxC" | "star[:hub]" | "kbip"`` over ``n`` workers (kbip: even ids
+    against odd ids)."""
+    name, _, arg = str(spec).partition(":")
+    if name == "chain":
+        return chain_graph(n)
+    if name == "ring":
+        return ring_graph(n)
+    if name == "grid":
+        try:
+            r, c = (int(v) for v in arg.lower().split("x"))
+        except ValueError:
+            raise ValueError("grid graph: 'grid:RxC', got %r" % spec)
+        if r * c != n:
+            raise ValueError("grid %dx%d has %d workers, the problem %d" % (r, c, r * c, n))
+        return grid_graph(r, c)
+    if name == "star":
+        return star_graph(n, int(arg) if arg else 0)
+    if name == "kbip":
+        return complete_bipartite_graph((n + 1) // 2, n // 2)
+    raise ValueError("unknown graph %r (chain, ring, grid:RxC, star[:hub], kbip)" % spec)
