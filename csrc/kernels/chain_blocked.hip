@@ -1301,226 +1301,100 @@ int gadmm_chain_blocked_launch(const PersistArgs* args, hipStream_t st) {
 // Solves one launch of chain_blocked_sweep_kernel can run side by side (one per XCD).
 int gadmm_chain_blocked_sweep_capacity() { return 8; }
 
-// nb <= 8 independent static-chain solves (one GPU each, 12-wave layout, one DB class) in ONE launch,
-// solve j on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its
-// own ctl, trace, theta, mu, granule tables and xchk (per-XCD L2s are not coherent: two slots never
-// write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each, owned by the caller and
-// left alone until the stream has drained; the entries go up in one async copy ahead of the kernel.
-// -1: refused before any HIP call; -2: the workgroups cannot all be resident (as the single launch).
-int gadmm_chain_blocked_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, PersistArgs* dev_stage,
-                                     hipStream_t st) {
-  if (nb < 1 || nb > gadmm_chain_blocked_sweep_capacity()) {
-    gadmm_set_error("blocked sweep: %d solves, one launch takes 1..%d", nb, gadmm_chain_blocked_sweep_capacity());
-    return -1;
-  }
-  if (!batch || !host_stage || !dev_stage) {
-    gadmm_set_error("blocked sweep: null batch or staging buffer");
-    return -1;
-  }
-  int blocks[8], max_blocks = 0, sum_blocks = 0;
-  long lds = gadmm_chain_blocked_lds(0, 0);
+// nb <= 8 independent solves (one GPU each, 12-wave layout, one DB class) in ONE launch, solve j on the
+// blocks b % 8 == j: static chains on chain_blocked_sweep_kernel, or (dyn) D-GADMM epoch chunks on
+// chain_blocked_dyn_sweep_kernel, first chunks and continuations (cont) side by side. Every entry passes
+// the single launch's checks -- a dynamic one those of the single dynamic launch (epoch tables, padded
+// inverse image, 1..EPL epochs, hard stop at or after the start) -- and each must name its own ctl, trace,
+// theta, mu, granule tables and xchk (gadmm_sweep_shares). Staging buffers and the residency refusal
+// (-2): gadmm_sweep_launch. -1: refused before any HIP call.
+static int blocked_sweep_launch(bool dyn, const PersistArgs* batch, int nb, PersistArgs* host_stage,
+                                PersistArgs* dev_stage, hipStream_t st) {
+  const char* name = dyn ? "blocked dynamic sweep" : "blocked sweep";
+  if (!gadmm_sweep_batch_ok(name, batch, nb, gadmm_chain_blocked_sweep_capacity(), host_stage, dev_stage)) return -1;
+  int blocks[8];
+  long lds = gadmm_chain_blocked_lds(0, 0) + (dyn ? DYN_LDS_BYTES : 0);  // + the staged epoch tables
   for (int j = 1; j < nb; ++j)
     if ((batch[j].d <= 32) != (batch[0].d <= 32)) {
-      gadmm_set_error("blocked sweep: solves of different register classes (d = %d and %d; d <= 32 or 33..52)",
-                      batch[0].d, batch[j].d);
+      gadmm_set_error("%s: solves of different register classes (d = %d and %d; d <= 32 or 33..52)", name, batch[0].d,
+                      batch[j].d);
       return -1;
     }
   for (int j = 0; j < nb; ++j) {
     const PersistArgs& a = batch[j];
-    if (a.nranks > 1 || a.sys_scope || a.n_epochs > 0 || a.blk_pw == 2 || a.timeline || a.blk_dl || a.dl_halo ||
-        a.blk_npeer != 0 || a.hard_stop != 0 || a.cont) {
-      gadmm_set_error("blocked sweep: solve %d is multi-rank, system-scope, dynamic, paired-wave, instrumented or "
-                      "data-local (one-GPU static 12-wave solves only)", j);
+    if (dyn && a.n_epochs < 1) {
+      gadmm_set_error("%s: solve %d is static (no epochs): it belongs in the static sweep", name, j);
       return -1;
     }
+    if (a.nranks > 1 || a.sys_scope || a.blk_pw == 2 || a.timeline || a.blk_dl || a.dl_halo || a.blk_npeer != 0 ||
+        (!dyn && (a.n_epochs > 0 || a.hard_stop != 0 || a.cont))) {
+      gadmm_set_error(dyn ? "%s: solve %d is multi-rank, system-scope, paired-wave, instrumented or data-local "
+                            "(one-GPU 12-wave solves only)"
+                          : "%s: solve %d is multi-rank, system-scope, dynamic, paired-wave, instrumented or "
+                            "data-local (one-GPU static 12-wave solves only)", name, j);
+      return -1;
+    }
+    if (dyn) {
+      if (a.n_epochs > EPL) {
+        gadmm_set_error("%s: solve %d has %d epochs, a launch stages at most %d", name, j, a.n_epochs, EPL);
+        return -1;
+      }
+      if (!a.epoch_start || !a.ep_slots || !a.ep_pos || !a.ep_flush || !a.minv_pad) {
+        gadmm_set_error("%s: solve %d lacks epoch tables or the padded inverse image (gadmm_chain_blocked_pad_len)",
+                        name, j);
+        return -1;
+      }
+      if (a.hard_stop < 0 || (a.hard_stop > 0 && a.hard_stop < a.start_iter)) {
+        gadmm_set_error("%s: solve %d: hard stop %d before its start %d", name, j, a.hard_stop, a.start_iter);
+        return -1;
+      }
+    }
     if (!a.xchk) {
-      gadmm_set_error("blocked sweep: solve %d has no placement-check buffer (xchk)", j);
+      gadmm_set_error("%s: solve %d has no placement-check buffer (xchk)", name, j);
       return -1;
     }
     if (a.blk_k < 1 || a.blk_len < 1 || a.blk_len + 4 * a.blk_k > MAXW || a.d < 1 || a.d > 52 || a.n < 2 ||
         !a.blk_tab || !a.dec_push || !a.objg || !a.decg || !a.ctl || !a.trace || !a.theta || !a.mu || !a.slots ||
         !a.Minv || !a.A || !a.b || !a.yy || !a.has_monitor || a.n != a.n_local) {
-      gadmm_set_error("blocked sweep: solve %d: unsupported configuration", j);
+      gadmm_set_error("%s: solve %d: unsupported configuration", name, j);
       return -1;
     }
-    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-      gadmm_set_error("blocked sweep: solve %d: ring/lag/tag range", j);
+    if (gadmm_range_defects(a)) {
+      gadmm_set_error("%s: solve %d: ring/lag/tag range", name, j);
       return -1;
     }
-    for (int i = 0; i < j; ++i) {
-      const PersistArgs& o = batch[i];
-      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.blk_tab == a.blk_tab ||
-          o.objg == a.objg || o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp)) {
-        gadmm_set_error("blocked sweep: solves %d and %d share a buffer that both write", i, j);
+    for (int i = 0; i < j; ++i)
+      if (gadmm_sweep_shares(a, batch[i]) || batch[i].blk_tab == a.blk_tab) {
+        gadmm_set_error("%s: solves %d and %d share a buffer that both write", name, i, j);
         return -1;
       }
-    }
     const int W = (a.n + a.blk_len - 1) / a.blk_len, Wo = (a.n + MAXW - 1) / MAXW;
     blocks[j] = W + Wo + 1;
     if (blocks[j] > XCHK) {
-      gadmm_set_error("blocked sweep: solve %d has %d workgroups, the placement check holds %d", j, blocks[j], XCHK);
+      gadmm_set_error("%s: solve %d has %d workgroups, the placement check holds %d", name, j, blocks[j], XCHK);
       return -1;
     }
-    sum_blocks += blocks[j];
-    if (blocks[j] > max_blocks) max_blocks = blocks[j];
     if (lds < (long)a.n * 8) lds = (long)a.n * 8;
   }
   if (lds > 160 * 1024) {
-    gadmm_set_error("blocked sweep: %ld B of LDS", lds);
+    gadmm_set_error("%s: %ld B of LDS", name, lds);
     return -1;
   }
-  const void* fn = batch[0].d <= 32 ? (const void*)chain_blocked_sweep_kernel<32> : (const void*)chain_blocked_sweep_kernel<52>;
-  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
-  // its 8-strided blocks are dealt to
-  const long cap = gadmm_resident_capacity(fn, 64 * MAXW, (size_t)lds);
-  const long cus_xcd = gadmm_cu_count() / 8;
-  if (sum_blocks > cap) {
-    gadmm_set_error("blocked sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
-    return -2;
-  }
-  for (int j = 0; j < nb; ++j)
-    if (blocks[j] > cus_xcd) {
-      gadmm_set_error("blocked sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
-      return -2;
-    }
-  if (lds > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int dbg = 0, xenv = -1;
-  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
-  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
-  for (int j = 0; j < nb; ++j) {
-    PersistArgs& ka = host_stage[j];
-    ka = batch[j];
-    ka.dbg = dbg;
-    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
-    const int x = xenv >= 0 ? xenv : ka.xcd;
-    ka.xcd = x >= 2 ? 2 : 1;
-    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
-  }
-  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
-  const PersistArgs* dbatch = dev_stage;
-  void* kargs[] = {&dbatch, &nb};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64 * MAXW), kargs, (size_t)lds, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  const bool small = batch[0].d <= 32;
+  const void* fn = !dyn ? (small ? (const void*)chain_blocked_sweep_kernel<32> : (const void*)chain_blocked_sweep_kernel<52>)
+                        : (small ? (const void*)chain_blocked_dyn_sweep_kernel<32> : (const void*)chain_blocked_dyn_sweep_kernel<52>);
+  return gadmm_sweep_launch({fn, 64 * MAXW, (size_t)lds, name, true}, batch, nb, blocks, host_stage, dev_stage, st);
 }
 
-// nb <= 8 independent D-GADMM epoch chunks (one GPU each, 12-wave layout, one DB class) in ONE launch of
-// chain_blocked_dyn_sweep_kernel, chunk j on the blocks b % 8 == j. Every entry passes the checks of the
-// single dynamic launch (epoch tables, padded inverse image, 1..EPL epochs, hard stop at or after the
-// start) and of the static sweep (own written buffers and xchk, block counts, residency); a static entry
-// (n_epochs == 0) belongs in gadmm_chain_blocked_sweep_launch. Entries may be first chunks and
-// continuations (cont) side by side. Staging buffers and return codes as the static sweep launcher.
+int gadmm_chain_blocked_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, PersistArgs* dev_stage,
+                                     hipStream_t st) {
+  return blocked_sweep_launch(false, batch, nb, host_stage, dev_stage, st);
+}
+
+// A static entry (n_epochs == 0) belongs in gadmm_chain_blocked_sweep_launch.
 int gadmm_chain_blocked_dyn_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage,
                                          PersistArgs* dev_stage, hipStream_t st) {
-  if (nb < 1 || nb > gadmm_chain_blocked_sweep_capacity()) {
-    gadmm_set_error("blocked dynamic sweep: %d solves, one launch takes 1..%d", nb, gadmm_chain_blocked_sweep_capacity());
-    return -1;
-  }
-  if (!batch || !host_stage || !dev_stage) {
-    gadmm_set_error("blocked dynamic sweep: null batch or staging buffer");
-    return -1;
-  }
-  int blocks[8], max_blocks = 0, sum_blocks = 0;
-  long lds = gadmm_chain_blocked_lds(0, 0) + DYN_LDS_BYTES;  // + the staged epoch tables
-  for (int j = 1; j < nb; ++j)
-    if ((batch[j].d <= 32) != (batch[0].d <= 32)) {
-      gadmm_set_error("blocked dynamic sweep: solves of different register classes (d = %d and %d; d <= 32 or "
-                      "33..52)", batch[0].d, batch[j].d);
-      return -1;
-    }
-  for (int j = 0; j < nb; ++j) {
-    const PersistArgs& a = batch[j];
-    if (a.n_epochs < 1) {
-      gadmm_set_error("blocked dynamic sweep: solve %d is static (no epochs): it belongs in the static sweep", j);
-      return -1;
-    }
-    if (a.nranks > 1 || a.sys_scope || a.blk_pw == 2 || a.timeline || a.blk_dl || a.dl_halo || a.blk_npeer != 0) {
-      gadmm_set_error("blocked dynamic sweep: solve %d is multi-rank, system-scope, paired-wave, instrumented or "
-                      "data-local (one-GPU 12-wave solves only)", j);
-      return -1;
-    }
-    if (a.n_epochs > EPL) {
-      gadmm_set_error("blocked dynamic sweep: solve %d has %d epochs, a launch stages at most %d", j, a.n_epochs, EPL);
-      return -1;
-    }
-    if (!a.epoch_start || !a.ep_slots || !a.ep_pos || !a.ep_flush || !a.minv_pad) {
-      gadmm_set_error("blocked dynamic sweep: solve %d lacks epoch tables or the padded inverse image "
-                      "(gadmm_chain_blocked_pad_len)", j);
-      return -1;
-    }
-    if (a.hard_stop < 0 || (a.hard_stop > 0 && a.hard_stop < a.start_iter)) {
-      gadmm_set_error("blocked dynamic sweep: solve %d: hard stop %d before its start %d", j, a.hard_stop, a.start_iter);
-      return -1;
-    }
-    if (!a.xchk) {
-      gadmm_set_error("blocked dynamic sweep: solve %d has no placement-check buffer (xchk)", j);
-      return -1;
-    }
-    if (a.blk_k < 1 || a.blk_len < 1 || a.blk_len + 4 * a.blk_k > MAXW || a.d < 1 || a.d > 52 || a.n < 2 ||
-        !a.blk_tab || !a.dec_push || !a.objg || !a.decg || !a.ctl || !a.trace || !a.theta || !a.mu || !a.slots ||
-        !a.Minv || !a.A || !a.b || !a.yy || !a.has_monitor || a.n != a.n_local) {
-      gadmm_set_error("blocked dynamic sweep: solve %d: unsupported configuration", j);
-      return -1;
-    }
-    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-      gadmm_set_error("blocked dynamic sweep: solve %d: ring/lag/tag range", j);
-      return -1;
-    }
-    for (int i = 0; i < j; ++i) {
-      const PersistArgs& o = batch[i];
-      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.blk_tab == a.blk_tab ||
-          o.objg == a.objg || o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) ||
-          (a.rres && o.rres == a.rres)) {
-        gadmm_set_error("blocked dynamic sweep: solves %d and %d share a buffer that both write", i, j);
-        return -1;
-      }
-    }
-    const int W = (a.n + a.blk_len - 1) / a.blk_len, Wo = (a.n + MAXW - 1) / MAXW;
-    blocks[j] = W + Wo + 1;
-    if (blocks[j] > XCHK) {
-      gadmm_set_error("blocked dynamic sweep: solve %d has %d workgroups, the placement check holds %d", j, blocks[j],
-                      XCHK);
-      return -1;
-    }
-    sum_blocks += blocks[j];
-    if (blocks[j] > max_blocks) max_blocks = blocks[j];
-    if (lds < (long)a.n * 8) lds = (long)a.n * 8;
-  }
-  if (lds > 160 * 1024) {
-    gadmm_set_error("blocked dynamic sweep: %ld B of LDS", lds);
-    return -1;
-  }
-  const void* fn = batch[0].d <= 32 ? (const void*)chain_blocked_dyn_sweep_kernel<32>
-                                    : (const void*)chain_blocked_dyn_sweep_kernel<52>;
-  const long cap = gadmm_resident_capacity(fn, 64 * MAXW, (size_t)lds);
-  const long cus_xcd = gadmm_cu_count() / 8;
-  if (sum_blocks > cap) {
-    gadmm_set_error("blocked dynamic sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
-    return -2;
-  }
-  for (int j = 0; j < nb; ++j)
-    if (blocks[j] > cus_xcd) {
-      gadmm_set_error("blocked dynamic sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
-      return -2;
-    }
-  if (lds > 65536) GADMM_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int dbg = 0, xenv = -1;
-  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
-  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
-  for (int j = 0; j < nb; ++j) {
-    PersistArgs& ka = host_stage[j];
-    ka = batch[j];
-    ka.dbg = dbg;
-    const int x = xenv >= 0 ? xenv : ka.xcd;  // the 8-strided layout is inherent to a sweep (see above)
-    ka.xcd = x >= 2 ? 2 : 1;
-    ka.xtag = (int)gadmm_next_xtag();  // fresh per slot and per launch: a continuation re-runs the check
-  }
-  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
-  const PersistArgs* dbatch = dev_stage;
-  void* kargs[] = {&dbatch, &nb};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64 * MAXW), kargs, (size_t)lds, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return blocked_sweep_launch(true, batch, nb, host_stage, dev_stage, st);
 }
 
 }  // extern "C"

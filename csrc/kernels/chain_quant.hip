@@ -635,32 +635,24 @@ bool q_entry_ok(const PersistArgs& a, const char* who) {
 
 // nb <= 8 independent Q-GADMM solves (one GPU each, one QT class: d <= 52 or 53..64) in ONE launch, solve j
 // on the blocks b % 8 == j. Every entry passes the single launch's checks; each must name its own ctl,
-// trace, theta, mu, true theta, message table, objective / decision rings and xchk (per-XCD L2s are not
-// coherent: two slots never write one buffer). host_stage (pinned) / dev_stage: nb PersistArgs each,
-// owned by the caller and left alone until the stream has drained; the entries go up in one async copy
-// ahead of the kernel. -1: refused before any HIP call; -2: the workgroups cannot all be resident.
+// trace, theta, mu, true theta, message table, objective / decision rings and xchk (gadmm_sweep_shares
+// and the buffers only these kernels write). Staging buffers and the residency refusal (-2):
+// gadmm_sweep_launch. -1: refused before any HIP call.
 int q_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st) {
-  if (nb < 1 || nb > Q_SWEEP_CAPACITY) {
-    gadmm_set_error("persistent " Q_NAME " sweep: %d solves, one launch takes 1..%d", nb,
-                    Q_SWEEP_CAPACITY);
-    return -1;
-  }
-  if (!batch || !host_stage || !dev_stage) {
-    gadmm_set_error("persistent " Q_NAME " sweep: null batch or staging buffer");
-    return -1;
-  }
+  const char* name = "persistent " Q_NAME " sweep";
+  if (!gadmm_sweep_batch_ok(name, batch, nb, Q_SWEEP_CAPACITY, host_stage, dev_stage)) return -1;
   for (int j = 1; j < nb; ++j)
     if ((batch[j].d <= 52) != (batch[0].d <= 52)) {
-      gadmm_set_error("persistent " Q_NAME " sweep: solves of different register classes (d = %d and %d; d <= 52 or 53..64)",
-                      batch[0].d, batch[j].d);
+      gadmm_set_error("%s: solves of different register classes (d = %d and %d; d <= 52 or 53..64)", name, batch[0].d,
+                      batch[j].d);
       return -1;
     }
-  int blocks[8], max_blocks = 0, sum_blocks = 0;
+  int blocks[8];
   size_t shm = 0;
   for (int j = 0; j < nb; ++j) {
     const PersistArgs& a = batch[j];
     char who[48];
-    snprintf(who, sizeof(who), "persistent " Q_NAME " sweep: solve %d", j);
+    snprintf(who, sizeof(who), "%s: solve %d", name, j);
     if (!q_entry_ok(a, who)) return -1;
     if (!a.trace || !a.b || !a.yy) {  // (the single launch leaves these to its one caller)
       gadmm_set_error("%s: a required buffer is null", who);
@@ -677,54 +669,21 @@ int q_sweep_launch(const PersistArgs* batch, int nb, PersistArgs* host_stage, Pe
     }
     for (int i = 0; i < j; ++i) {
       const PersistArgs& o = batch[i];
-      if (o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.qg == a.qg ||
-          (a.q_true && o.q_true == a.q_true) || o.objg == a.objg || o.decg == a.decg || o.dec_push == a.dec_push ||
-          o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres) ||
+      if (gadmm_sweep_shares(a, o) || o.qg == a.qg || (a.q_true && o.q_true == a.q_true) || o.dec_push == a.dec_push ||
           (CENS_TU && o.c_sent == a.c_sent)) {
-        gadmm_set_error("persistent " Q_NAME " sweep: solves %d and %d share a buffer that both write", i, j);
+        gadmm_set_error("%s: solves %d and %d share a buffer that both write", name, i, j);
         return -1;
       }
     }
-    // the ranges gadmm_persist_launch checks for the single launch
-    if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+    if (gadmm_range_defects(a)) {  // last of a slot's checks (tests/test_qsweep_cpu.py builds on that)
       gadmm_set_error("%s: ring/lag/tag range", who);
       return -1;
     }
-    sum_blocks += blocks[j];
-    if (blocks[j] > max_blocks) max_blocks = blocks[j];
     const size_t need = pick_q_variant(a).shm;
     if (need > shm) shm = need;
   }
   const void* fn = batch[0].d <= 52 ? (const void*)Q_SWEEP_KERNEL<13> : (const void*)Q_SWEEP_KERNEL<16>;
-  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
-  // its 8-strided blocks are dealt to
-  const long cap = gadmm_resident_capacity(fn, 64, shm);
-  const long cus_xcd = gadmm_cu_count() / 8;
-  if (sum_blocks > cap) {
-    gadmm_set_error("persistent " Q_NAME " sweep: %d workgroups but only %ld can be resident", sum_blocks, cap);
-    return -2;
-  }
-  for (int j = 0; j < nb; ++j)
-    if (blocks[j] > cus_xcd) {
-      gadmm_set_error("persistent " Q_NAME " sweep: solve %d has %d workgroups but an XCD has %ld CUs", j, blocks[j], cus_xcd);
-      return -2;
-    }
-  int xenv = -1;
-  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
-  for (int j = 0; j < nb; ++j) {
-    PersistArgs& ka = host_stage[j];
-    ka = batch[j];
-    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
-    const int x = xenv >= 0 ? xenv : ka.xcd;
-    ka.xcd = x >= 2 ? 2 : 1;
-    ka.xtag = (int)gadmm_next_xtag();  // fresh placement-check tag per slot: no memset of xchk
-  }
-  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
-  const PersistArgs* dbatch = dev_stage;
-  void* kargs[] = {&dbatch, &nb};
-  GADMM_CHECK(hipLaunchKernel(fn, dim3(8 * max_blocks), dim3(64), kargs, shm, st));
-  GADMM_CHECK(hipGetLastError());
-  return 0;
+  return gadmm_sweep_launch({fn, 64, shm, name, false}, batch, nb, blocks, host_stage, dev_stage, st);
 }
 
 }  // namespace

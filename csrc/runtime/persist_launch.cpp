@@ -1,5 +1,6 @@
 // Host side of the persistent (single-launch) kernels: how many workgroups can be resident, the XCD
-// packing mode of a launch, and the launch sequence the chain launchers share (persist_launch.h).
+// packing mode of a launch, the launch sequence the chain launchers share, and the one the sweep
+// launchers (up to eight solves in one launch, one per XCD) share (persist_launch.h).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <atomic>
@@ -79,12 +80,18 @@ extern "C" unsigned gadmm_next_xtag() {
   return 0x80000000u | ((launches.fetch_add(1, std::memory_order_relaxed) + 1u) & 0x7fffffffu);
 }
 
+int gadmm_range_defects(const PersistArgs& a) {
+  return (a.lag < 1 ? RANGE_LAG : 0) | (a.ring <= a.lag + 1 ? RANGE_RING : 0) |
+         (a.start_iter + a.max_iter + a.lag >= (1 << 20) ? RANGE_TAGS : 0);
+}
+
 int gadmm_persist_launch(const PersistLaunch& l, PersistArgs* ka, void** kargs, hipStream_t st) {
-  if (ka->ring <= ka->lag + 1) {
+  const int bad = gadmm_range_defects(*ka);  // (a launcher whose kernel needs lag >= 1 says so itself)
+  if (bad & RANGE_RING) {
     gadmm_set_error("%s: ring must exceed lag + 1", l.name);
     return -1;
   }
-  if (ka->start_iter + ka->max_iter + ka->lag >= (1 << 20)) {
+  if (bad & RANGE_TAGS) {
     gadmm_set_error("%s: iteration tags limited to 2^20", l.name);
     return -1;
   }
@@ -97,6 +104,66 @@ int gadmm_persist_launch(const PersistLaunch& l, PersistArgs* ka, void** kargs, 
   ka->xcd = l.pack ? gadmm_xcd_mode(ka, l.blocks, cap) : 0;
   ka->xtag = (int)gadmm_next_xtag();  // fresh placement-check tag: no memset of xchk
   GADMM_CHECK(hipLaunchKernel(l.fn, dim3(ka->xcd > 0 ? 8 * l.blocks : l.blocks), dim3(l.threads), kargs, l.shm, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}
+
+bool gadmm_sweep_batch_ok(const char* name, const void* batch, int nb, int cap, const void* host_stage,
+                          const void* dev_stage) {
+  if (nb < 1 || nb > cap) {
+    gadmm_set_error("%s: %d solves, one launch takes 1..%d", name, nb, cap);
+    return false;
+  }
+  if (!batch || !host_stage || !dev_stage) {
+    gadmm_set_error("%s: null batch or staging buffer", name);
+    return false;
+  }
+  return true;
+}
+
+bool gadmm_sweep_shares(const PersistArgs& a, const PersistArgs& o) {
+  return o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || o.objg == a.objg ||
+         o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres);
+}
+
+int gadmm_sweep_launch(const SweepLaunch& l, const PersistArgs* batch, int nb, const int* blocks,
+                       PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st) {
+  int max_blocks = 0, sum_blocks = 0;
+  for (int j = 0; j < nb; ++j) {
+    sum_blocks += blocks[j];
+    if (blocks[j] > max_blocks) max_blocks = blocks[j];
+  }
+  // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
+  // its 8-strided blocks are dealt to
+  const long cap = gadmm_resident_capacity(l.fn, l.threads, l.shm);
+  const long cus_xcd = gadmm_cu_count() / 8;
+  if (sum_blocks > cap) {
+    gadmm_set_error("%s: %d workgroups but only %ld can be resident", l.name, sum_blocks, cap);
+    return -2;
+  }
+  for (int j = 0; j < nb; ++j)
+    if (blocks[j] > cus_xcd) {
+      gadmm_set_error("%s: solve %d has %d workgroups but an XCD has %ld CUs", l.name, j, blocks[j], cus_xcd);
+      return -2;
+    }
+  if (l.shm > 65536) GADMM_CHECK(hipFuncSetAttribute(l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.shm));
+  int dbg = 0, xenv = -1;
+  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
+  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
+  for (int j = 0; j < nb; ++j) {
+    PersistArgs& ka = host_stage[j];
+    ka = batch[j];
+    if (l.dbg) ka.dbg = dbg;
+    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
+    const int x = xenv >= 0 ? xenv : ka.xcd;
+    ka.xcd = x >= 2 ? 2 : 1;
+    // fresh placement-check tag per slot and per launch (a continuation re-runs the check): no memset of xchk
+    ka.xtag = (int)gadmm_next_xtag();
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
+  const PersistArgs* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb};
+  GADMM_CHECK(hipLaunchKernel(l.fn, dim3(8 * max_blocks), dim3(l.threads), kargs, l.shm, st));
   GADMM_CHECK(hipGetLastError());
   return 0;
 }

@@ -18,6 +18,8 @@ Two executions of the same schedule:
   plumbing, torch.distributed on GPU, single process);
 * ``backend='native'``: the C++/HIP chain engine (graph-replayed fused phase kernels with RCCL
   p2p, or the persistent single-launch kernel on one GPU). ``'auto'`` picks native on a HIP device.
+
+Many solves side by side in one launch (``chain_admm_sweep`` and its kin): algorithms/sweeps.py.
 """
 from __future__ import annotations
 
@@ -118,134 +120,6 @@ def chain_admm(model, local_ids: Sequence[int], n_total: int, rho: float, obj0: 
     return _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
                              local_solver, step, max_inner, inner_tol, cost_quirk, name, record_theta, state,
                              check_exchange, failures)
-
-
-def sweep_groups(n: int, width: int) -> List[List[int]]:
-    """Indices 0..n-1 in consecutive groups of at most ``width`` (one group per sweep launch)."""
-    if width < 1:
-        raise ValueError("sweep width must be >= 1")
-    return [list(range(i, min(i + width, n))) for i in range(0, n, width)]
-
-
-def run_in_groups(items: Sequence, width: int, run_group) -> list:
-    """``run_group(group_items, group_indices)`` per ``sweep_groups`` group; the results in input order."""
-    out = [None] * len(items)
-    for g in sweep_groups(len(items), width):
-        res = run_group([items[i] for i in g], g)
-        if len(res) != len(g):
-            raise RuntimeError("a sweep group of %d returned %d results" % (len(g), len(res)))
-        for i, r in zip(g, res):
-            out[i] = r
-    return out
-
-
-def chain_admm_sweep(model, local_ids: Sequence[int], n_total: int, rhos: Sequence[float], obj0: float, tol: float,
-                     max_iter: int, *, tols: Optional[Sequence[float]] = None, placement: Optional[Placement] = None,
-                     backend: str = "auto", name: str = "GADMM", engine_opts: Optional[dict] = None,
-                     comm: Optional[Comm] = None) -> List[RunResult]:
-    """The static-chain closed-form GADMM solve at every rho of ``rhos``: one ``RunResult`` per rho, in
-    the order given, equal to ``[chain_admm(model, ..., rho, ...) for rho in rhos]``. On one HIP device
-    the solves run side by side, up to eight per kernel launch, one per XCD
-    (engine/chain_sweep.py; more values run in groups), each to its own stop: ``tols`` gives one
-    tolerance per rho (default ``tol`` for all). Each result then carries ``extra['sweep'] = {width,
-    slot, kernel, placed, wall_ms_launch}`` and its ``wall_s`` is that solve's OWN time: the wall
-    clock of its launch (set-up, launch, read-back) less the device time between its stop decision and
-    the last member's, so the slowest member's equals the launch's; ``time_trace`` is each curve's own
-    device clock. ``extra['state']`` is not produced (a caller that checkpoints runs ``chain_admm``).
-    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, a shape the sweep kernel does not
-    take, or a device that cannot hold the group's workgroups -- it IS that loop, and every result
-    records ``extra['sweep_fallback'] = reason``. ``engine_opts``: ``refresh`` (recompute Gram +
-    inverses from the raw shards first), ``residual``, ``cache``, as in ``chain_admm``."""
-    rhos = [float(r) for r in rhos]
-    opts = dict(engine_opts or {})
-    tols = [float(tol)] * len(rhos) if tols is None else [float(t) for t in tols]
-    if len(tols) != len(rhos):
-        raise ValueError("tols: one per rho")
-    nranks = comm.nranks if comm is not None else 1
-
-    def sequential(reason: str) -> List[RunResult]:
-        out = []
-        for rho, t in zip(rhos, tols):
-            r = chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
-                           backend=backend, name=name, engine_opts=engine_opts)
-            r.extra["sweep_fallback"] = reason
-            out.append(r)
-        return out
-
-    if not rhos:
-        return []
-    if model.device.type != "cuda":
-        return sequential("cpu tensors")
-    if backend == "torch":
-        return sequential("torch backend")
-    if nranks > 1:
-        return sequential("several ranks")
-    if model.kind != "linear" or sorted(int(w) for w in local_ids) != list(range(n_total)):
-        return sequential("not a one-GPU linear closed-form chain")
-    if getenv("GADMM_CHECK_EXCHANGE", "0") == "1":
-        return sequential("exchange checker")
-    from ..ops import native
-    if not native.available():
-        return sequential("native library unavailable")
-    from ..engine.chain_engine import ResidencyError
-    from ..engine.chain_sweep import ChainSweepEngine, sweep_capacity
-
-    refresh = bool(opts.get("refresh", False))
-    residual = bool(opts.get("residual", True))
-
-    def run_group(g_rhos, idx):
-        t_begin = time.perf_counter()
-        g_tols = [tols[i] for i in idx]
-        key = ("sweep", n_total, tuple(map(int, local_ids)), tuple(g_rhos), int(max_iter), residual)
-        cache = getattr(model, "_chain_engines", None)
-        sw = cache.get(key) if cache is not None else None
-        if sw is None:
-            if refresh:
-                from ..ops.linalg import gram
-                gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
-            sw = ChainSweepEngine.rho_sweep(model.X, model.y, local_ids, n_total, g_rhos, obj0=obj0, tols=g_tols,
-                                            max_iters=max_iter, precomputed=(model.A, model.b, model.yy),
-                                            placement=placement, residual=residual)
-            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
-            if opts.get("cache", True):
-                if cache is None:
-                    cache = {}
-                    model._chain_engines = cache
-                cache[key] = sw
-        else:
-            sw.set_targets(obj0, g_tols)
-            if refresh:
-                sw.refresh(model.X, model.y)
-        runs = sw.run()
-        wall = time.perf_counter() - t_begin
-        ticks = sw.stop_ticks(runs)
-        last = max(ticks)
-        out = []
-        for j, (m, r, rho) in enumerate(zip(sw.members, runs, g_rhos)):
-            iters, done = int(r.iters), int(r.done)
-            tr, tt = m.traces(iters)
-            own = wall - (last - ticks[j]) * 1e-8 if ticks[j] > 0 else wall
-            res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(done == 1),
-                            wall_s=own, time_trace=tt,
-                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
-                            com_cost=np.arange(1, iters + 1) * 0.0, bytes_sent=0, bytes_total=0,
-                            primal_res=m.primal_residual(iters),
-                            extra={"backend": "native", "engine": "persistent", "rank": 0, "nranks": 1,
-                                   "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0, "transport": "local",
-                                   "obj_mode": m.obj_mode_name, "engine_obj": m,
-                                   "sweep": {"width": len(g_rhos), "slot": j, "kernel": sw.last_kernel,
-                                             "placed": int(sw.last_placed[j]), "wall_ms_launch": sw.last_wall_ms},
-                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j})
-            out.append(res)
-        return out
-
-    try:
-        with roctx_range("%s sweep native N=%d K=%d" % (name, n_total, len(rhos))):
-            return run_in_groups(rhos, sweep_capacity(), run_group)
-    except ResidencyError as e:
-        return sequential("ResidencyError: %s" % e)
-    except ValueError as e:  # a shape the sweep kernel does not take (d > 52, no blocked plan, ...)
-        return sequential("not eligible: %s" % e)
 
 
 def _chain_admm_torch(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule,
@@ -1199,142 +1073,6 @@ def censored_quantized_group_admm(model, rho, obj0, acc, max_iter, bits, tau0, x
     return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, quantize=(bits, seed), censor=(tau0, xi), **kw)
 
 
-def _sweep_member(cfg):
-    """A sweep member ``(rho, bits, seed)`` or ``(rho, bits, seed, tau0, xi)`` as ``((rho, bits, seed),
-    censor or None)``."""
-    from .quantize import check_censor
-    if len(cfg) == 3:
-        return (float(cfg[0]), int(cfg[1]), int(cfg[2])), None
-    if len(cfg) == 5:
-        return (float(cfg[0]), int(cfg[1]), int(cfg[2])), check_censor(cfg[3:])
-    raise ValueError("a Q sweep member is (rho, bits, seed) or (rho, bits, seed, tau0, xi), got %r" % (tuple(cfg),))
-
-
-def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float, max_iter: int, *,
-                               tols: Optional[Sequence[float]] = None, placement: Optional[Placement] = None,
-                               backend: str = "auto", name: str = "Q-GADMM", engine_opts: Optional[dict] = None,
-                               comm: Optional[Comm] = None, n_total: Optional[int] = None,
-                               local_ids: Optional[Sequence[int]] = None) -> List[RunResult]:
-    """Q-GADMM on a static chain under every ``(rho, bits, seed)`` of ``configs``: one ``RunResult`` per
-    config, in the order given, equal to ``[chain_admm(model, ..., rho, ..., quantize=(bits, seed)) for
-    ...]``. On one HIP device the solves run side by side, up to eight per kernel launch, one per XCD
-    (engine/quant_sweep.py; more configs run in groups), each to its own stop: ``tols`` gives one
-    tolerance per config (default ``tol`` for all). Each result then carries the single native Q
-    solve's fields plus ``extra['sweep'] = {width, slot, kernel, placed, wall_ms_launch}``, and its
-    ``wall_s`` is that solve's OWN time (as ``chain_admm_sweep``: the wall clock of its launch less the
-    device time between its stop decision and the last member's). ``extra['state']`` is not produced.
-    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, the exchange checker, no native
-    library, a non-linear model, not every worker local, d > 64, or a device that cannot hold the
-    group's workgroups -- it IS that loop, and every result records ``extra['sweep_fallback'] =
-    reason``. A hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``, as in ``chain_admm``.
-    A member may also be ``(rho, bits, seed, tau0, xi)``: CQ-GADMM, equal to its own ``chain_admm(...,
-    quantize=(bits, seed), censor=(tau0, xi))``. A group with at least one censored member runs on the
-    censored sweep kernel, where an uncensored member gets an all-zero threshold table and so stays
-    Q-GADMM bit for bit; a group without one runs on the Q sweep kernel as before."""
-    members = [_sweep_member(c) for c in configs]
-    configs = [m[0] for m in members]
-    censors = [m[1] for m in members]
-    opts = dict(engine_opts or {})
-    n_total = model.n_local if n_total is None else int(n_total)
-    local_ids = list(range(model.n_local)) if local_ids is None else [int(w) for w in local_ids]
-    tols = [float(tol)] * len(configs) if tols is None else [float(t) for t in tols]
-    if len(tols) != len(configs):
-        raise ValueError("tols: one per config")
-    nranks = comm.nranks if comm is not None else 1
-
-    def sequential(reason: str) -> List[RunResult]:
-        out = []
-        for (rho, bits, seed), cen, t in zip(configs, censors, tols):
-            r = chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
-                           backend=backend, name=name, engine_opts=engine_opts, quantize=(bits, seed), censor=cen)
-            r.extra["sweep_fallback"] = reason
-            out.append(r)
-        return out
-
-    if not configs:
-        return []
-    if model.device.type != "cuda":
-        return sequential("cpu tensors")
-    if backend == "torch":
-        return sequential("torch backend")
-    if nranks > 1:
-        return sequential("several ranks")
-    if getenv("GADMM_CHECK_EXCHANGE", "0") == "1":
-        return sequential("exchange checker")
-    if model.kind != "linear":
-        return sequential("not the linear closed-form model")
-    if sorted(local_ids) != list(range(n_total)):
-        return sequential("not every worker local")
-    if model.d > 64:
-        return sequential("d > 64")
-    from ..ops import native
-    if not native.available():
-        return sequential("native library unavailable")
-    from ..engine.chain_engine import ResidencyError
-    from ..engine.quant_sweep import QuantSweepEngine, quant_sweep_capacity
-    from . import quantize as Q
-
-    xcd = int(opts.get("xcd", 2))
-
-    def run_group(g_cfgs, idx):
-        t_begin = time.perf_counter()
-        g_tols = [tols[i] for i in idx]
-        g_cens = [censors[i] for i in idx]
-        key = ("qsweep", n_total, tuple(local_ids), tuple(g_cfgs), int(max_iter), xcd, tuple(g_cens))
-        cache = getattr(model, "_chain_engines", None)
-        sw = cache.get(key) if cache is not None else None
-        if sw is None:
-            sw = QuantSweepEngine.build(model.X, model.y, local_ids, n_total, g_cfgs, obj0=obj0, tols=g_tols,
-                                        max_iters=max_iter, precomputed=(model.A, model.b, model.yy),
-                                        placement=placement, xcd=xcd,
-                                        censors=g_cens)
-            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
-            if opts.get("cache", True):
-                if cache is None:
-                    cache = {}
-                    model._chain_engines = cache
-                cache[key] = sw
-        else:
-            sw.set_targets(obj0, g_tols)
-        runs = sw.run()
-        wall = time.perf_counter() - t_begin
-        ticks = sw.stop_ticks(runs)
-        last = max(ticks)
-        out = []
-        for j, (m, r, (rho, bits, seed)) in enumerate(zip(sw.members, runs, g_cfgs)):
-            iters, done = int(r.iters), int(r.done)
-            tr, tt = m.traces(iters)
-            own = wall - (last - ticks[j]) * 1e-8 if ticks[j] > 0 else wall
-            G = Q.granules_per_row(model.d, bits)
-            res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(done == 1),
-                            wall_s=own, time_trace=tt,
-                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
-                            com_cost=np.arange(1, iters + 1) * 0.0, bytes_sent=0, bytes_total=0, primal_res=None,
-                            extra={"backend": "native", "engine": "persistent", "kernel": sw.last_kernel, "rank": 0,
-                                   "nranks": 1, "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0,
-                                   "transport": "local", "obj_mode": m.obj_mode_name, "engine_obj": m,
-                                   "q_granules": G, "q_wire_bytes": iters * n_total * G * 16,
-                                   "placed": int(sw.last_placed[j]),
-                                   "sweep": {"width": len(g_cfgs), "slot": j, "kernel": sw.last_kernel,
-                                             "placed": int(sw.last_placed[j]), "wall_ms_launch": sw.last_wall_ms},
-                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j})
-            cen = g_cens[j]
-            _quant_accounting(res, bits, seed, n_total, model.d,
-                              sent=m.sent_trace(iters) if cen is not None else None, censor=cen)
-            if cen is not None:
-                res.extra["q_wire_bytes"] = res.extra["transmissions"] * G * 16 + res.extra["censored"] * 16
-            out.append(res)
-        return out
-
-    try:
-        with roctx_range("%s sweep native-Q N=%d K=%d" % (name, n_total, len(configs))):
-            return run_in_groups(configs, quant_sweep_capacity(), run_group)
-    except ResidencyError as e:
-        return sequential("ResidencyError: %s" % e)
-    except ValueError as e:  # a shape or a device budget the sweep kernel does not take
-        return sequential("not eligible: %s" % e)
-
-
 def group_admm_closed_form(model, rho, obj0, acc, max_iter, **kw) -> RunResult:
     """``group_ADMM_closedForm`` (A1) on all local workers (single rank unless comm given)."""
     n_total = kw.pop("n_total", model.n_local)
@@ -1369,149 +1107,6 @@ def dynamic_group_admm(model, rho, obj0, acc, max_iter, path, path_cost, coheren
                       name="D-GADMM(coh=%s)" % coherence, **kw)
 
 
-def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, coherences, seeds, kind="findPath2",
-                             max_iters: Optional[Sequence[int]] = None, backend: str = "auto",
-                             engine_opts: Optional[dict] = None, comm: Optional[Comm] = None, **kw) -> List[RunResult]:
-    """``dynamic_group_admm`` at every coherence of ``coherences`` (member j re-chains from its own
-    ``PathSchedule`` seeded ``seeds[j]``): one ``RunResult`` per coherence, in the order given, equal to
-    ``[dynamic_group_admm(model, ..., coh, seed=s) for coh, s in zip(coherences, seeds)]`` in iterations,
-    objective trace, ``com_cost``, ``comm_units``, primal residual and ``converged``. On one HIP device
-    the solves run side by side, up to eight per kernel launch, one per XCD (engine/dyn_sweep.py; more
-    run in groups): every member on the blocked kernel's dynamic mode, in rounds of epoch chunks, each
-    to its own stop; a member that never re-chains within ``max_iter`` runs as a one-epoch slot. Only
-    the chains a member reaches are drawn. Each result carries ``extra['sweep'] = {width, slot, kernel,
-    placed, launches, wall_ms_launch}``; its ``wall_s`` is that solve's OWN time: the wall clock of the
-    rounds it took part in less the device time between its stop decision and the end of its last
-    round. ``extra['state']`` is not produced. ``max_iters``: one cap per member (default ``max_iter``).
-    Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, ``GADMM_CHECK_EXCHANGE=1``, no
-    native library, a shape the kernel does not take, or a device that cannot hold the group's
-    workgroups -- it IS that loop, and every result records ``extra['sweep_fallback'] = reason``.
-    ``engine_opts``: ``refresh``, ``residual``, ``cache``, ``epoch_chunk`` as in ``chain_admm``."""
-    coherences, seeds = list(coherences), list(seeds)
-    if len(coherences) != len(seeds):
-        raise ValueError("seeds: one per coherence (%d coherences, %d seeds)" % (len(coherences), len(seeds)))
-    caps = [int(max_iter)] * len(coherences) if max_iters is None else [int(v) for v in max_iters]
-    if len(caps) != len(coherences):
-        raise ValueError("max_iters: one per coherence")
-    n_total = kw.pop("n_total", model.n_local)
-    local_ids = kw.pop("local_ids", list(range(model.n_local)))
-    opts = dict(engine_opts or {})
-    nranks = comm.nranks if comm is not None else 1
-
-    def sequential(reason: str) -> List[RunResult]:
-        out = []
-        for coh, s, mi in zip(coherences, seeds, caps):
-            r = dynamic_group_admm(model, rho, obj0, acc, mi, path, path_cost, coh, seed=s, kind=kind,
-                                   n_total=n_total, local_ids=local_ids, backend=backend, engine_opts=engine_opts,
-                                   comm=comm, **kw)
-            r.extra["sweep_fallback"] = reason
-            out.append(r)
-        return out
-
-    if not coherences:
-        return []
-    if model.device.type != "cuda":
-        return sequential("cpu tensors")
-    if backend == "torch":
-        return sequential("torch backend")
-    if nranks > 1:
-        return sequential("several ranks")
-    if model.kind != "linear" or sorted(int(w) for w in local_ids) != list(range(n_total)) \
-            or kw.get("local_solver") not in (None, "closed") or kw.get("state") is not None or kw.get("failures"):
-        return sequential("not a one-GPU linear closed-form chain")
-    if kw.get("check_exchange") or (kw.get("check_exchange") is None and getenv("GADMM_CHECK_EXCHANGE", "0") == "1"):
-        return sequential("exchange checker")
-    from ..ops import native
-    if not native.available():
-        return sequential("native library unavailable")
-    from ..engine.chain_engine import ResidencyError
-    from ..engine.chain_sweep import sweep_capacity
-    from ..engine.dyn_sweep import DynSweepEngine
-
-    refresh = bool(opts.get("refresh", False))
-    residual = bool(opts.get("residual", True))
-    cost_quirk = bool(kw.get("cost_quirk", True))
-    placement = kw.get("placement") or Placement.contiguous(n_total, 1)
-    n_heads = (n_total + 1) // 2
-
-    def run_group(g_cohs, idx):
-        _timing.host_stamp("dsw:begin")
-        g_caps = [caps[i] for i in idx]
-        key = ("dyn-sweep", n_total, tuple(map(int, local_ids)), float(rho), len(g_cohs), tuple(g_caps), residual)
-        cache = getattr(model, "_chain_engines", None)
-        sw = cache.get(key) if cache is not None else None
-        if sw is None:
-            if refresh:
-                from ..ops.linalg import gram
-                gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
-            sw = DynSweepEngine.coherence_sweep(model.X, model.y, local_ids, n_total, rho, len(g_cohs), obj0=obj0,
-                                                tol=acc, max_iters=g_caps, precomputed=(model.A, model.b, model.yy),
-                                                residual=residual)
-            torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
-            if opts.get("cache", True):
-                if cache is None:
-                    cache = {}
-                    model._chain_engines = cache
-                cache[key] = sw
-        else:
-            sw.set_targets(obj0, acc)
-            if refresh:
-                sw.refresh(model.X, model.y)
-        scheds = []
-        for m, i in zip(sw.members, idx):
-            sc = PathSchedule(n_total, path, path_cost, coherences[i], kind=kind, seed=seeds[i])
-            m.set_path(sc.path, placement, 0)
-            scheds.append(sc)
-        runs = sw.run(scheds, epoch_chunk=opts.get("epoch_chunk"))
-        out = []
-        for j, (m, r, i) in enumerate(zip(sw.members, runs, idx)):
-            iters, coh = int(r.iters), coherences[i]
-            tr, tt = m.traces(iters)
-            if _static_schedule(scheds[j], g_caps[j]):  # chain_admm's static-chain accounting
-                com = np.arange(1, iters + 1) * (float(np.sum(r.cost0)) * (n_heads if cost_quirk else 1))
-            else:
-                com = _dyn_com_cost(r, n_total, n_heads if cost_quirk else 1)[:iters]
-            own = sum(sw.last_round_ms[:r.rounds]) * 1e-3 - r.tail_ticks * 1e-8
-            res = RunResult(algorithm="D-GADMM(coh=%s)" % coh, obj=tr, loss=np.abs(tr - obj0), iters=iters,
-                            converged=(int(r.done) == 1), wall_s=own, time_trace=tt,
-                            comm_units=np.arange(1, iters + 1, dtype=np.float64) * n_total,
-                            com_cost=np.asarray(com[:iters]), bytes_sent=0, bytes_total=0,
-                            primal_res=m.primal_residual(iters),
-                            extra={"backend": "native", "engine": "persistent-dynamic", "rank": 0, "nranks": 1,
-                                   "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0, "transport": "local",
-                                   "obj_mode": m.obj_mode_name, "engine_obj": m,
-                                   "sweep": {"width": len(g_cohs), "slot": j, "kernel": sw.last_kernel,
-                                             "placed": int(r.placed), "launches": int(r.rounds),
-                                             "wall_ms_launch": sw.last_wall_ms},
-                                   "sweep_kernel": sw.last_kernel, "sweep_slot": j, "sweep_launches": int(r.rounds)})
-            out.append(res)
-        _timing.host_stamp("dsw:end")
-        return out
-
-    try:
-        with roctx_range("D-GADMM sweep native N=%d K=%d" % (n_total, len(coherences))):
-            return run_in_groups(coherences, sweep_capacity(), run_group)
-    except ResidencyError as e:
-        return sequential("ResidencyError: %s" % e)
-    except ValueError as e:  # a shape the sweep kernel does not take (d > 52, no blocked plan, ...)
-        return sequential("not eligible: %s" % e)
-
-
-def _dyn_com_cost(r, n_total: int, scale: int) -> np.ndarray:
-    """Cumulative ``com_cost`` of the iterations covered by the epochs a sweep member drew, with the
-    arithmetic of ``_chain_admm_native``'s ``cost_arrays`` (per-epoch hop-cost sums, scaled, one cumsum)."""
-    drawn_C, nd = r.costs, len(r.starts)
-    if drawn_C and any(c.dtype == object for c in drawn_C):
-        Cn = np.empty(sum(len(c) for c in drawn_C), dtype=object)
-        Cn[:] = [c for cc in drawn_C for c in cc]
-    else:
-        Cn = np.concatenate(drawn_C) if drawn_C else np.zeros((0, max(n_total - 1, 0)))
-    csum = Cn.sum(axis=1) if (len(Cn) and Cn.dtype != object) else np.asarray([float(np.sum(c)) for c in Cn])
-    per_it = np.concatenate([[float(np.sum(r.cost0))], csum]) * scale
-    which = np.searchsorted(r.starts[:nd], np.arange(1, int(r.span) + 1), side="right") - 1
-    return np.cumsum(per_it[which])
-
-
 def dynamic_group_admm_v0(model, rho, obj0, acc, max_iter, path_matrix, cost_matrix, coherence,
                           faithful_initial_cost=True, **kw) -> RunResult:
     """``dynamic_group_ADMM_closedForm_v0`` (A5): consume pre-generated chains. With
@@ -1538,3 +1133,9 @@ def static_group_admm(model, rho, obj0, acc, max_iter, coherence, cost_static_ma
                          path_matrix=[ident] * cm.shape[0], cost_matrix=cm)
     return chain_admm(model, local_ids, n_total, rho, obj0, acc, max_iter, schedule=sched,
                       name="GADMM-static(coh=%s)" % coherence, **kw)
+
+
+# The sweeps lived here and callers name them here: algorithms/sweeps.py, which builds on the solves
+# above, so it is imported once they exist.
+from .sweeps import (_sweep_member, chain_admm_sweep, dynamic_group_admm_sweep,  # noqa: E402,F401
+                     quantized_group_admm_sweep, run_in_groups, sweep_groups)

@@ -16,19 +16,20 @@ Two ways to build one:
   in place;
 * ``ChainSweepEngine(members)``: already-built engines (different data, N and d within one register
   class of the kernel: d <= 32 or 33..52); they are moved onto the sweep's stream.
+
+What a sweep engine is apart from its kernel and its members' preparation: sweep_base.py.
 """
 from __future__ import annotations
 
-import ctypes
 import time
 from typing import List, Optional, Sequence
 
 import torch
 
 from ..ops import native
-from ..ops.linalg import gram, spd_inverse
 from ..parallel.topology import Placement
-from .chain_engine import EngineRun, HandoffTimeout, NativeChainEngine, ResidencyError
+from .chain_engine import EngineRun, NativeChainEngine
+from .sweep_base import SweepEngineBase, per_member
 
 
 def sweep_capacity() -> int:
@@ -36,107 +37,35 @@ def sweep_capacity() -> int:
     return int(native.require().gadmm_chain_blocked_sweep_capacity())
 
 
-class ChainSweepEngine:
-    def __init__(self, members: Sequence[NativeChainEngine], stream: Optional[torch.cuda.Stream] = None):
-        members = list(members)
-        if not members:
-            raise ValueError("a sweep needs at least one member")
-        cap = sweep_capacity()
-        if len(members) > cap:
-            raise ValueError("%d members: one sweep launch takes at most %d" % (len(members), cap))
-        if len({id(m) for m in members}) != len(members):
-            raise ValueError("a member appears twice (every slot needs its own state)")
-        dev = members[0].device
-        if any(m.device != dev for m in members):
-            raise ValueError("the members of a sweep live on one device")
-        if len({m.d <= 32 for m in members}) != 1:
-            raise ValueError("members of different register classes (d <= 32 and 33..52) cannot share a launch")
-        for j, m in enumerate(members):
-            if m.model != "linear" or m.nranks != 1 or m.n_local != m.n_total:
-                raise ValueError("member %d: one-GPU linear closed-form solves only" % j)
-            if m.plan is None:
-                raise ValueError("member %d has no chain installed (set_path)" % j)
-        self.lib = native.require()
-        self.device = dev
-        self.members = members
-        self.stream = stream if stream is not None else members[0].stream
-        for m in members:  # one stream: every member's resets and zero-fills precede the launch
-            if m.stream is not self.stream:
-                m.adopt_stream(self.stream)
-        nbytes = cap * ctypes.sizeof(native.PersistArgs)
-        # the launcher's staging pair: the slots' PersistArgs go up in one async copy ahead of the kernel
-        self._stage_host = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
-        self._stage_dev = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self._shared = None
-        self.last_kernel = None
-        self.last_placed: List[int] = []
-        self.last_wall_ms = 0.0
+class ChainSweepEngine(SweepEngineBase):
+    capacity = staticmethod(sweep_capacity)
 
-    # ---------------------------------------------------------------------------------------------
+    def _member_defect(self, m):
+        return " has no chain installed (set_path)" if m.plan is None else None
+
     @classmethod
     def rho_sweep(cls, X: torch.Tensor, y: torch.Tensor, local_ids: Sequence[int], n_total: int,
                   rhos: Sequence[float], obj0: float = 0.0, tols=1e-4, max_iters=1000, precomputed=None,
                   placement: Optional[Placement] = None, residual: bool = False, xcd: int = 2) -> "ChainSweepEngine":
         """Members = the same shards at every rho of ``rhos``. ``tols`` / ``max_iters``: one value or one
         per member. ``precomputed``: an ``(A, b, yy)`` Gram to share (else computed here, once)."""
-        if not X.is_cuda:
-            raise ValueError("ChainSweepEngine runs on a HIP device")
-        K = len(rhos)
-        if K < 1 or K > sweep_capacity():
-            raise ValueError("%d values of rho: one sweep launch takes 1..%d" % (K, sweep_capacity()))
-        tols = [float(tols)] * K if not isinstance(tols, (list, tuple)) else [float(t) for t in tols]
-        max_iters = [int(max_iters)] * K if not isinstance(max_iters, (list, tuple)) else [int(v) for v in max_iters]
-        if len(tols) != K or len(max_iters) != K:
-            raise ValueError("tols / max_iters: one value, or one per rho")
-        X = X.to(torch.float64).contiguous()
-        y = y.to(torch.float64).contiguous()
-        n_total = int(n_total)
-        if len(local_ids) != n_total:
-            raise ValueError("a sweep member holds every worker of its chain (one GPU)")
-        dev = X.device
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        # degree-1 and degree-2 shifts per member, as NativeChainEngine._build_inverses picks them
-        if n_total < 2:
-            raise ValueError("a chain needs at least two workers")
-        per = [[r] if n_total == 2 else [r, 2.0 * r] for r in (float(r) for r in rhos)]
-        V = len(per[0])
-        with torch.cuda.stream(stream):
-            A, b, yy = precomputed if precomputed is not None else gram(X, y)
-            shifts = torch.tensor([s for p in per for s in p], dtype=torch.float64, device=dev).unsqueeze(0).expand(
-                A.shape[0], -1).contiguous()
-            Minv = spd_inverse(A, shifts)  # ONE launch for all K x V shifts (checks positive definiteness)
+        K, n_total = len(rhos), int(n_total)
+        X, y, stream, shared = cls._shared_tables(X, y, local_ids, n_total, rhos, K, "values of rho", precomputed)
+        tols = per_member(tols, K, float, "tols / max_iters: one value, or one per rho")
+        max_iters = per_member(max_iters, K, int, "tols / max_iters: one value, or one per rho")
+        A, b, yy, _, Minv, _, V = shared
         pl = placement if placement is not None else Placement.contiguous(n_total, 1)
         members = []
         for j, rho in enumerate(rhos):
-            dtv = (j * V, j * V, j * V + V - 1)
             m = NativeChainEngine(X, y, local_ids, n_total, "linear", rho=float(rho), obj0=obj0, tol=tols[j],
                                   max_iter=max_iters[j], stream=stream, precomputed=(A, b, yy), residual=residual,
-                                  xcd=xcd, inverses=(Minv, K * V, dtv))
+                                  xcd=xcd, inverses=(Minv, K * V, (j * V, j * V, j * V + V - 1)))
             m.set_path(list(range(n_total)), pl, 0)
             members.append(m)
         self = cls(members, stream=stream)
-        self._shared = (A, b, yy, shifts, Minv, torch.zeros((1,), dtype=torch.int32, device=dev))
+        self._shared = shared
         return self
 
-    def refresh(self, X: torch.Tensor, y: torch.Tensor):
-        """Recompute the shared Gram and the shared table of inverses from the raw shards, in place, on
-        the sweep's stream: one Gram and one inverse launch for the whole sweep (rho_sweep engines)."""
-        if self._shared is None:
-            raise RuntimeError("refresh: members built elsewhere refresh themselves")
-        A, b, yy, shifts, Minv, status = self._shared
-        with torch.cuda.stream(self.stream):
-            gram(X, y, out=(A, b, yy))
-            spd_inverse(A, shifts, out=Minv, check_status=False, status=status)
-        for m in self.members:
-            m._minv_version += 1
-
-    def set_targets(self, obj0: float, tols) -> None:
-        tols = [float(tols)] * len(self.members) if not isinstance(tols, (list, tuple)) else list(tols)
-        for m, t in zip(self.members, tols):
-            m.set_targets(obj0, float(t))
-
-    # ---------------------------------------------------------------------------------------------
     def blocks(self) -> List[int]:
         """Workgroups of every member (worker + objective workgroups + the monitor)."""
         out = []
@@ -160,50 +89,16 @@ class ChainSweepEngine:
         plans = []
         for j, m in enumerate(self.members):
             try:
-                pa, plan = m.prepare_blocked(lag=lag, timeout_s=timeout_s)
+                batch[j], plan = m.prepare_blocked(lag=lag, timeout_s=timeout_s)
             except ValueError as e:
                 raise ValueError("sweep member %d: %s" % (j, e))
-            batch[j] = pa
             plans.append(plan)
         self.last_kernel = "blocked-sweep(K=%d,k=%s,L=%s)" % (
             K, "/".join(sorted({str(p[0]) for p in plans})), "/".join(sorted({str(p[1]) for p in plans})))
         for m in self.members:
             m.last_kernel = self.last_kernel
         t0 = time.perf_counter()
-        rc = int(self.lib.gadmm_chain_blocked_sweep_launch(batch, K, self._stage_host.data_ptr(),
-                                                           self._stage_dev.data_ptr(), self.stream.cuda_stream))
-        if rc == -2:
-            raise ResidencyError(self.lib.gadmm_last_error().decode())
-        if rc == -1:
-            raise ValueError(self.lib.gadmm_last_error().decode())
-        native.check(rc, "chain_blocked_sweep_launch")
-        fetch = [m._queue_readback(fetch_trace) for m in self.members]
-        self.stream.synchronize()
-        self.last_wall_ms = (time.perf_counter() - t0) * 1e3
-        # every control block first (host memory only), then the verdicts: after a timeout nothing more
-        # is started on the GPU in this call
-        codes = [m._ctl_host.tolist() for m in self.members]
-        self.last_placed = [c[6] for c in codes]
-        bad = [j for j, c in enumerate(codes) if c[1] == 4]
-        if bad:
-            for m, c in zip(self.members, codes):
-                m.last_placed = c[6]
-            raise HandoffTimeout("blocked sweep kernel: slot %d timed out (hand-off never completed)" % bad[0])
+        self._launch(self.lib.gadmm_chain_blocked_sweep_launch, batch, K, "chain_blocked_sweep_launch")
+        fetch, _ = self._collect(self.members, fetch_trace, t0)
         return [m.finish_blocked(1, self.last_wall_ms, f, "blocked sweep kernel: slot %d" % j)
                 for j, (m, f) in enumerate(zip(self.members, fetch))]
-
-    def stop_ticks(self, runs: Sequence[EngineRun]) -> List[int]:
-        """Device clock (s_memrealtime, 100 MHz) of each member's stop decision in the last run, read
-        from the pinned read-back block (``run(fetch_trace=True)``); 0 where no decision was stamped."""
-        out = []
-        for m, r in zip(self.members, runs):
-            nt = m.trace.numel()
-            if not getattr(m, "_tr_valid", False) or r.iters < 1 or r.iters > nt:
-                out.append(0)
-                continue
-            out.append(int(m._rb_host_np[8 + nt + r.iters - 1:8 + nt + r.iters].view("int64")[0]))
-        return out
-
-    def close(self):
-        for m in self.members:
-            m.close()

@@ -17,23 +17,24 @@ shards at one rho: one Gram, one table of inverses (as ``ChainSweepEngine.rho_sw
 ``inverses=``) and one padded inverse image shared by all, built once and rebuilt once per
 ``refresh``. ``DynSweepEngine(members)`` takes engines with their own data (different N and d within
 one register class). Every member runs the blocked dynamic mode, whatever its coherence.
+
+What a sweep engine is apart from its kernel and its members' preparation: sweep_base.py.
 """
 from __future__ import annotations
 
-import ctypes
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Sequence
 
 import numpy as np
 import torch
 
 from ..ops import native
-from ..ops.linalg import gram, spd_inverse
-from ..parallel.topology import Placement, rechain_iterations
+from ..parallel.topology import rechain_iterations
 from ..utils import timing as _timing
-from .chain_engine import HandoffTimeout, NativeChainEngine, ResidencyError
+from .chain_engine import NativeChainEngine
 from .chain_sweep import sweep_capacity
+from .sweep_base import SweepEngineBase, per_member
 
 
 @dataclass
@@ -98,83 +99,33 @@ class _Member:
             self.costs.append(Cn)
 
 
-class DynSweepEngine:
-    def __init__(self, members: Sequence[NativeChainEngine], stream: Optional[torch.cuda.Stream] = None):
-        members = list(members)
-        if not members:
-            raise ValueError("a sweep needs at least one member")
-        cap = sweep_capacity()
-        if len(members) > cap:
-            raise ValueError("%d members: one sweep launch takes at most %d" % (len(members), cap))
-        if len({id(m) for m in members}) != len(members):
-            raise ValueError("a member appears twice (every slot needs its own state)")
-        dev = members[0].device
-        if any(m.device != dev for m in members):
-            raise ValueError("the members of a sweep live on one device")
-        if len({m.d <= 32 for m in members}) != 1:
-            raise ValueError("members of different register classes (d <= 32 and 33..52) cannot share a launch")
-        for j, m in enumerate(members):
-            if m.model != "linear" or m.nranks != 1 or m.n_local != m.n_total:
-                raise ValueError("member %d: one-GPU linear closed-form solves only" % j)
-        self.lib = native.require()
-        self.device = dev
-        self.members = members
-        self.stream = stream if stream is not None else members[0].stream
-        for m in members:  # one stream: every member's resets, table copies and zero-fills precede the launch
-            if m.stream is not self.stream:
-                m.adopt_stream(self.stream)
-        nbytes = cap * ctypes.sizeof(native.PersistArgs)
-        self._stage_host = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
-        self._stage_dev = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self._shared = None
-        self.last_kernel = None
-        self.last_placed: List[int] = []
-        self.last_round_ms: List[float] = []
-        self.last_wall_ms = 0.0
+class DynSweepEngine(SweepEngineBase):
+    _WHAT = "blocked dynamic sweep kernel"
+    capacity = staticmethod(sweep_capacity)
 
-    # ---------------------------------------------------------------------------------------------
+    def __init__(self, members: Sequence[NativeChainEngine], stream=None):
+        super().__init__(members, stream)
+        self.last_round_ms: List[float] = []
+
     @classmethod
     def coherence_sweep(cls, X: torch.Tensor, y: torch.Tensor, local_ids: Sequence[int], n_total: int, rho: float,
                         width: int, obj0: float = 0.0, tol: float = 1e-4, max_iters=1000, precomputed=None,
                         residual: bool = False, xcd: int = 2) -> "DynSweepEngine":
         """``width`` members over the same shards at ``rho``. ``max_iters``: one value or one per
         member. ``precomputed``: an ``(A, b, yy)`` Gram to share (else computed here, once)."""
-        if not X.is_cuda:
-            raise ValueError("DynSweepEngine runs on a HIP device")
-        K = int(width)
-        if K < 1 or K > sweep_capacity():
-            raise ValueError("%d members: one sweep launch takes 1..%d" % (K, sweep_capacity()))
-        max_iters = [int(max_iters)] * K if not isinstance(max_iters, (list, tuple)) else [int(v) for v in max_iters]
-        if len(max_iters) != K:
-            raise ValueError("max_iters: one value, or one per member")
-        X = X.to(torch.float64).contiguous()
-        y = y.to(torch.float64).contiguous()
-        n_total = int(n_total)
-        if len(local_ids) != n_total:
-            raise ValueError("a sweep member holds every worker of its chain (one GPU)")
-        if n_total < 2:
-            raise ValueError("a chain needs at least two workers")
-        dev = X.device
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        # degree-1 and degree-2 shifts, as NativeChainEngine._build_inverses picks them
-        per = [float(rho)] if n_total == 2 else [float(rho), 2.0 * float(rho)]
-        V = len(per)
-        with torch.cuda.stream(stream):
-            A, b, yy = precomputed if precomputed is not None else gram(X, y)
-            shifts = torch.tensor(per, dtype=torch.float64, device=dev).unsqueeze(0).expand(A.shape[0], -1).contiguous()
-            Minv = spd_inverse(A, shifts)  # checks positive definiteness
-        members = []
-        for j in range(K):
-            members.append(NativeChainEngine(X, y, local_ids, n_total, "linear", rho=float(rho), obj0=obj0, tol=tol,
-                                             max_iter=max_iters[j], stream=stream, precomputed=(A, b, yy),
-                                             residual=residual, xcd=xcd, inverses=(Minv, V, (0, 0, V - 1))))
+        K, n_total = int(width), int(n_total)
+        X, y, stream, shared = cls._shared_tables(X, y, local_ids, n_total, [rho], K, "members", precomputed)
+        max_iters = per_member(max_iters, K, int, "max_iters: one value, or one per member")
+        A, b, yy, _, Minv, _, V = shared
+        members = [NativeChainEngine(X, y, local_ids, n_total, "linear", rho=float(rho), obj0=obj0, tol=tol,
+                                     max_iter=max_iters[j], stream=stream, precomputed=(A, b, yy), residual=residual,
+                                     xcd=xcd, inverses=(Minv, V, (0, 0, V - 1))) for j in range(K)]
         self = cls(members, stream=stream)
-        self._shared = (A, b, yy, shifts, Minv, torch.zeros((1,), dtype=torch.int32, device=dev))
-        self._share_pad()
+        self._shared = shared
+        self._refreshed()
         return self
 
-    def _share_pad(self):
+    def _refreshed(self):
         """One padded inverse image for all members of a shared table: member 0 builds it (in place
         after the first time) on the sweep's stream, the others name the same buffer."""
         m0 = self.members[0]
@@ -182,23 +133,6 @@ class DynSweepEngine:
         m0._attach_minv_pad(native.PersistArgs())
         for m in self.members[1:]:
             m._minv_pad, m._minv_pad_version = m0._minv_pad, m._minv_version
-
-    def refresh(self, X: torch.Tensor, y: torch.Tensor):
-        """Recompute the shared Gram, the shared table of inverses and the shared padded image from the
-        raw shards, in place, on the sweep's stream: once for the whole sweep (coherence_sweep engines)."""
-        if self._shared is None:
-            raise RuntimeError("refresh: members built elsewhere refresh themselves")
-        A, b, yy, shifts, Minv, status = self._shared
-        with torch.cuda.stream(self.stream):
-            gram(X, y, out=(A, b, yy))
-            spd_inverse(A, shifts, out=Minv, check_status=False, status=status)
-        for m in self.members:
-            m._minv_version += 1
-        self._share_pad()
-
-    def set_targets(self, obj0: float, tol: float) -> None:
-        for m in self.members:
-            m.set_targets(obj0, float(tol))
 
     # ---------------------------------------------------------------------------------------------
     def _begin(self, m: NativeChainEngine, schedule, epoch_chunk) -> _Member:
@@ -273,43 +207,27 @@ class DynSweepEngine:
                 self.last_kernel = kname
                 for m in self.members:
                     m.last_kernel = kname
-            rc = int(self.lib.gadmm_chain_blocked_dyn_sweep_launch(batch, K, self._stage_host.data_ptr(),
-                                                                   self._stage_dev.data_ptr(), self.stream.cuda_stream))
-            if rc == -2:
-                raise ResidencyError(self.lib.gadmm_last_error().decode())
-            if rc == -1:
-                raise ValueError(self.lib.gadmm_last_error().decode())
-            native.check(rc, "chain_blocked_dyn_sweep_launch")
+            self._launch(self.lib.gadmm_chain_blocked_dyn_sweep_launch, batch, K, "chain_blocked_dyn_sweep_launch")
             _timing.host_stamp("dsw:launched")
-            for i in live:
-                state[i].fetch = state[i].eng._queue_readback(True)
-            self.stream.synchronize()
-            _timing.host_stamp("dsw:synced")
-            # every control block first (host memory only), then the verdicts: after a timeout nothing
-            # more is started on the GPU in this call
-            codes = {i: state[i].eng._ctl_host.tolist() for i in live}
-            for i in live:
-                state[i].placed = state[i].eng.last_placed = codes[i][6]
-                state[i].eng._tr_valid = state[i].fetch
-                state[i].eng.last_timeline = state[i].eng.last_timeline_slots = None
-            bad = [i for i in live if codes[i][1] == 4]
-            if bad:
-                self.last_placed = [s.placed for s in state]
-                raise HandoffTimeout("blocked dynamic sweep kernel: slot %d (member %d) timed out (hand-off never "
-                                     "completed)" % (state[bad[0]].slot, bad[0]))
+            fetch, codes = self._collect([state[i].eng for i in live], True, t0, "dsw:synced",
+                                         lambda slot: "slot %d (member %d)" % (slot, live[slot]))
+            for i, f in zip(live, fetch):
+                s = state[i]
+                s.fetch = s.eng._tr_valid = f
+                s.placed = s.eng.last_placed
+                s.eng.last_timeline = s.eng.last_timeline_slots = None
             nxt_live = []
             ticks = []
-            for i in live:
-                s, c = state[i], codes[i]
+            for i, c in zip(live, codes):
+                s = state[i]
                 done, conv, nxt = c[1], c[2], c[0]
                 s.rounds += 1
                 s.done = done
                 last_it = conv if done in (1, 2, 3) else s.hard_stop  # the last iteration decided in this round
-                nt = s.eng.trace.numel()
-                if not 1 <= last_it <= nt:
+                if not 1 <= last_it <= s.eng.trace.numel():
                     s.stop_tick = 0
                 elif s.fetch:
-                    s.stop_tick = int(s.eng._rb_host_np[8 + nt + last_it - 1:8 + nt + last_it].view("int64")[0])
+                    s.stop_tick = self._stop_tick(s.eng, last_it)
                 else:  # a trace too long for the one-copy read-back: this stamp alone (a blocking 8-byte copy)
                     s.stop_tick = int(s.eng.tstamp[last_it - 1:last_it].cpu().item())
                 ticks.append(s.stop_tick)
@@ -329,7 +247,6 @@ class DynSweepEngine:
             self.last_round_ms.append((time.perf_counter() - t0) * 1e3)
             live = nxt_live
         self.last_wall_ms = float(sum(self.last_round_ms))
-        self.last_placed = [s.placed for s in state]
         out = []
         for s in state:
             hints = s.eng.__dict__.setdefault("_dyn_epoch_hint", {})
@@ -342,7 +259,3 @@ class DynSweepEngine:
                                    starts=starts, paths=s.Pall[:s.n_drawn], costs=s.costs,
                                    cost0=np.asarray(s.saved[2]), span=int(s.ep_start[s.n_drawn] - 1) if s.n_drawn < s.E_total else int(s.eng.max_iter)))
         return out
-
-    def close(self):
-        for m in self.members:
-            m.close()

@@ -161,6 +161,70 @@ def test_dyn_sweep_launch_refuses_two_entries_sharing_blk_tab():
     assert rc == -1 and "share a buffer" in msg
 
 
+# The cases below pass every check the ones above stop at, so none of their batches may ever reach a
+# launch: the LAST entry keeps an iteration-tag range that the launcher refuses (start_iter + max_iter +
+# lag >= 2^20), and each case adds ONE defect to an earlier entry, so the message tells which check fired.
+_WRITTEN = ("ctl", "trace", "theta", "mu", "blk_tab", "objg", "decg", "xchk", "tstamp", "rres")
+_READ_ONLY = ("A", "b", "yy", "Minv", "slots")
+
+
+def _guarded(nb):
+    batch = _valid(nb)
+    for j in range(nb):
+        batch[j].rres = 0x10000 * (j + 1) + 0x100 * 0x40
+    batch[nb - 1].max_iter = 1 << 20  # never launched, whatever else the case changes
+    return batch
+
+
+def test_dyn_sweep_launch_base_batch_is_refused_by_its_tag_range_only():
+    for nb in (1, 3, 8):
+        rc, msg = _launch(_guarded(nb), nb)
+        assert rc == -1 and "blocked dynamic sweep: solve %d: ring/lag/tag range" % (nb - 1) in msg, msg
+
+
+def test_dyn_sweep_launch_refuses_null_batch_or_staging():
+    lib = native.require()
+    stage = (native.PersistArgs * 8)()
+    batch = _guarded(1)
+    for args in ((None, 1, ctypes.addressof(stage), ctypes.addressof(stage)),
+                 (batch, 1, None, ctypes.addressof(stage)), (batch, 1, ctypes.addressof(stage), None)):
+        assert lib.gadmm_chain_blocked_dyn_sweep_launch(*args, None) == -1
+        assert "blocked dynamic sweep: null batch or staging buffer" in lib.gadmm_last_error().decode()
+
+
+def test_dyn_sweep_launch_refuses_more_workgroups_than_the_placement_check_holds():
+    batch = _guarded(2)
+    batch[0].n = batch[0].n_local = 768  # 768 / 4 worker + 768 / 12 objective workgroups + the monitor
+    rc, msg = _launch(batch, 2)
+    assert rc == -1 and "solve 0 has 257 workgroups, the placement check holds 256" in msg, msg
+
+
+@pytest.mark.parametrize("field,value", [("ring", 9), ("lag", 0), ("max_iter", 1 << 20)])
+def test_dyn_sweep_launch_refuses_ring_lag_tag_range(field, value):
+    batch = _guarded(3)
+    setattr(batch[1], field, value)  # lag = 8: ring 9 = lag + 1
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "blocked dynamic sweep: solve 1: ring/lag/tag range" in msg, msg
+
+
+@pytest.mark.parametrize("name", _WRITTEN)
+def test_dyn_sweep_launch_refuses_a_shared_written_buffer(name):
+    batch = _guarded(3)
+    setattr(batch[0], name, 0x7fff0000)
+    setattr(batch[1], name, 0x7fff0000)
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "blocked dynamic sweep: solves 0 and 1 share a buffer that both write" in msg, msg
+
+
+@pytest.mark.parametrize("name", _READ_ONLY)
+def test_dyn_sweep_launch_lets_read_only_inputs_be_shared(name):
+    batch = _guarded(3)
+    for j in range(3):
+        setattr(batch[j], name, 0x7fff0000)
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "solve 2: ring/lag/tag range" in msg, msg  # no earlier check objected
+
+
 def test_static_sweep_launcher_still_refuses_what_the_dynamic_one_takes():
     lib = native.require()
     stage = (native.PersistArgs * 8)()

@@ -88,6 +88,76 @@ def test_sweep_launch_refuses_null_xchk():
     assert rc == -1 and "xchk" in msg
 
 
+# The batches below name buffers by made-up addresses, so none of them may ever reach a launch: the LAST
+# entry of every batch keeps an iteration-tag range that the launcher refuses (start_iter + max_iter +
+# lag >= 2^20), and each case adds ONE defect to an earlier entry, so the message tells which check fired.
+_WRITTEN = ("ctl", "trace", "theta", "mu", "blk_tab", "objg", "decg", "xchk", "tstamp", "rres")
+_READ_ONLY = ("A", "b", "yy", "Minv", "slots")
+
+
+def _valid(nb):
+    """Entries that pass every per-entry check but the last one's tag range: addresses that are never
+    dereferenced, distinct per entry and per field."""
+    batch = (native.PersistArgs * max(nb, 1))()
+    for j in range(nb):
+        a = batch[j]
+        a.d, a.n, a.n_local, a.start_iter, a.max_iter, a.lag, a.ring, a.nvar = 14, 24, 24, 1, 100, 8, 12, 2
+        a.has_monitor, a.nranks, a.blk_pw, a.blk_k, a.blk_len = 1, 1, 1, 2, 4
+        for i, f in enumerate(_READ_ONLY + _WRITTEN + ("dec_push",)):
+            setattr(a, f, 0x10000000 + 0x100000 * j + 0x1000 * (i + 1))
+    batch[max(nb, 1) - 1].max_iter = 1 << 20  # never launched, whatever else the case changes
+    return batch
+
+
+def test_sweep_launch_base_batch_is_refused_by_its_tag_range_only():
+    for nb in (1, 3, 8):
+        rc, msg = _launch(_valid(nb), nb)
+        assert rc == -1 and "blocked sweep: solve %d: ring/lag/tag range" % (nb - 1) in msg, msg
+
+
+def test_sweep_launch_refuses_null_batch_or_staging():
+    lib = native.require()
+    stage = (native.PersistArgs * 8)()
+    batch = _valid(1)
+    for args in ((None, 1, ctypes.addressof(stage), ctypes.addressof(stage)),
+                 (batch, 1, None, ctypes.addressof(stage)), (batch, 1, ctypes.addressof(stage), None)):
+        assert lib.gadmm_chain_blocked_sweep_launch(*args, None) == -1
+        assert "blocked sweep: null batch or staging buffer" in lib.gadmm_last_error().decode()
+
+
+def test_sweep_launch_refuses_more_workgroups_than_the_placement_check_holds():
+    batch = _valid(2)
+    batch[0].n = batch[0].n_local = 768  # 768 / 4 worker + 768 / 12 objective workgroups + the monitor
+    rc, msg = _launch(batch, 2)
+    assert rc == -1 and "solve 0 has 257 workgroups, the placement check holds 256" in msg, msg
+
+
+@pytest.mark.parametrize("field,value", [("ring", 9), ("lag", 0), ("max_iter", 1 << 20)])
+def test_sweep_launch_refuses_ring_lag_tag_range(field, value):
+    batch = _valid(3)
+    setattr(batch[1], field, value)  # lag = 8: ring 9 = lag + 1
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "blocked sweep: solve 1: ring/lag/tag range" in msg, msg
+
+
+@pytest.mark.parametrize("name", _WRITTEN)
+def test_sweep_launch_refuses_a_shared_written_buffer(name):
+    batch = _valid(3)
+    setattr(batch[0], name, 0x7fff0000)
+    setattr(batch[1], name, 0x7fff0000)
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "blocked sweep: solves 0 and 1 share a buffer that both write" in msg, msg
+
+
+@pytest.mark.parametrize("name", _READ_ONLY)
+def test_sweep_launch_lets_read_only_inputs_be_shared(name):
+    batch = _valid(3)
+    for j in range(3):
+        setattr(batch[j], name, 0x7fff0000)
+    rc, msg = _launch(batch, 3)
+    assert rc == -1 and "solve 2: ring/lag/tag range" in msg, msg  # no earlier check objected
+
+
 # ---- grouping: more values of rho than one launch takes
 def test_eleven_values_run_as_eight_plus_three_in_input_order():
     assert [len(g) for g in sweep_groups(11, 8)] == [8, 3]
