@@ -28,7 +28,11 @@ specification), in the form the kernels evaluate them:
   IAG's schedule) computed once in float64 and shared with the engines;
 * the set-up kernels (Grams, inverses) have exact references at the end of this file: integer data whose
   Gram is known exactly (``exact_gram``, ``image_gram``) and the long-double inverse, with the kernels'
-  Gauss-Jordan recurrences in float64 (``gauss_jordan_inverse``) as the noise measure.
+  Gauss-Jordan recurrences in float64 (``gauss_jordan_inverse``) as the noise measure;
+* the block-packed symmetric GEMV of the large-d engines (csrc/include/sym_gemv.h) is held to the integer
+  product of integer data (``symv_int_data``), exact in float64 in any order; ``symv_packed_model`` is its
+  block structure in NumPy (stored blocks, direct and transposed partials, the grouped row reduction),
+  with the mistakes the GPU test must catch as mutants.
 
 This is a helper module, not a conftest: test modules import it as ``import hp_reference``.
 """
@@ -598,7 +602,9 @@ LINEAR_SHAPES = [(2, 3, 1), (3, 7, 3), (5, 40, 32), (4, 40, 33), (5, 60, 52), (5
                  (3, 80, 65), (4, 150, 128), (3, 150, 129), (3, 280, 256), (3, 280, 257)]
 LOGISTIC_SHAPES = [(3, 5, 3), (4, 30, 20), (3, 40, 52), (3, 52, 20), (3, 40, 53), (3, 64, 64), (3, 100, 20),
                    (2, 60, 128), (3, 200, 30), (3, 250, 40), (3, 100, 100)]
-STAR_SHAPES = [(3, 7, 3), (4, 60, 52), (4, 70, 53), (3, 40, 64), (3, 80, 65)]
+STAR_SHAPES = [(3, 7, 3), (4, 60, 52), (4, 70, 53), (3, 40, 64), (2, 8, 6), (5, 8, 6), (26, 60, 53),
+               (3, 80, 65), (2, 70, 66), (4, 80, 65), (4, 150, 128), (3, 150, 129), (3, 280, 256), (3, 280, 257)]
+assert all(n - 1 < max(d, 16) for n, _, d in STAR_SHAPES)  # the hub's sum of n - 1 rows is under the floor's size
 LIVE_STOP = ((4, 30, 20), 1e-3)  # the one logistic case with a live inner stop rule
 
 _CACHE = {}
@@ -653,7 +659,10 @@ def linear_path_case(n, m, d, path, K=K_ITERS):
 
 
 def star_case(n, m, d, K=K_ITERS):
-    """As ``linear_case`` for ``star_admm_linear`` (the same data)."""
+    """As ``linear_case`` for ``star_admm_linear`` (the same data). The size behind the dot-product floor
+    of the bounds is d, although the hub's right-hand side sums n - 1 rows: at every shape of
+    ``STAR_SHAPES`` n - 1 < max(d, 16), so the longer sum would not move a bound there, and at n = 66,
+    d = 6 (tests/test_gpu_stop_rule.py) it would only widen one that the kernel meets as it is."""
     def build():
         X, y, rho = make_linear(n, m, d, seed_of(n, m, d))
         _freeze(X, y)
@@ -1839,3 +1848,91 @@ def qgadmm_clamp_case(n, m, d, bits, path=None):
                             return out + ((t, w, i, low),)
         raise AssertionError("no missing-clamp case for %r" % ((n, m, d, bits, path),))
     return _cached(("qgadmm-clamp", n, m, d, bits, None if path is None else tuple(path_l)), build)
+
+
+# ------------------------------------------------------------------------------------------------
+# The block-packed symmetric GEMV (csrc/include/sym_gemv.h; tests/test_gpu_symv_exact.py). Integer
+# data: M symmetric and x with entries in [-2^19, 2^19], so every partial sum of every product of up to
+# 8193 terms stays below 8193 * 2^38 < 2^53 -- every FMA and every addition of a float64 evaluation is
+# exact IN ANY ORDER, and the kernel's output must equal the int64 product bit for bit.
+SYMV_B = 128      # block edge (symv::B)
+SYMV_RG = 8       # groups of partials per block row (symv::RG)
+SYMV_LOADS = 8    # partials a reduce_row thread loads per trip of its loop
+SYMV_AMP = 2 ** 19
+SYMV_MAX_D = 8193  # SYMV_MAX_D * SYMV_AMP^2 < 2^53
+# d -> what it is the smallest d to reach (tests/test_gpu_symv_exact.py)
+SYMV_SHAPES = (1, 127, 128, 129, 255, 256, 257, 1024, 1025, 8193)
+SYMV_MUTANTS = ("drop-transposed", "clip-8", "wrong-x-block")
+assert SYMV_MAX_D * SYMV_AMP ** 2 < 2 ** 53
+
+
+def symv_int_data(d, seed=0, count=1):
+    """``(M (count, d, d) int32 symmetric, x (count, d) int64, y (count, d) int64 = M x)``, entries of M
+    and x uniform in [-SYMV_AMP, SYMV_AMP]; the product is formed in int64, row chunk by row chunk."""
+    assert 1 <= d <= SYMV_MAX_D
+    rng = np.random.default_rng(7919 * d + seed)
+    M = rng.integers(-SYMV_AMP, SYMV_AMP + 1, size=(count, d, d), dtype=np.int32)
+    for c in range(count):
+        low = np.tril(M[c], -1)
+        M[c] = np.tril(M[c])
+        M[c] += low.T
+    x = rng.integers(-SYMV_AMP, SYMV_AMP + 1, size=(count, d), dtype=np.int64)
+    y = np.zeros((count, d), dtype=np.int64)
+    for c in range(count):
+        for r0 in range(0, d, 1024):
+            y[c, r0:r0 + 1024] = M[c, r0:r0 + 1024].astype(np.int64) @ x[c]
+    return M, x, y
+
+
+def symv_packed_model(M, x, mutant=None):
+    """``M x`` (float64, (d,)) of one symmetric matrix the way sym_gemv.h forms it. Only the blocks (I, J),
+    J <= I, of the B x B tiling are read (a diagonal block as the mirror of its lower half, the rest zero
+    padded); block (I, J) gives the direct partial ``P[I][J] = M_IJ x_J`` and, off the diagonal, the
+    transposed one ``P[J][I] = M_IJ' x_I``; block row t of the result is the sum of ``P[t][s]`` over s as
+    ``reduce_row`` takes it: RG groups of ``per = ceil(nb / RG)`` consecutive s (the last one clipped at
+    nb, later ones empty), each summed in trips of eight, then the group sums in group order. A partial
+    nothing wrote is NaN, as in the GPU test's pre-filled work buffer.
+    ``mutant`` names a mistake of the kernel (tests/test_hp_reference_cpu.py shows each one changes the
+    result on the GPU test's data): ``"drop-transposed"`` the transposed product of the last stored
+    off-diagonal block is never written; ``"clip-8"`` a group sums its first eight partials only (no
+    second trip of the loop); ``"wrong-x-block"`` the direct product of block (1, 0) takes x's block 1
+    instead of block 0."""
+    assert mutant is None or mutant in SYMV_MUTANTS
+    B = SYMV_B
+    d = len(x)
+    nb = (d + B - 1) // B
+    xp = np.zeros(nb * B, dtype=np.float64)
+    xp[:d] = x
+
+    def stored(I, J):
+        blk = np.zeros((B, B), dtype=np.float64)
+        sub = M[I * B:(I + 1) * B, J * B:(J + 1) * B]
+        blk[:sub.shape[0], :sub.shape[1]] = sub
+        if I == J:
+            blk = np.tril(blk) + np.tril(blk, -1).T
+        return blk
+
+    P = np.full((nb, nb, B), np.nan, dtype=np.float64)
+    for I in range(nb):
+        for J in range(I + 1):
+            blk = stored(I, J)
+            src = I if (mutant == "wrong-x-block" and (I, J) == (1, 0)) else J
+            P[I, J] = blk @ xp[src * B:(src + 1) * B]
+            if I != J and not (mutant == "drop-transposed" and (I, J) == (nb - 1, nb - 2)):
+                P[J, I] = blk.T @ xp[I * B:(I + 1) * B]
+    per = (nb + SYMV_RG - 1) // SYMV_RG
+    out = np.zeros(nb * B, dtype=np.float64)
+    for t in range(nb):
+        y = np.zeros(B, dtype=np.float64)
+        for g in range(SYMV_RG):
+            s0, s1 = g * per, min(g * per + per, nb)
+            acc = np.zeros(B, dtype=np.float64)
+            for s in range(s0, s1, SYMV_LOADS):
+                for u in range(SYMV_LOADS):
+                    if s + u < s1:
+                        acc = acc + P[t, s + u]
+                if mutant == "clip-8":
+                    break
+            y = y + acc
+        out[t * B:(t + 1) * B] = y
+    return out[:d]

@@ -20,6 +20,12 @@ The "K4 primal residual" section runs the chain classes once more with ``residua
 every solve a user runs) and holds the K residual sums and the per-worker rows behind them to
 hp_reference.chain_residual under the same rule (profiles/residual_classes/README.md).
 
+The star section runs the streaming engine (star_big.hip) past its first block and block row, with the
+hub in the middle of the local order and with the device stop rule firing inside a block of enqueued
+iterations, and the persistent star kernel over the hub's row layout (one, two and nine rows per helper
+wave), where the hub's copies of the duals must be the workers' duals one step on, bit for bit
+(profiles/star_classes/README.md).
+
 Each parameter list names the dispatch condition that puts its d in its class: if a threshold moves,
 the list next to it is the one to revisit.
 
@@ -506,35 +512,93 @@ def test_residual_logistic_persistent_kernel(n, m, d, zrec, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------
-# Star ADMM: star_variant (star_persistent.hip) takes QT = 13 at d <= 52 and 16 at 53..64;
-# standard_admm (algorithms/std_admm.py) sends d > 64 to the streaming engine (star_big.hip)
+# Star ADMM: star_variant (star_persistent.hip) takes QT = 13 at d <= 52 and 16 at 53..64
 STAR_PERSISTENT = [
     (3, 7, 3),
     (4, 60, 52),     # QT = 13: the top
     (4, 70, 53),     # QT = 16: the first
     (3, 40, 64),     # QT = 16: the top; m < d
+    # the hub's row layout: helper wave v of HW - 1 = 3 owns the upload rows q = v - 1, v + 2, ...
+    (2, 8, 6),       # one upload row: helper waves 2 and 3 own nothing and still pass both barriers
+    (5, 8, 6),       # the first n at which a helper (wave 1: rows 0 and 3) owns two rows
+    (26, 60, 53),    # QT = 16 at 25 rows: wave 1 owns 9, its poll takes a second batch of SB = 8 with one
+                     # wanted slot and seven masked ones (bit 8 of `got`)
 ]
-assert STAR_PERSISTENT + [(3, 80, 65)] == H.STAR_SHAPES
+# standard_admm (algorithms/std_admm.py) sends d > 64 to the streaming engine (star_big.hip): 256-thread
+# blocks over d in sb_rhs / sb_sum / sb_hubrhs, 128-element block rows in sb_post / sb_sym_reduce /
+# sb_local_obj, nb (nb + 1) / 2 stored blocks in sb_sym_part (sym_gemv.h)
+STAR_BIG = [
+    (3, 80, 65),     # the first d; odd d: the scalar path of wave_rows_dot in sb_obj
+    (2, 70, 66),     # n = 2, one worker and the hub; even d: the double2 path of wave_rows_dot
+    (4, 80, 65),     # the shape of the permuted case below, in worker order
+    (4, 150, 128),   # d = B exactly
+    (3, 150, 129),   # nb = 2: a transposed product inside a star solve; block row 1 with one live lane
+    (3, 280, 256),   # nb = 2 full; the top of one 256-thread block
+    (3, 280, 257),   # nb = 3; the second 256-thread block of sb_rhs / sb_sum / sb_hubrhs, one live thread
+]
+assert STAR_PERSISTENT + STAR_BIG == H.STAR_SHAPES
+STAR_PERSISTENT_ORDER = ((5, 8, 6), (3, 4, 0, 2, 1))   # local order: the hub (worker 4) is workgroup 1
+STAR_BIG_ORDER = ((4, 80, 65), (2, 3, 0, 1))           # the hub (worker 3) is local worker 1
+STAR_STOP_AT = 11   # test_star_big_stops_in_mid_block: inside the second block of 8 iterations
 
 
-def run_star_persistent(n, m, d):
+def _fma(a, b, c):
+    """round(a * b + c), one rounding, elementwise on float64 arrays: through exact rationals (a float
+    of a Fraction is correctly rounded)."""
+    from fractions import Fraction
+    flat = [float(Fraction(x) * Fraction(y) + Fraction(z))
+            for x, y, z in zip(np.ravel(a).tolist(), np.ravel(b).tolist(), np.ravel(c).tolist())]
+    return np.asarray(flat, dtype=np.float64).reshape(np.shape(c))
+
+
+def _mirror_state(lam_hub, lam, theta, hub, rho):
+    """The hub keeps its own copies of the workers' duals ("same arithmetic, bit-identical",
+    star_persistent.hip). When the kernel leaves they differ from the workers' own by the one step a
+    worker applies lazily: lam_hub[q] = lam[q] + rho * (theta[q] - theta[hub]), in float64 in the kernel's
+    operand order. Rows by worker id. Returns (entries that differ from the two-rounding evaluation,
+    entries that differ from the fused one (the product unrounded into the sum), largest distance from
+    the first in units of ulp(rho max|theta|))."""
+    rows = [q for q in range(theta.shape[0]) if q != hub]
+    diff = theta[rows] - theta[hub]
+    plain = lam[rows] + rho * diff
+    fused = _fma(np.full_like(diff, rho), diff, lam[rows])
+    got = lam_hub[rows]
+    ulp = np.spacing(rho * np.max(np.abs(theta)))
+    return int(np.sum(got != plain)), int(np.sum(got != fused)), float(np.max(np.abs(got - plain)) / ulp)
+
+
+def run_star_persistent(n, m, d, order=None):
+    """``order``: the local order of the workers (workgroup b runs worker order[b]); None: by id."""
     from gadmm_amd.engine.star_engine import StarEngine
     X, y, rho, _ = H.star_case(n, m, d)
-    eng = StarEngine(_dev(X), _dev(y), list(range(n)), n, rho, 0.0, 0.0, K)
+    order = list(range(n)) if order is None else [int(w) for w in order]
+    assert sorted(order) == list(range(n))
+    eng = StarEngine(_dev(X[order]), _dev(y[order]), order, n, rho, 0.0, 0.0, K)
     assert eng.eligible() and eng.last_kernel == "star-persistent"
     iters, done, _ = eng.run()
     last = int(eng.ctl.cpu()[0]) - 1  # the workers leave `lag` iterations after the cap's decision
     assert iters == K and K <= last <= K + 16, (iters, done, last)
     ref = H.star_case(n, m, d, last)[3]
-    lam_hub = _host(eng.lam_hub)[: n - 1]  # the hub's copies: updated through iteration `last`
+    lam_hub = _host(eng.lam_hub)[: n - 1]  # the hub's copies, by worker id: updated through iteration `last`
+    theta, lam = np.zeros((n, d)), np.zeros((n, d))  # by worker id
+    theta[order], lam[order] = _host(eng.theta), _host(eng.lam)
     # a worker's own dual is lazy: the update of iteration `last` would come with the next broadcast
     th_l, rho_l = ref.theta[last - 1], np.asarray(rho, dtype=H.LD)
     lam_prev = ref.dual[: n - 1] - rho_l * (th_l[: n - 1] - th_l[n - 1])
     out = {"objective": ref.err_obj(eng.objective_trace(K)) / ref.b_obj,
-           "theta": ref.err_theta(_host(eng.theta), last) / ref.b_theta,
+           "theta": ref.err_theta(theta, last) / ref.b_theta,
            "dual": ref.err_dual(lam_hub, ref.dual[: n - 1]) / ref.b_dual,
-           "worker_dual": ref.err_dual(_host(eng.lam)[: n - 1], lam_prev) / ref.b_dual}
-    assert np.all(_host(eng.lam)[n - 1] == 0)
+           "worker_dual": ref.err_dual(lam[: n - 1], lam_prev) / ref.b_dual}
+    assert np.all(lam[n - 1] == 0)
+    # the hub's copies are the workers' duals one step on, bit for bit, in the kernel's arithmetic: both
+    # sides compile to one subtraction and one FMA, so the product goes unrounded into the sum. The
+    # two-rounding evaluation of the same expression is printed (on this data it agrees at every entry,
+    # profiles/star_classes/README.md) and held to 2 ulp of rho max|theta|
+    plain, fused, ulps = _mirror_state(lam_hub, lam, theta, n - 1, float(rho))
+    print("star persistent %s%s: hub's duals against the workers' one step on: %d of %d entries differ unfused, "
+          "%d fused, at most %.2f ulp(rho max|theta|)" % ((n, m, d), "" if order == list(range(n)) else " order %s" % (order,),
+                                                       plain, (n - 1) * d, fused, ulps))
+    assert fused == 0 and ulps <= 2.0, (plain, fused, ulps)
     return out
 
 
@@ -543,24 +607,84 @@ def test_star_persistent_kernel(n, m, d):
     _report("star persistent %s" % ((n, m, d),), run_star_persistent(n, m, d))
 
 
-@pytest.mark.parametrize("exact", [False, True])
-def test_star_big_first_shape(exact):
-    """(3, 80, 65): the first d of the streaming star engine, with its default objective (the identity
-    A th = r - shift th of the solve) and with the exact one (a second GEMV by the Gram)."""
+def test_star_persistent_hub_not_last_workgroup():
+    """(5, 8, 6) in the local order (3, 4, 0, 2, 1): the hub is workgroup 1, every worker's table row and
+    objective slot is its id, not its workgroup."""
+    shape, order = STAR_PERSISTENT_ORDER
+    _report("star persistent %s order %s" % (shape, order), run_star_persistent(*shape, order=order))
+
+
+def _star_big(n, m, d, exact, order=None, max_iter=K, obj0=0.0, tol=0.0):
+    """One solve of the streaming engine over the data of ``star_case`` in the local order ``order``
+    (None: by id). Returns (the result, theta by worker id, lam by worker id)."""
     from gadmm_amd.algorithms import standard_admm
     from gadmm_amd.models import LinearRegression
-    n, m, d = 3, 80, 65
-    X, y, rho, ref = H.star_case(n, m, d)
-    model = LinearRegression(_dev(X), _dev(y))
-    a = standard_admm(model, list(range(n)), n, rho, 0.0, 0.0, K, engine_opts={"exact_objective": exact})
+    X, y, rho, _ = H.star_case(n, m, d)
+    order = list(range(n)) if order is None else [int(w) for w in order]
+    assert sorted(order) == list(range(n))
+    model = LinearRegression(_dev(X[order]), _dev(y[order]))
+    a = standard_admm(model, order, n, rho, obj0, tol, max_iter, engine_opts={"exact_objective": exact})
     assert a.extra["backend"] == "native" and a.extra["engine"].startswith("star-big"), a.extra
     assert a.extra["engine"] == "star-big(%s objective)" % ("exact" if exact else "identity")
     eng = a.extra["engine_obj"]
+    assert eng.local == order and eng.hub_li == order.index(n - 1)
+    theta, lam = np.zeros((n, d)), np.zeros((n, d))
+    theta[order], lam[order] = _host(eng.theta), _host(eng.lam)
+    assert np.all(np.isfinite(theta)) and np.all(np.isfinite(lam)) and np.all(lam[n - 1] == 0)
+    return a, theta, lam
+
+
+def _star_big_ratios(a, theta, lam, ref, k):
+    return {"objective": ref.err_obj(a.obj) / ref.b_obj, "theta": ref.err_theta(theta, k) / ref.b_theta,
+            "dual": ref.err_dual(lam) / ref.b_dual}
+
+
+@pytest.mark.parametrize("exact", [False, True])
+@pytest.mark.parametrize("n,m,d", STAR_BIG)
+def test_star_big_kernel(n, m, d, exact):
+    """The streaming star engine with its default objective (the identity A th = r - shift th of the
+    solve) and with the exact one (a second GEMV by the Gram)."""
+    ref = H.star_case(n, m, d)[3]
+    a, theta, lam = _star_big(n, m, d, exact)
     assert a.iters == K and len(a.obj) == K
-    out = {"objective": ref.err_obj(a.obj) / ref.b_obj,
-           "theta": ref.err_theta(_host(eng.theta), K) / ref.b_theta,
-           "dual": ref.err_dual(_host(eng.lam)) / ref.b_dual}
-    _report("star-big %s %s" % ("exact" if exact else "identity", (n, m, d)), out)
+    _report("star-big %s %s" % ("exact" if exact else "identity", (n, m, d)), _star_big_ratios(a, theta, lam, ref, K))
+
+
+@pytest.mark.parametrize("exact", [False, True])
+def test_star_big_hub_not_last_local_worker(exact):
+    """(4, 80, 65) in the local order (2, 3, 0, 1): hub_li = 1, so the `s == hub_li` skips of sb_rhs,
+    sb_sum and sb_sym_* fall inside the worker loop and objp[gid[s]] scatters out of order."""
+    (n, m, d), order = STAR_BIG_ORDER
+    ref = H.star_case(n, m, d)[3]
+    a, theta, lam = _star_big(n, m, d, exact, order=order)
+    assert a.iters == K and len(a.obj) == K and a.extra["engine_obj"].hub_li == 1
+    _report("star-big %s %s order %s" % ("exact" if exact else "identity", (n, m, d), order),
+            _star_big_ratios(a, theta, lam, ref, K))
+
+
+def test_star_big_stops_in_mid_block():
+    """(3, 150, 129), identity objective, the default block of 8 iterations per host look, stopped by the
+    device rule at iteration 11: obj0 is the reference's objective of iteration 11 and tol half the
+    smallest gap of the ten before it (as tests/test_gpu_stop_rule.py; 0.396 = 2.5e-3 |obj0|, every
+    earlier gap >= 2 tol: no engine's rounding moves the stop). The host has enqueued 16 iterations when
+    it looks; the five behind the stop must be no-ops: theta and the duals are those of iteration 11."""
+    n, m, d = 3, 150, 129
+    full = np.asarray(H.star_case(n, m, d)[3].obj, dtype=np.float64)
+    obj0 = float(full[STAR_STOP_AT - 1])
+    tol = 0.5 * float(np.min(np.abs(full[:STAR_STOP_AT - 1] - obj0)))
+    assert tol > 1e-6 * abs(obj0) and K > STAR_STOP_AT > 8 and STAR_STOP_AT % 8 != 0, (tol, obj0)
+    ref = H.star_case(n, m, d, STAR_STOP_AT)[3]
+    assert np.array_equal(ref.obj, H.star_case(n, m, d)[3].obj[:STAR_STOP_AT])
+    a, theta, lam = _star_big(n, m, d, False, max_iter=K, obj0=obj0, tol=tol)
+    eng = a.extra["engine_obj"]
+    ctl = eng.ctl.cpu().tolist()
+    trace = _host(eng.trace)
+    print("star-big stop in mid-block %s: obj0 %.6f tol %.3f, iterations %d, converged %s, ctl (iter, done, conv) %s"
+          % ((n, m, d), obj0, tol, a.iters, a.converged, ctl[:3]))
+    assert a.iters == STAR_STOP_AT and a.converged and ctl[:3] == [STAR_STOP_AT + 1, 1, STAR_STOP_AT], (a.iters, ctl)
+    assert len(a.obj) == STAR_STOP_AT and len(trace) == K and np.array_equal(trace[:STAR_STOP_AT], a.obj)
+    assert np.all(np.isnan(trace[STAR_STOP_AT:])), trace
+    _report("star-big stop in mid-block %s" % ((n, m, d),), _star_big_ratios(a, theta, lam, ref, STAR_STOP_AT))
 
 
 # ------------------------------------------------------------------------------------------------

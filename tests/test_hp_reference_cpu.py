@@ -1,6 +1,6 @@
 """CPU tests of tests/hp_reference.py, the long-double reference of tests/test_gpu_dispatch_classes.py,
 tests/test_gpu_dgadmm_classes.py, tests/test_gpu_newton_classes.py, tests/test_gpu_first_order_classes.py,
-tests/test_gpu_setup_kernels.py and tests/test_gpu_qgadmm_classes.py.
+tests/test_gpu_setup_kernels.py, tests/test_gpu_qgadmm_classes.py and tests/test_gpu_symv_exact.py.
 
 The helper is only worth trusting if its float64 / long-double runs reproduce the committed oracle
 (gadmm_amd/oracle/reference.py) on every shape the GPU tests use: here the oracle stands where a
@@ -1108,3 +1108,46 @@ def test_residual_of_the_torch_path(n, m, d):
     ratio = ref.err_res(np.asarray(a.primal_res)) / ref.b_res
     print("torch path %s: residual err/bound %.3f (e64 %.2e)" % ((n, m, d), ratio, ref.e_res))
     assert ratio <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------
+# The block-packed symmetric GEMV (tests/test_gpu_symv_exact.py): the NumPy model of its block structure
+# equals the integer product, and each mistake the GPU test is there to catch changes the result on the
+# very data that test uses.
+@pytest.mark.parametrize("d", [129, 1025, 8193])
+def test_symv_packed_model_and_its_mutants(d):
+    """d = 129: nb = 2, the first transposed product; 1025: nb = 9, per = 2, a clipped last group and
+    empty ones; 8193: nb = 65, per = 9, a second, masked trip of the eight-loads loop. A mutant differs at
+    every d that has the path it breaks: "clip-8" needs per > 8, so only d = 8193 can see it -- at 129 and
+    1025 it IS the product, which is why the GPU test runs d = 8193."""
+    M, x, y = H.symv_int_data(d)
+    M, x, y = M[0], x[0], y[0]
+    assert np.array_equal(M, M.T) and np.abs(M).max() <= H.SYMV_AMP and np.abs(x).max() <= H.SYMV_AMP
+    if d == 129:  # the int64 product against Python integers
+        assert [int(v) for v in y] == [sum(int(a) * int(b) for a, b in zip(row, x)) for row in M]
+    good = H.symv_packed_model(M, x)
+    assert good.dtype == np.float64 and np.all(np.isfinite(good))
+    assert np.array_equal(good.astype(np.int64), y) and np.array_equal(good, y.astype(np.float64))
+    nb = -(-d // H.SYMV_B)
+    per = -(-nb // H.SYMV_RG)
+    for mutant in H.SYMV_MUTANTS:
+        bad = H.symv_packed_model(M, x, mutant)
+        live = per > H.SYMV_LOADS if mutant == "clip-8" else nb >= 2
+        wrong = int(np.sum(~(bad == good)))  # a NaN (a partial nothing wrote) counts as wrong
+        print("symv model d=%d %s: %d of %d entries differ" % (d, mutant, wrong, d))
+        assert (wrong > 0) == live, (d, mutant, wrong)
+    # the dropped transposed product surfaces as NaN: the partial is read and was never written
+    assert np.isnan(H.symv_packed_model(M, x, "drop-transposed")).any()
+
+
+def test_symv_packed_model_smallest_shapes():
+    """d = 1, 127, 128 (one diagonal block, read as the mirror of its lower half) and 1024 (per = 1, every
+    group one block): the model is the product there too."""
+    for d in (1, 127, 128, 1024):
+        M, x, y = H.symv_int_data(d)
+        assert np.array_equal(H.symv_packed_model(M[0], x[0]), y[0].astype(np.float64))
+    # the upper half of a diagonal block is never read: garbage there changes nothing
+    M, x, y = H.symv_int_data(127)
+    G = M[0].copy()
+    G[np.triu_indices(127, 1)] = 12345
+    assert np.array_equal(H.symv_packed_model(G, x[0]), y[0].astype(np.float64))
