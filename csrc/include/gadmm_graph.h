@@ -36,3 +36,13 @@ struct GraphArgs {
   u32x4* xchk;                     // XCD packing: as PersistArgs::xchk / xcd / xtag
   int xcd, xtag;
 };
+
+// Q-GGADMM (csrc/kernels/graph_quant.hip): the same launch with a quantized exchange. GraphArgs comes
+// first, unchanged (thg is not read); the quantizer's fields follow it.
+struct GraphQArgs {
+  GraphArgs g;
+  u32x4* qg;                       // [n][G] message granules, G = q_words(d, q_bits) + 1: ONE row per worker
+  int q_bits, q_pad;               // 4, 8 or 16
+  unsigned long long q_seed;
+  double* q_true;                  // optional [n][d] out: the TRUE iterates (theta receives the public models)
+};

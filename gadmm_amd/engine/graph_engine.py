@@ -5,6 +5,10 @@ one GPU: every worker is a resident wave that holds its cached inverse ``(A_n + 
 and its Gram in VGPRs; theta travels as tagged granules, one table row per worker; the stop rule runs
 on the device (the monitor workgroup). The specification is ``algorithms/ggadmm.py``.
 
+With ``quant=(bits, seed)`` the launch is Q-GGADMM (csrc/kernels/graph_quant.hip): the exchange is the
+quantized difference to each worker's public model, packed as in Q-GADMM (``algorithms/quantize.py``);
+``theta`` then holds the public models and ``theta_true`` the true iterates.
+
 Every device buffer is allocated and filled on the engine's own stream, the stream of the launch, so
 no fill can land while the kernel's workgroups already post their granules.
 """
@@ -28,16 +32,23 @@ class NativeGraphEngine:
     MAX_D = 64
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, graph, rho: float, obj0: float, tol: float, max_iter: int,
-                 precomputed=None, xcd: int = 2, residual: bool = True):
+                 precomputed=None, xcd: int = 2, residual: bool = True, quant=None):
         """``X`` (n, m, d), ``y`` (n, m): every worker's shard, in worker order (``graph.n`` of them).
         ``precomputed``: ``(A, b, yy)`` of those shards (the Gram is then not recomputed). ``xcd``: as
         ``NativeChainEngine`` (0 default grid, 1 packed onto one XCD, 2 also L2-resident plain stores
         once the kernel has verified the placement; speed only). ``residual``: the tails also emit the
-        K4 primal residual rows (``rres``, ``primal_residual``)."""
+        K4 primal residual rows (``rres``, ``primal_residual``). ``quant``: ``(bits, seed)``, ``bits`` in
+        {4, 8, 16} -- Q-GGADMM: ``theta`` receives the public models, ``theta_true`` the true iterates,
+        ``q_msg`` shows every worker's last message, the K4 rows are taken on the public models."""
         if not X.is_cuda:
             raise ValueError("NativeGraphEngine runs on a HIP device; use graph_admm(backend='torch') on CPU")
         self.lib = native.require()
         native.check_graph_abi(self.lib)
+        self.quant = None
+        if quant is not None:
+            from ..algorithms.quantize import check_bits, granules_per_row
+            native.check_graph_q_abi(self.lib)
+            self.quant = (check_bits(quant[0]), int(quant[1]))
         self.graph = graph
         self.device = X.device
         self.n, self.d = int(X.shape[0]), int(X.shape[2])
@@ -79,6 +90,11 @@ class NativeGraphEngine:
             self._decg = torch.zeros((self.ring,), dtype=torch.int64, device=dev)
             self._dec_push = torch.tensor([self._decg.data_ptr()], dtype=torch.int64, device=dev)
             self._xchk = torch.zeros((256 * 4,), dtype=torch.int32, device=dev)
+            if self.quant is not None:
+                # the message table, zeroed once like thg (tags are salted per launch), and the true iterates
+                self.q_granules = granules_per_row(d, self.quant[0])
+                self._qg = torch.zeros((n * self.q_granules * 4,), dtype=torch.int32, device=dev)
+                self.theta_true = torch.zeros((n, d), dtype=f64, device=dev)
         self.stream.synchronize()
         self._epoch = 0
         self._rb_host = None
@@ -106,22 +122,39 @@ class NativeGraphEngine:
         a.xchk, a.xcd = self._xchk.data_ptr(), self.xcd
         return a
 
+    def _q_args(self, timeout_s: float = 20.0) -> native.GraphQArgs:
+        q = native.GraphQArgs()
+        q.g = self._args(timeout_s)
+        q.qg, q.q_bits, q.q_seed = self._qg.data_ptr(), self.quant[0], self.quant[1] & ((1 << 64) - 1)
+        q.q_true = self.theta_true.data_ptr()
+        return q
+
     def kernel_class(self) -> int:
-        """Granules the launch polls back to back (2, 4, 8, 16 or 32); 0: the shape is not eligible."""
+        """Neighbours the launch polls back to back (2, 4, 8, 16 or 32; with ``quant`` at most 16, two
+        granules each); 0: the shape is not eligible."""
+        if self.quant is not None:
+            return int(self.lib.gadmm_graph_persistent_q_class(ctypes.byref(self._q_args())))
         return int(self.lib.gadmm_graph_persistent_class(ctypes.byref(self._args())))
 
     def resident_capacity(self) -> int:
         key = ("cap", getenv("GADMM_CU_BUDGET"))
         memo = self.__dict__.setdefault("_cap_memo", {})
         if key not in memo:
-            memo[key] = int(self.lib.gadmm_graph_persistent_capacity(ctypes.byref(self._args())))
+            if self.quant is not None:
+                memo[key] = int(self.lib.gadmm_graph_persistent_q_capacity(ctypes.byref(self._q_args())))
+            else:
+                memo[key] = int(self.lib.gadmm_graph_persistent_capacity(ctypes.byref(self._args())))
         return memo[key]
+
+    def _lds_bytes(self) -> int:
+        fn = self.lib.gadmm_graph_persistent_q_lds if self.quant is not None else self.lib.gadmm_graph_persistent_lds
+        return int(fn(self.n, self.graph.max_degree))
 
     def refusal(self) -> Optional[str]:
         """Why the persistent kernel does not take this engine, decided without a launch; None: it does."""
         if self.d > self.MAX_D:
             return "d > 64"
-        if int(self.lib.gadmm_graph_persistent_lds(self.n, self.graph.max_degree)) > 65536:
+        if self._lds_bytes() > 65536:
             return "max_degree %d: the neighbour staging does not fit in LDS" % self.graph.max_degree
         if self.max_iter + self.LAG + 1 >= (1 << 20):
             return "max_iter past the 2^20 iteration tags"
@@ -154,10 +187,16 @@ class NativeGraphEngine:
         if why is not None and not why.startswith("ResidencyError"):
             raise RuntimeError("persistent graph kernel not eligible: %s" % why)
         self._epoch = self._epoch % 4095 + 1  # fresh tag salt: the tables of the last solve never match
-        a = self._args(timeout_s)
-        self.last_kernel = "persistent-graph(deg<=%d)" % self._class_bound()
+        if self.quant is not None:
+            a = self._q_args(timeout_s)
+            self.last_kernel = "persistent-graph-Q(deg<=%d,b=%d)" % (self._class_bound(), self.quant[0])
+            launch = self.lib.gadmm_graph_persistent_q_launch
+        else:
+            a = self._args(timeout_s)
+            self.last_kernel = "persistent-graph(deg<=%d)" % self._class_bound()
+            launch = self.lib.gadmm_graph_persistent_launch
         t0 = time.perf_counter()
-        rc = int(self.lib.gadmm_graph_persistent_launch(ctypes.byref(a), self.stream.cuda_stream))
+        rc = int(launch(ctypes.byref(a), self.stream.cuda_stream))
         if rc == -2:
             raise ResidencyError(self.lib.gadmm_last_error().decode())
         native.check(rc, "graph_persistent_launch")
@@ -183,7 +222,8 @@ class NativeGraphEngine:
 
     def _class_bound(self) -> int:
         k, g = self.kernel_class(), self.graph.max_degree
-        return k if g <= k else 32 * ((g + 31) // 32)
+        top = 16 if self.quant is not None else 32  # the largest poll group; past it, groups of that size
+        return k if g <= k else top * ((g + top - 1) // top)
 
     # ---------------------------------------------------------------------------------------------
     def traces(self, upto: int):
@@ -209,6 +249,17 @@ class NativeGraphEngine:
         """(max_iter, n) K4 rows by worker id: a tail's entry is the squared distance over its edges,
         a head's stays 0. None unless built with ``residual=True``."""
         return None if self._rres is None else self._rres.view(self.max_iter, self.n)
+
+    @property
+    def q_msg(self) -> Optional[torch.Tensor]:
+        """(n, G) uint64 words of every worker's last message as it sits in the message table (word 0 the
+        bits of R, then the code words), tags stripped; None without ``quant``. Shown as int64 (torch has no
+        arithmetic on uint64): ``.cpu().numpy().view(numpy.uint64)``."""
+        if self.quant is None:
+            return None
+        self.stream.synchronize()
+        g = self._qg.view(self.n, self.q_granules, 4).to(torch.int64) & 0xffffffff
+        return (g[:, :, 3] << 32) | g[:, :, 1]
 
     def primal_residual(self, upto: int) -> Optional[np.ndarray]:
         if self._rres is None or upto <= 0:

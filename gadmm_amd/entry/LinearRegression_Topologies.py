@@ -4,10 +4,14 @@ worker 0, complete bipartite even vs odd ids) and rho. The chain is GADMM; the o
 same gap in a fraction of its iterations (algorithms/ggadmm.py). Outputs one run per graph x rho,
 ``GGADMM_<graph>_rho<rho>``, with the usual summary, per-iteration traces and the three panels (gap
 against iteration / cumulative communication / clock); each summary names its engine, kernel and graph.
+``quant_bits`` (4, 8, 16; seed ``quant_seed``) adds a Q-GGADMM run per graph x rho x bit width next to
+them, ``Q-GGADMM_b<bits>_<graph>_rho<rho>``: the quantized exchange of Q-GADMM on the graph, its
+communication counted in equivalent full-precision messages.
 
     python -m gadmm_amd LinearRegression_Topologies
     python -m gadmm_amd LinearRegression_Topologies --quick --device cpu
     python -m gadmm_amd LinearRegression_Topologies --set graphs=ring,grid:3x8 rhos=1,3
+    python -m gadmm_amd LinearRegression_Topologies --set quant_bits=8,4
 """
 from .common import Problem, attach_modelled_clock, run_entry
 
@@ -24,17 +28,30 @@ def body(cfg, sess, args, writer):
     prob = Problem(cfg, sess)
     sess.log("  obj0 = %.13f (normal equations, opt_sol_closedForm.m)" % prob.obj0)
     runs = {}
+
+    def keep(key, r, spec, graph, rho):
+        for k in ("engine_obj", "state", "theta_true", "q_msg"):
+            r.extra.pop(k, None)
+        r.extra.update(graph_name=str(spec), graph_edges=len(graph.edges), graph_max_degree=graph.max_degree,
+                       rho=float(rho))
+        runs[key] = attach_modelled_clock(r, prob.model, rho, sess)
+
     for spec in cfg.graphs:
         graph = parse_graph(spec, prob.n_total)
         for rho in cfg.rhos:
             with roctx_range("ggadmm %s rho=%g" % (spec, rho)):
                 r = graph_admm(prob.model, graph, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, backend=args.backend,
                                name="GGADMM(%s,rho=%g)" % (spec, rho))
-            r.extra.pop("engine_obj", None)
-            r.extra.pop("state", None)
-            r.extra.update(graph_name=str(spec), graph_edges=len(graph.edges), graph_max_degree=graph.max_degree,
-                           rho=float(rho))
-            runs["GGADMM_%s_rho%g" % (spec, rho)] = attach_modelled_clock(r, prob.model, rho, sess)
+            keep("GGADMM_%s_rho%g" % (spec, rho), r, spec, graph, rho)
+    for bits in cfg.quant_bits:  # Q-GGADMM next to them
+        for spec in cfg.graphs:
+            graph = parse_graph(spec, prob.n_total)
+            for rho in cfg.rhos:
+                with roctx_range("q-ggadmm b=%d %s rho=%g" % (int(bits), spec, rho)):
+                    r = graph_admm(prob.model, graph, rho, prob.obj0, cfg.acc, cfg.gadmm_iters, backend=args.backend,
+                                   name="Q-GGADMM(b=%d,%s,rho=%g)" % (int(bits), spec, rho),
+                                   quantize=(int(bits), cfg.quant_seed))
+                keep("Q-GGADMM_b%d_%s_rho%g" % (int(bits), spec, rho), r, spec, graph, rho)
     return {"runs": runs, "obj0": prob.obj0, "dataset": prob.dataset_meta,
             "figure_groups": {"LinearRegression_Topologies": runs}}
 

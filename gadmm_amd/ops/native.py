@@ -173,6 +173,31 @@ def check_graph_abi(lib) -> None:
                            "%s vs %s" % (list(buf[:k]), graph_abi_expected()))
 
 
+class GraphQArgs(ctypes.Structure):
+    """Mirror of ``GraphQArgs`` of csrc/include/gadmm_graph.h (persistent Q-GGADMM): ``GraphArgs`` first,
+    then the quantizer's fields."""
+    _fields_ = [
+        ("g", GraphArgs), ("qg", c_void_p), ("q_bits", c_int), ("q_pad", c_int),
+        ("q_seed", ctypes.c_ulonglong), ("q_true", c_void_p),
+    ]
+
+
+def graph_q_abi_expected() -> list:
+    """What ``gadmm_graph_q_abi_layout`` must report for the ``GraphQArgs`` mirror above."""
+    Q = GraphQArgs
+    return [ctypes.sizeof(Q), Q.g.offset, Q.qg.offset, Q.q_bits.offset, Q.q_seed.offset, Q.q_true.offset,
+            ctypes.sizeof(GraphArgs)]
+
+
+def check_graph_q_abi(lib) -> None:
+    """ABI self-check of ``GraphQArgs`` against the built library (raises on a mismatch: a stale build)."""
+    buf = (c_longlong * 16)()
+    k = lib.gadmm_graph_q_abi_layout(buf, 16)
+    if list(buf[:k]) != graph_q_abi_expected():
+        raise RuntimeError("GraphQArgs layout mismatch between gadmm_amd/ops/native.py and the native library: "
+                           "%s vs %s" % (list(buf[:k]), graph_q_abi_expected()))
+
+
 MODEL_LINEAR, MODEL_LOGISTIC = 0, 1
 
 
@@ -250,6 +275,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_graph_persistent_class": (c_int, [ctypes.POINTER(GraphArgs)]),
         "gadmm_graph_persistent_capacity": (c_long, [ctypes.POINTER(GraphArgs)]),
         "gadmm_graph_persistent_launch": (c_int, [ctypes.POINTER(GraphArgs), c_void_p]),
+        "gadmm_graph_q_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_graph_persistent_q_lds": (c_long, [c_int, c_int]),
+        "gadmm_graph_persistent_q_class": (c_int, [ctypes.POINTER(GraphQArgs)]),
+        "gadmm_graph_persistent_q_capacity": (c_long, [ctypes.POINTER(GraphQArgs)]),
+        "gadmm_graph_persistent_q_launch": (c_int, [ctypes.POINTER(GraphQArgs), c_void_p]),
         "gadmm_sym_pack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "gadmm_sym_packed_doubles": (c_long, [c_int]),
         "gadmm_ipc_box_bytes": (c_long, [c_int, c_int, c_int, c_int]),
