@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <hip/hip_runtime.h>
 #include "gadmm_chain.h"
+#include "gadmm_common.h"
+#include "gadmm_graph.h"
 
 extern "C" {
 
@@ -61,3 +63,70 @@ bool gadmm_sweep_shares(const PersistArgs& a, const PersistArgs& o);
 // own not on the one XCD that its 8-strided blocks are dealt to.
 int gadmm_sweep_launch(const SweepLaunch& l, const PersistArgs* batch, int nb, const int* blocks,
                        PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st);
+
+// gadmm_sweep_shares for the graph sweeps (graph_persistent.hip, graph_quant.hip): ctl, trace, theta, mu,
+// thg, objg, decg, dec_push, xchk, and tstamp / rres where a has them. A, b, yy, Minv and the CSR arrays
+// may be shared. The Q launcher adds qg and q_true.
+bool gadmm_graph_sweep_shares(const GraphArgs& a, const GraphArgs& o);
+// The graph sweep kernels' third argument: log2 of slot j's degree class dk[j] (2 .. 32) in bits 4 j .. 4 j + 3.
+unsigned gadmm_graph_sweep_classes(const int* dk, int nb);
+
+// The same tail over any slot argument type (gadmm_sweep_launch is its PersistArgs instantiation; the
+// graph sweeps run it over GraphArgs / GraphQArgs). SweepSlot<Args> names where a slot keeps what the
+// tail sets: xcd(), xtag(), and set_dbg() (a no-op where the kernel has no debug word).
+template <class Args>
+struct SweepSlot;
+
+template <>
+struct SweepSlot<PersistArgs> {
+  static int& xcd(PersistArgs& a) { return a.xcd; }
+  static int& xtag(PersistArgs& a) { return a.xtag; }
+  static void set_dbg(PersistArgs& a, int v) { a.dbg = v; }
+};
+
+template <>
+struct SweepSlot<GraphArgs> {
+  static int& xcd(GraphArgs& a) { return a.xcd; }
+  static int& xtag(GraphArgs& a) { return a.xtag; }
+  static void set_dbg(GraphArgs&, int) {}
+};
+
+template <>
+struct SweepSlot<GraphQArgs> {
+  static int& xcd(GraphQArgs& a) { return a.g.xcd; }
+  static int& xtag(GraphQArgs& a) { return a.g.xtag; }
+  static void set_dbg(GraphQArgs&, int) {}
+};
+
+// The residency half of the tail (no argument type in it): the sum of blocks[] against the resident
+// capacity of the kernel, each blocks[j] against the CUs of one XCD, and the dynamic-LDS attribute past
+// 64 KiB. *max_blocks: the widest slot. 0, -2 (refused), or a HIP error.
+int gadmm_sweep_residency(const SweepLaunch& l, int nb, const int* blocks, int* max_blocks);
+// GADMM_BLK_DBG (0 if unset) and GADMM_XCD (-1 if unset), as the tail reads them per launch.
+void gadmm_sweep_env(int* dbg, int* xenv);
+
+// extra: nullable pointer to a third kernel argument (after batch and nb), e.g. the graph sweeps' classes.
+template <class Args>
+int gadmm_sweep_launch_as(const SweepLaunch& l, const Args* batch, int nb, const int* blocks, Args* host_stage,
+                          Args* dev_stage, hipStream_t st, void* extra = nullptr) {
+  int max_blocks = 0;
+  if (const int rc = gadmm_sweep_residency(l, nb, blocks, &max_blocks)) return rc;
+  int dbg = 0, xenv = -1;
+  gadmm_sweep_env(&dbg, &xenv);
+  for (int j = 0; j < nb; ++j) {
+    Args& ka = host_stage[j];
+    ka = batch[j];
+    if (l.dbg) SweepSlot<Args>::set_dbg(ka, dbg);
+    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
+    const int x = xenv >= 0 ? xenv : SweepSlot<Args>::xcd(ka);
+    SweepSlot<Args>::xcd(ka) = x >= 2 ? 2 : 1;
+    // fresh placement-check tag per slot and per launch (a continuation re-runs the check): no memset of xchk
+    SweepSlot<Args>::xtag(ka) = (int)gadmm_next_xtag();
+  }
+  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(Args), hipMemcpyHostToDevice, st));
+  const Args* dbatch = dev_stage;
+  void* kargs[] = {&dbatch, &nb, extra};
+  GADMM_CHECK(hipLaunchKernel(l.fn, dim3(8 * max_blocks), dim3(l.threads), kargs, l.shm, st));
+  GADMM_CHECK(hipGetLastError());
+  return 0;
+}

@@ -88,8 +88,21 @@ __device__ __forceinline__ bool poll_all(__amdgpu_buffer_rsrc_t rth, const int (
   return ok;
 }
 
-template <int QT, int DK>
-__global__ void __launch_bounds__(64) graph_persistent_kernel(GraphArgs a) {
+// A sweep slot's GraphArgs (graph_persistent_sweep_kernel below): written by the host before the launch
+// and never by a kernel, so it is read like kernel arguments, through the constant address space
+// (wave-uniform scalar loads), as SweepArgs of persist_device.h.
+typedef __attribute__((address_space(4))) GraphArgs GraphSweepArgs;
+
+// The persistent GGADMM solve (described above) as a body shared by the single-solve and the sweep
+// kernel, as q_persistent_body of chain_quant.hip.
+// SWEEP: the body runs as one slot of graph_persistent_sweep_kernel: always 8-strided, this slot's
+// blocks are blockIdx.x >> 3, and a block past the slot's own n + 1 leaves before the placement check
+// and before any barrier (place_block_sweep). Everything the body reads or writes is named by the
+// slot's own arguments, and the LDS layout is the slot's own (its n and max_degree) inside a dynamic
+// allocation sized for the launch's largest.
+// GA: GraphArgs (the kernel's own argument) or GraphSweepArgs (a slot's entry).
+template <int QT, int DK, bool SWEEP, class GA>
+__device__ __forceinline__ void graph_body(const GA& a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int* xflag = reinterpret_cast<int*>(lds);  // the placement verdict (xcd_verdict's LDS word)
   const int d = a.d, n = a.n;
@@ -97,7 +110,9 @@ __global__ void __launch_bounds__(64) graph_persistent_kernel(GraphArgs a) {
   const __amdgpu_buffer_rsrc_t rth = rsrc_of(a.thg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
-  const Placement pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  Placement pl;
+  if constexpr (SWEEP) pl = place_block_sweep(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  else pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
   if (pl.spacer) return;
   const int bid = pl.bid;
   const bool local = pl.local;
@@ -221,6 +236,38 @@ __global__ void __launch_bounds__(64) graph_persistent_kernel(GraphArgs a) {
   if (lane == 0) post_outcome<false>(a.ctl, abort, bid, stop_code, stop_iter, it);
 }
 
+template <int QT, int DK>
+__global__ void __launch_bounds__(64) graph_persistent_kernel(GraphArgs a) {
+  graph_body<QT, DK, false>(a);
+}
+
+// Up to 8 independent GGADMM solves in one launch, one per XCD: slot j = blockIdx.x & 7 runs solve j on
+// the blocks b % 8 == j, i.e. on the blocks that the single-solve launch leaves as exiting spacers.
+// batch[j] is solve j's own GraphArgs: its own graph (CSR arrays, launch order), theta / mu, granule
+// table, objective and decision rings, ctl, trace, tstamp, rres, xchk, tag salt, rho, stop rule and
+// deadline; only the read-only inputs (A, b, yy, Minv, the CSR arrays) may be shared. Slots may differ in
+// n, d (within the QT class), graph and degree class: `classes` holds log2 of slot j's own DK (what
+// pick_graph_variant gives its single launch) in bits 4 j .. 4 j + 3, and the wave-uniform switch below
+// sends the slot into the body of that class, so every slot executes the poll code of its own single
+// solve (a chain member does not pay for a star's 32-wide poll group). The kernel's registers are those
+// of its widest body. Nothing assumes WHICH XCD a slot gets (place_block_sweep).
+template <int QT>
+__global__ void __launch_bounds__(64) graph_persistent_sweep_kernel(const GraphArgs* __restrict__ batch, int nb,
+                                                                    unsigned classes) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  const GraphSweepArgs& a = *(const GraphSweepArgs*)(batch + j);
+  switch ((classes >> (4 * j)) & 15u) {
+    case 1: graph_body<QT, 2, true>(a); break;
+    case 2: graph_body<QT, 4, true>(a); break;
+    case 3: graph_body<QT, 8, true>(a); break;
+    case 4: graph_body<QT, 16, true>(a); break;
+    default: graph_body<QT, 32, true>(a); break;
+  }
+}
+
+#define GRAPH_SWEEP_CAPACITY 8
+
 struct GVariant {
   const void* fn = nullptr;
   size_t shm = 0;
@@ -245,6 +292,33 @@ GVariant pick_graph_variant(const GraphArgs& a) {
   v.fn = a.d <= 52 ? graph_fn<13>(v.dk) : graph_fn<16>(v.dk);
   v.shm = (size_t)graph_lds_doubles(a.n, a.max_degree) * 8;
   return v;
+}
+
+// What the launch of one solve asks of its arguments, before residency (`who` prefixes the reason in
+// gadmm_set_error): 0 fine, -1 malformed, -2 the staging does not fit in LDS. No HIP call.
+int graph_entry_check(const GraphArgs& a, const GVariant& v, const char* who) {
+  if (!v.fn) {
+    gadmm_set_error("%s: d=%d, n=%d, max_degree=%d not eligible (1 <= d <= 64, n >= 2)", who, a.d, a.n, a.max_degree);
+    return -1;
+  }
+  if (!a.nb_ptr || !a.nb_idx || !a.wid || !a.is_head || !a.Minv || !a.A || !a.b || !a.yy || !a.theta || !a.mu ||
+      !a.thg || !a.objg || !a.decg || !a.dec_push || !a.trace || !a.ctl) {
+    gadmm_set_error("%s: a required buffer is null", who);
+    return -1;
+  }
+  if (a.n_local != a.n || a.nranks != 1 || a.timeline_iters != 0) {
+    gadmm_set_error("%s: one GPU, every worker local", who);
+    return -1;
+  }
+  if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter < 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+    gadmm_set_error("%s: ring must exceed lag + 1, iteration tags are limited to 2^20", who);
+    return -1;
+  }
+  if (v.shm > 65536) {
+    gadmm_set_error("%s: max_degree=%d needs %zu bytes of LDS staging, 65536 fit", who, a.max_degree, v.shm);
+    return -2;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -282,29 +356,7 @@ long gadmm_graph_persistent_capacity(const GraphArgs* args) {
 int gadmm_graph_persistent_launch(const GraphArgs* args, hipStream_t st) {
   const GraphArgs& a = *args;
   const GVariant v = pick_graph_variant(a);
-  if (!v.fn) {
-    gadmm_set_error("persistent graph kernel: d=%d, n=%d, max_degree=%d not eligible (1 <= d <= 64, n >= 2)", a.d, a.n,
-                    a.max_degree);
-    return -1;
-  }
-  if (!a.nb_ptr || !a.nb_idx || !a.wid || !a.is_head || !a.Minv || !a.A || !a.b || !a.yy || !a.theta || !a.mu ||
-      !a.thg || !a.objg || !a.decg || !a.dec_push || !a.trace || !a.ctl) {
-    gadmm_set_error("persistent graph kernel: a required buffer is null");
-    return -1;
-  }
-  if (a.n_local != a.n || a.nranks != 1 || a.timeline_iters != 0) {
-    gadmm_set_error("persistent graph kernel: one GPU, every worker local");
-    return -1;
-  }
-  if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter < 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-    gadmm_set_error("persistent graph kernel: ring must exceed lag + 1, iteration tags are limited to 2^20");
-    return -1;
-  }
-  if (v.shm > 65536) {
-    gadmm_set_error("persistent graph kernel: max_degree=%d needs %zu bytes of LDS staging, 65536 fit", a.max_degree,
-                    v.shm);
-    return -2;
-  }
+  if (const int rc = graph_entry_check(a, v, "persistent graph kernel")) return rc;
   const int blocks = a.n + 1;
   const long cap = gadmm_resident_capacity(v.fn, 64, v.shm);
   if (blocks > cap) {  // every workgroup must be resident together (they spin on each other)
@@ -318,6 +370,56 @@ int gadmm_graph_persistent_launch(const GraphArgs* args, hipStream_t st) {
   GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.xcd > 0 ? 8 * blocks : blocks), dim3(64), kargs, v.shm, st));
   GADMM_CHECK(hipGetLastError());
   return 0;
+}
+
+// Solves one launch of graph_persistent_sweep_kernel can run side by side (one per XCD).
+int gadmm_graph_persistent_sweep_capacity() { return GRAPH_SWEEP_CAPACITY; }
+
+// nb <= 8 independent GGADMM solves (one register class: d <= 52 or 53..64; any graphs, each slot on the
+// degree class of its own single launch) in ONE launch, solve j on the blocks b % 8 == j. Every entry
+// passes the single launch's checks and names its own written buffers (gadmm_graph_sweep_shares) and a
+// placement-check buffer. Dynamic LDS: the largest entry's. Staging buffers and the residency refusal
+// (-2: the sum of the workgroups, or one solve's n + 1 past the CUs of an XCD): gadmm_sweep_launch_as.
+// -1: refused before any HIP call.
+int gadmm_graph_persistent_sweep_launch(const GraphArgs* batch, int nb, GraphArgs* host_stage, GraphArgs* dev_stage,
+                                        hipStream_t st) {
+  const char* name = "persistent graph sweep";
+  if (!gadmm_sweep_batch_ok(name, batch, nb, GRAPH_SWEEP_CAPACITY, host_stage, dev_stage)) return -1;
+  int blocks[8], dk[8];
+  size_t shm = 0;
+  for (int j = 0; j < nb; ++j) {
+    const GraphArgs& a = batch[j];
+    char who[48];
+    snprintf(who, sizeof(who), "%s: solve %d", name, j);
+    if ((a.d <= 52) != (batch[0].d <= 52)) {
+      gadmm_set_error("%s: solves of different register classes (d = %d and %d; d <= 52 or 53..64)", name, batch[0].d,
+                      a.d);
+      return -1;
+    }
+    const GVariant v = pick_graph_variant(a);
+    if (const int rc = graph_entry_check(a, v, who)) return rc;
+    if (!a.xchk) {
+      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
+      return -1;
+    }
+    blocks[j] = a.n + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i)
+      if (gadmm_graph_sweep_shares(a, batch[i])) {
+        gadmm_set_error("%s: solves %d and %d share a buffer that both write", name, i, j);
+        return -1;
+      }
+    dk[j] = v.dk;
+    if (v.shm > shm) shm = v.shm;
+  }
+  unsigned classes = gadmm_graph_sweep_classes(dk, nb);
+  const void* fn = batch[0].d <= 52 ? (const void*)graph_persistent_sweep_kernel<13>
+                                    : (const void*)graph_persistent_sweep_kernel<16>;
+  return gadmm_sweep_launch_as<GraphArgs>({fn, 64, shm, name, false}, batch, nb, blocks, host_stage, dev_stage, st,
+                                          &classes);
 }
 
 }  // extern "C"

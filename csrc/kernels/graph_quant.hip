@@ -131,17 +131,27 @@ __device__ __forceinline__ bool poll_all_q(__amdgpu_buffer_rsrc_t rq, const int 
   return all;
 }
 
-template <int QT, int DK>
-__global__ void __launch_bounds__(64) graph_persistent_q_kernel(GraphQArgs qa) {
+// A sweep slot's GraphQArgs (graph_persistent_q_sweep_kernel below), read through the constant address
+// space like kernel arguments (as GraphSweepArgs of graph_persistent.hip).
+typedef __attribute__((address_space(4))) GraphQArgs GraphQSweepArgs;
+
+// The persistent Q-GGADMM solve (described above) as a body shared by the single-solve and the sweep
+// kernel. SWEEP: one slot of graph_persistent_q_sweep_kernel: 8-strided, blocks blockIdx.x >> 3, a block
+// past the slot's own n + 1 leaves before the placement check and before any barrier; the LDS layout is
+// the slot's own. QA: GraphQArgs (the kernel's own argument) or GraphQSweepArgs (a slot's entry).
+template <int QT, int DK, bool SWEEP, class QA>
+__device__ __forceinline__ void graph_q_body(const QA& qa) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int* xflag = reinterpret_cast<int*>(lds);  // the placement verdict (xcd_verdict's LDS word)
-  const GraphArgs& a = qa.g;
+  const auto& a = qa.g;
   const int d = a.d, n = a.n;
   const int lane = threadIdx.x;
   const __amdgpu_buffer_rsrc_t rq = rsrc_of(qa.qg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
-  const Placement pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  Placement pl;
+  if constexpr (SWEEP) pl = place_block_sweep(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  else pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
   if (pl.spacer) return;
   const int bid = pl.bid;
   const bool local = pl.local;
@@ -288,6 +298,32 @@ __global__ void __launch_bounds__(64) graph_persistent_q_kernel(GraphQArgs qa) {
   if (lane == 0) post_outcome<false>(a.ctl, abort, bid, stop_code, stop_iter, it);
 }
 
+template <int QT, int DK>
+__global__ void __launch_bounds__(64) graph_persistent_q_kernel(GraphQArgs qa) {
+  graph_q_body<QT, DK, false>(qa);
+}
+
+// Up to 8 independent Q-GGADMM solves in one launch, one per XCD, as graph_persistent_sweep_kernel: slot
+// j = blockIdx.x & 7 runs batch[j] on the blocks b % 8 == j, on the body of its own degree class (log2 of
+// it in bits 4 j .. 4 j + 3 of `classes`; 2 .. 16 here). Slots may differ in graph, n, d (within the QT
+// class), bits and seed; each names its own message table, public models, true iterates, duals, rings,
+// ctl, trace and xchk.
+template <int QT>
+__global__ void __launch_bounds__(64) graph_persistent_q_sweep_kernel(const GraphQArgs* __restrict__ batch, int nb,
+                                                                      unsigned classes) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  const GraphQSweepArgs& qa = *(const GraphQSweepArgs*)(batch + j);
+  switch ((classes >> (4 * j)) & 15u) {
+    case 1: graph_q_body<QT, 2, true>(qa); break;
+    case 2: graph_q_body<QT, 4, true>(qa); break;
+    case 3: graph_q_body<QT, 8, true>(qa); break;
+    default: graph_q_body<QT, 16, true>(qa); break;
+  }
+}
+
+#define GRAPH_Q_SWEEP_CAPACITY 8
+
 struct GQVariant {
   const void* fn = nullptr;
   size_t shm = 0;
@@ -313,6 +349,39 @@ GQVariant pick_graph_q_variant(const GraphQArgs& qa) {
   v.fn = a.d <= 52 ? graph_q_fn<13>(v.dk) : graph_q_fn<16>(v.dk);
   v.shm = (size_t)graph_q_lds_doubles(a.n, a.max_degree) * 8;
   return v;
+}
+
+// What the launch of one solve asks of its arguments, before residency (`who` prefixes the reason in
+// gadmm_set_error): 0 fine, -1 malformed (q_bits outside {4, 8, 16} among them), -2 the staging does not
+// fit in LDS. No HIP call.
+int graph_q_entry_check(const GraphQArgs& qa, const GQVariant& v, const char* who) {
+  const GraphArgs& a = qa.g;
+  if (qa.q_bits != 4 && qa.q_bits != 8 && qa.q_bits != 16) {
+    gadmm_set_error("%s: q_bits must be 4, 8 or 16, got %d", who, qa.q_bits);
+    return -1;
+  }
+  if (!v.fn) {
+    gadmm_set_error("%s: d=%d, n=%d, max_degree=%d not eligible (1 <= d <= 64, n >= 2)", who, a.d, a.n, a.max_degree);
+    return -1;
+  }
+  if (!a.nb_ptr || !a.nb_idx || !a.wid || !a.is_head || !a.Minv || !a.A || !a.b || !a.yy || !a.theta || !a.mu ||
+      !qa.qg || !a.objg || !a.decg || !a.dec_push || !a.trace || !a.ctl) {
+    gadmm_set_error("%s: a required buffer is null", who);
+    return -1;
+  }
+  if (a.n_local != a.n || a.nranks != 1 || a.timeline_iters != 0) {
+    gadmm_set_error("%s: one GPU, every worker local", who);
+    return -1;
+  }
+  if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter < 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
+    gadmm_set_error("%s: ring must exceed lag + 1, iteration tags are limited to 2^20", who);
+    return -1;
+  }
+  if (v.shm > 65536) {
+    gadmm_set_error("%s: max_degree=%d needs %zu bytes of LDS staging, 65536 fit", who, a.max_degree, v.shm);
+    return -2;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -351,34 +420,8 @@ long gadmm_graph_persistent_q_capacity(const GraphQArgs* args) {
 int gadmm_graph_persistent_q_launch(const GraphQArgs* args, hipStream_t st) {
   const GraphQArgs& qa = *args;
   const GraphArgs& a = qa.g;
-  if (qa.q_bits != 4 && qa.q_bits != 8 && qa.q_bits != 16) {
-    gadmm_set_error("persistent graph Q kernel: q_bits must be 4, 8 or 16, got %d", qa.q_bits);
-    return -1;
-  }
   const GQVariant v = pick_graph_q_variant(qa);
-  if (!v.fn) {
-    gadmm_set_error("persistent graph Q kernel: d=%d, n=%d, max_degree=%d not eligible (1 <= d <= 64, n >= 2)", a.d,
-                    a.n, a.max_degree);
-    return -1;
-  }
-  if (!a.nb_ptr || !a.nb_idx || !a.wid || !a.is_head || !a.Minv || !a.A || !a.b || !a.yy || !a.theta || !a.mu ||
-      !qa.qg || !a.objg || !a.decg || !a.dec_push || !a.trace || !a.ctl) {
-    gadmm_set_error("persistent graph Q kernel: a required buffer is null");
-    return -1;
-  }
-  if (a.n_local != a.n || a.nranks != 1 || a.timeline_iters != 0) {
-    gadmm_set_error("persistent graph Q kernel: one GPU, every worker local");
-    return -1;
-  }
-  if (a.lag < 1 || a.ring <= a.lag + 1 || a.start_iter < 1 || a.start_iter + a.max_iter + a.lag >= (1 << 20)) {
-    gadmm_set_error("persistent graph Q kernel: ring must exceed lag + 1, iteration tags are limited to 2^20");
-    return -1;
-  }
-  if (v.shm > 65536) {
-    gadmm_set_error("persistent graph Q kernel: max_degree=%d needs %zu bytes of LDS staging, 65536 fit", a.max_degree,
-                    v.shm);
-    return -2;
-  }
+  if (const int rc = graph_q_entry_check(qa, v, "persistent graph Q kernel")) return rc;
   const int blocks = a.n + 1;
   const long cap = gadmm_resident_capacity(v.fn, 64, v.shm);
   if (blocks > cap) {  // every workgroup must be resident together (they spin on each other)
@@ -392,6 +435,56 @@ int gadmm_graph_persistent_q_launch(const GraphQArgs* args, hipStream_t st) {
   GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.g.xcd > 0 ? 8 * blocks : blocks), dim3(64), kargs, v.shm, st));
   GADMM_CHECK(hipGetLastError());
   return 0;
+}
+
+// Solves one launch of graph_persistent_q_sweep_kernel can run side by side (one per XCD).
+int gadmm_graph_persistent_q_sweep_capacity() { return GRAPH_Q_SWEEP_CAPACITY; }
+
+// nb <= 8 independent Q-GGADMM solves in ONE launch, as gadmm_graph_persistent_sweep_launch: one register
+// class, every entry passes the single launch's checks, no two entries share a written buffer (the graph
+// sweep's, plus the message table and the true iterates). -1 / -2 as there.
+int gadmm_graph_persistent_q_sweep_launch(const GraphQArgs* batch, int nb, GraphQArgs* host_stage,
+                                          GraphQArgs* dev_stage, hipStream_t st) {
+  const char* name = "persistent graph Q sweep";
+  if (!gadmm_sweep_batch_ok(name, batch, nb, GRAPH_Q_SWEEP_CAPACITY, host_stage, dev_stage)) return -1;
+  int blocks[8], dk[8];
+  size_t shm = 0;
+  for (int j = 0; j < nb; ++j) {
+    const GraphQArgs& qa = batch[j];
+    const GraphArgs& a = qa.g;
+    char who[48];
+    snprintf(who, sizeof(who), "%s: solve %d", name, j);
+    if ((a.d <= 52) != (batch[0].g.d <= 52)) {
+      gadmm_set_error("%s: solves of different register classes (d = %d and %d; d <= 52 or 53..64)", name,
+                      batch[0].g.d, a.d);
+      return -1;
+    }
+    const GQVariant v = pick_graph_q_variant(qa);
+    if (const int rc = graph_q_entry_check(qa, v, who)) return rc;
+    if (!a.xchk) {
+      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
+      return -1;
+    }
+    blocks[j] = a.n + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i) {
+      const GraphQArgs& o = batch[i];
+      if (gadmm_graph_sweep_shares(a, o.g) || o.qg == qa.qg || (qa.q_true && o.q_true == qa.q_true)) {
+        gadmm_set_error("%s: solves %d and %d share a buffer that both write", name, i, j);
+        return -1;
+      }
+    }
+    dk[j] = v.dk;
+    if (v.shm > shm) shm = v.shm;
+  }
+  unsigned classes = gadmm_graph_sweep_classes(dk, nb);
+  const void* fn = batch[0].g.d <= 52 ? (const void*)graph_persistent_q_sweep_kernel<13>
+                                      : (const void*)graph_persistent_q_sweep_kernel<16>;
+  return gadmm_sweep_launch_as<GraphQArgs>({fn, 64, shm, name, false}, batch, nb, blocks, host_stage, dev_stage, st,
+                                           &classes);
 }
 
 }  // extern "C"

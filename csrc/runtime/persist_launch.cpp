@@ -126,13 +126,29 @@ bool gadmm_sweep_shares(const PersistArgs& a, const PersistArgs& o) {
          o.decg == a.decg || o.xchk == a.xchk || (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres);
 }
 
-int gadmm_sweep_launch(const SweepLaunch& l, const PersistArgs* batch, int nb, const int* blocks,
-                       PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st) {
+bool gadmm_graph_sweep_shares(const GraphArgs& a, const GraphArgs& o) {
+  return o.ctl == a.ctl || o.trace == a.trace || o.theta == a.theta || o.mu == a.mu || (a.thg && o.thg == a.thg) ||
+         o.objg == a.objg || o.decg == a.decg || o.dec_push == a.dec_push || o.xchk == a.xchk ||
+         (a.tstamp && o.tstamp == a.tstamp) || (a.rres && o.rres == a.rres);
+}
+
+unsigned gadmm_graph_sweep_classes(const int* dk, int nb) {
+  unsigned c = 0;
+  for (int j = 0; j < nb; ++j) {
+    unsigned l = 0;
+    while ((1 << l) < dk[j]) ++l;
+    c |= l << (4 * j);
+  }
+  return c;
+}
+
+int gadmm_sweep_residency(const SweepLaunch& l, int nb, const int* blocks, int* max_blocks_out) {
   int max_blocks = 0, sum_blocks = 0;
   for (int j = 0; j < nb; ++j) {
     sum_blocks += blocks[j];
     if (blocks[j] > max_blocks) max_blocks = blocks[j];
   }
+  *max_blocks_out = max_blocks;
   // every workgroup of every solve must be resident together, and a solve's own on the one XCD that
   // its 8-strided blocks are dealt to
   const long cap = gadmm_resident_capacity(l.fn, l.threads, l.shm);
@@ -147,23 +163,17 @@ int gadmm_sweep_launch(const SweepLaunch& l, const PersistArgs* batch, int nb, c
       return -2;
     }
   if (l.shm > 65536) GADMM_CHECK(hipFuncSetAttribute(l.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.shm));
-  int dbg = 0, xenv = -1;
-  if (const char* e = getenv("GADMM_BLK_DBG")) dbg = atoi(e);
-  if (const char* e = getenv("GADMM_XCD")) xenv = atoi(e);
-  for (int j = 0; j < nb; ++j) {
-    PersistArgs& ka = host_stage[j];
-    ka = batch[j];
-    if (l.dbg) ka.dbg = dbg;
-    // the 8-strided layout is inherent to a sweep: 0 (no packing) maps to 1 (packed, sc1 stores)
-    const int x = xenv >= 0 ? xenv : ka.xcd;
-    ka.xcd = x >= 2 ? 2 : 1;
-    // fresh placement-check tag per slot and per launch (a continuation re-runs the check): no memset of xchk
-    ka.xtag = (int)gadmm_next_xtag();
-  }
-  GADMM_CHECK(hipMemcpyAsync(dev_stage, host_stage, (size_t)nb * sizeof(PersistArgs), hipMemcpyHostToDevice, st));
-  const PersistArgs* dbatch = dev_stage;
-  void* kargs[] = {&dbatch, &nb};
-  GADMM_CHECK(hipLaunchKernel(l.fn, dim3(8 * max_blocks), dim3(l.threads), kargs, l.shm, st));
-  GADMM_CHECK(hipGetLastError());
   return 0;
+}
+
+void gadmm_sweep_env(int* dbg, int* xenv) {
+  *dbg = 0;
+  *xenv = -1;
+  if (const char* e = getenv("GADMM_BLK_DBG")) *dbg = atoi(e);
+  if (const char* e = getenv("GADMM_XCD")) *xenv = atoi(e);
+}
+
+int gadmm_sweep_launch(const SweepLaunch& l, const PersistArgs* batch, int nb, const int* blocks,
+                       PersistArgs* host_stage, PersistArgs* dev_stage, hipStream_t st) {
+  return gadmm_sweep_launch_as<PersistArgs>(l, batch, nb, blocks, host_stage, dev_stage, st);
 }

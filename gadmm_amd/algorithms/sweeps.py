@@ -4,8 +4,9 @@ XCD (engine/sweep_base.py and the three engines on it); anywhere else the loop o
   ``chain_admm_sweep``            static-chain GADMM at several rho (engine/chain_sweep.py)
   ``quantized_group_admm_sweep``  Q-GADMM / CQ-GADMM under several (rho, bits, seed[, tau0, xi]) (engine/quant_sweep.py)
   ``dynamic_group_admm_sweep``    D-GADMM at several coherences (engine/dyn_sweep.py)
+  ``graph_admm_sweep``            GGADMM / Q-GGADMM over several (graph, rho[, bits, seed]) (engine/graph_sweep.py)
 
-The three are one driver (``_run_sweep``: the gates that send a call to the loop, the groups of one
+They are one driver (``_run_sweep``: the gates that send a call to the loop, the groups of one
 launch, the fall-back when a launch is refused) around what each sweep knows: its gates and their
 reasons, how a group's engine is built and run, and what a member's ``RunResult`` carries on top of the
 common part (``_member_result``). ``algorithms.gadmm``, where they used to live, re-exports them.
@@ -126,9 +127,11 @@ def _member_result(name: str, sw, slot: int, width: int, iters: int, done: int, 
                             "sweep_kernel": sw.last_kernel, "sweep_slot": slot})
 
 
-def _one_launch_results(name: str, sw, t_begin: float, obj0: float, n_total: int, primal: bool = True) -> List[RunResult]:
-    """Run ``sw`` (one launch) and return its members' results; ``t_begin``: when the group's set-up began."""
-    runs = sw.run()
+def _one_launch_results(name: str, sw, t_begin: float, obj0: float, n_total: int, primal: bool = True,
+                        **run_kw) -> List[RunResult]:
+    """Run ``sw`` (one launch, ``sw.run(**run_kw)``) and return its members' results; ``t_begin``: when the
+    group's set-up began."""
+    runs = sw.run(**run_kw)
     wall = time.perf_counter() - t_begin
     ticks = sw.stop_ticks(runs)
     last = max(ticks)
@@ -266,6 +269,82 @@ def quantized_group_admm_sweep(model, configs: Sequence, obj0: float, tol: float
              (sorted(local_ids) != list(range(n_total)), "not every worker local"), (model.d > 64, "d > 64")]
     return _run_sweep([(cfg, cen, t) for (cfg, cen), t in zip(parsed, tols)], sequential_one, gates, capacity,
                       run_group, "%s sweep native-Q N=%d K=%d" % (name, n_total, len(parsed)))
+
+
+def graph_admm_sweep(model, members: Sequence, obj0: float, tol: float, max_iter: int, *,
+                     tols: Optional[Sequence[float]] = None, backend: str = "auto", name: str = "GGADMM",
+                     engine_opts: Optional[dict] = None, comm: Optional[Comm] = None) -> List[RunResult]:
+    """GGADMM / Q-GGADMM of ``model`` under every member of ``members`` -- ``(graph, rho)`` or ``(graph, rho,
+    bits, seed)`` -- one ``RunResult`` per member, in the order given, equal to ``[graph_admm(model, graph,
+    rho, ...[, quantize=(bits, seed)]) ...]`` in iterations, objective trace, ``comm_units``, primal residual
+    and ``converged``, for a quantized member also in ``extra['theta_true']`` and the bit accounting. On one
+    HIP device the solves run side by side, up to eight per kernel launch, one per XCD
+    (engine/graph_sweep.py; more members run in groups), each to its own stop: ``tols`` gives one tolerance
+    per member (default ``tol`` for all). A launch is all unquantized or all quantized, so a mixed list is
+    split by kind (the results keep the input order). Each result then carries the single native solve's
+    fields plus ``extra['sweep'] = {width, slot, kernel, placed, wall_ms_launch}`` and ``extra['kernel']``
+    (the sweep's), and its ``wall_s`` is that solve's OWN time (as ``chain_admm_sweep``: the wall clock of
+    its launch less the device time between its stop decision and the last member's). ``extra['state']``
+    is not produced. Anywhere else -- CPU tensors, ``backend='torch'``, several ranks, a non-linear model,
+    d > 64, a member graph whose ``n`` is not the model's, no native library, or a launcher that refuses
+    the group (``ResidencyError``: a graph of more than 31 workers does not fit one XCD's slot; a shape it
+    does not take) -- it IS that loop, and every result records ``extra['sweep_fallback'] = reason``. A
+    hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``, ``residual``, ``timeout_s`` as in ``graph_admm``."""
+    from ..engine.graph_sweep import parse_member  # (no device code is touched by the import)
+    parsed = [parse_member(m) for m in members]
+    opts = dict(engine_opts or {})
+    tols = [float(tol)] * len(parsed) if tols is None else [float(t) for t in tols]
+    if len(tols) != len(parsed):
+        raise ValueError("tols: one per member")
+    xcd = int(opts.get("xcd", 2))
+    residual = bool(opts.get("residual", True))
+    n_model = int(model.n_local)
+
+    def sequential_one(mem):
+        from .ggadmm import graph_admm
+        (g, rho, quant), t = mem
+        return graph_admm(model, g, rho, obj0, t, max_iter, backend=backend, name=name, engine_opts=engine_opts,
+                          comm=comm, quantize=quant)
+
+    def run_group(group, idx):
+        from ..engine.graph_sweep import GraphSweepEngine
+        from . import quantize as Q
+        t_begin = time.perf_counter()
+        g_mems = [g[0] for g in group]
+        g_tols = [g[1] for g in group]
+        key = ("graph-sweep", tuple((g.key(), rho) + (q or ()) for g, rho, q in g_mems), int(max_iter), xcd, residual)
+        sw = _group_engine(model, key, opts, lambda: GraphSweepEngine.build(
+            model.X, model.y, [(g, rho) + (q or ()) for g, rho, q in g_mems], obj0=obj0, tols=g_tols,
+            max_iters=max_iter, precomputed=(model.A, model.b, model.yy), xcd=xcd, residual=residual), (obj0, g_tols))
+        out = _one_launch_results(name, sw, t_begin, obj0, n_model, timeout_s=float(opts.get("timeout_s", 20.0)))
+        for res, m, (g, rho, q) in zip(out, sw.members, g_mems):
+            res.extra.update(kernel=sw.last_kernel, placed=res.extra["sweep"]["placed"], graph=g.describe(),
+                             deliveries=res.iters * 2 * len(g.edges))
+            if q is not None:
+                G = Q.granules_per_row(model.d, q[0])
+                _quant_accounting(res, q[0], q[1], g.n, model.d)
+                res.extra.update(transmissions=res.iters * g.n, q_granules=G, q_wire_bytes=res.iters * g.n * G * 16,
+                                 theta_true=m.theta_true)
+        return out
+
+    def capacity():
+        from ..engine.graph_sweep import graph_sweep_capacity
+        return graph_sweep_capacity()
+
+    gates = [(backend == "torch", "torch backend"), (model.device.type != "cuda", "cpu tensors"),
+             (comm is not None and comm.nranks > 1, "several ranks"),
+             (getattr(model, "kind", None) != "linear", "not the linear closed-form model"), (model.d > 64, "d > 64"),
+             (any(g.n != n_model for g, _, _ in parsed), "a member graph's n differs from the model's")]
+    out: List[Optional[RunResult]] = [None] * len(parsed)
+    for quantized in (False, True):  # one launch is homogeneous: the plain members, then the quantized ones
+        idx = [i for i, (_, _, q) in enumerate(parsed) if (q is not None) == quantized]
+        if not idx:
+            continue
+        res = _run_sweep([(parsed[i], tols[i]) for i in idx], sequential_one, gates, capacity, run_group,
+                         "%s sweep native-graph%s N=%d K=%d" % (name, "-Q" if quantized else "", n_model, len(idx)))
+        for i, r in zip(idx, res):
+            out[i] = r
+    return out
 
 
 def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, coherences, seeds, kind="findPath2",

@@ -31,15 +31,22 @@ class NativeGraphEngine:
     LAG = 4
     MAX_D = 64
 
+    model = "linear"         # what a sweep (engine/sweep_base.py) asks of a member: a one-GPU linear solve
+    nranks = 1
+    obj_mode_name = "exact"  # the objective the monitor sums is the true one
+
     def __init__(self, X: torch.Tensor, y: torch.Tensor, graph, rho: float, obj0: float, tol: float, max_iter: int,
-                 precomputed=None, xcd: int = 2, residual: bool = True, quant=None):
+                 precomputed=None, xcd: int = 2, residual: bool = True, quant=None, stream=None, inverses=None):
         """``X`` (n, m, d), ``y`` (n, m): every worker's shard, in worker order (``graph.n`` of them).
         ``precomputed``: ``(A, b, yy)`` of those shards (the Gram is then not recomputed). ``xcd``: as
         ``NativeChainEngine`` (0 default grid, 1 packed onto one XCD, 2 also L2-resident plain stores
         once the kernel has verified the placement; speed only). ``residual``: the tails also emit the
         K4 primal residual rows (``rres``, ``primal_residual``). ``quant``: ``(bits, seed)``, ``bits`` in
         {4, 8, 16} -- Q-GGADMM: ``theta`` receives the public models, ``theta_true`` the true iterates,
-        ``q_msg`` shows every worker's last message, the K4 rows are taken on the public models."""
+        ``q_msg`` shows every worker's last message, the K4 rows are taken on the public models.
+        ``stream`` / ``inverses``: for a sweep's builder (engine/graph_sweep.py) -- the stream the engine
+        lives on (default: its own) and a contiguous ``(n, d, d)`` table of this member's inverses, each
+        worker's at ``rho`` times its own degree, computed by the caller (default: computed here)."""
         if not X.is_cuda:
             raise ValueError("NativeGraphEngine runs on a HIP device; use graph_admm(backend='torch') on CPU")
         self.lib = native.require()
@@ -56,8 +63,9 @@ class NativeGraphEngine:
             raise ValueError("the graph has %d workers, the data %d shards" % (graph.n, self.n))
         self.rho, self.obj0, self.tol, self.max_iter = float(rho), float(obj0), float(tol), int(max_iter)
         self.xcd = int(xcd)
+        self.n_local = self.n_total = self.n
         self.ring = self.LAG + 4
-        self.stream = torch.cuda.Stream(self.device)
+        self.stream = stream if stream is not None else torch.cuda.Stream(self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         dev, f64, n, d, mi = self.device, torch.float64, self.n, self.d, self.max_iter
         ptr, idx = graph.csr()
@@ -67,8 +75,13 @@ class NativeGraphEngine:
             else:
                 self.A, self.b, self.yy = gram(X.to(f64), y.to(f64))
             # every worker's inverse at its OWN degree: one variant per worker
-            self._shifts = torch.tensor([[self.rho * g] for g in graph.degree], dtype=f64, device=dev)
-            self.Minv = spd_inverse(self.A, self._shifts)
+            if inverses is not None:
+                if tuple(inverses.shape) != (n, d, d) or not inverses.is_contiguous():
+                    raise ValueError("inverses: a contiguous (n, d, d) table")
+                self._shifts, self.Minv = None, inverses
+            else:
+                self._shifts = torch.tensor([[self.rho * g] for g in graph.degree], dtype=f64, device=dev)
+                self.Minv = spd_inverse(self.A, self._shifts)
             self.theta = torch.zeros((n, d), dtype=f64, device=dev)
             self.mu = torch.zeros((n, d), dtype=f64, device=dev)
             # read-back block, as NativeChainEngine: [ctl (8 x i32) | t0stamp | pad x 3 | trace | tstamp]
@@ -183,16 +196,11 @@ class NativeGraphEngine:
         """One launch: the whole solve from the state ``reset()`` left. Raises ``ResidencyError`` when the
         launcher refuses (nothing was launched) and ``HandoffTimeout`` when a hand-off passed its
         deadline (done == 4)."""
-        why = self.refusal()
-        if why is not None and not why.startswith("ResidencyError"):
-            raise RuntimeError("persistent graph kernel not eligible: %s" % why)
-        self._epoch = self._epoch % 4095 + 1  # fresh tag salt: the tables of the last solve never match
+        a = self.prepare(timeout_s)
         if self.quant is not None:
-            a = self._q_args(timeout_s)
             self.last_kernel = "persistent-graph-Q(deg<=%d,b=%d)" % (self._class_bound(), self.quant[0])
             launch = self.lib.gadmm_graph_persistent_q_launch
         else:
-            a = self._args(timeout_s)
             self.last_kernel = "persistent-graph(deg<=%d)" % self._class_bound()
             launch = self.lib.gadmm_graph_persistent_launch
         t0 = time.perf_counter()
@@ -200,7 +208,24 @@ class NativeGraphEngine:
         if rc == -2:
             raise ResidencyError(self.lib.gadmm_last_error().decode())
         native.check(rc, "graph_persistent_launch")
-        # control block (and the short traces) come back behind the kernel through readback.hip's path
+        fetch = self._queue_readback(fetch_trace)
+        self.stream.synchronize()
+        return self.finish((time.perf_counter() - t0) * 1e3, fetch, "persistent graph kernel")
+
+    def prepare(self, timeout_s: float = 20.0):
+        """The arguments of the next launch (``GraphArgs``, or ``GraphQArgs`` with ``quant``) under a fresh
+        tag salt: the granule tables of the last solve never match, so they are never re-zeroed.
+        ``RuntimeError``: the kernel does not take the shape (a residency refusal is the launcher's)."""
+        why = self.refusal()
+        if why is not None and not why.startswith("ResidencyError"):
+            raise RuntimeError("persistent graph kernel not eligible: %s" % why)
+        self._epoch = self._epoch % 4095 + 1
+        return self._q_args(timeout_s) if self.quant is not None else self._args(timeout_s)
+
+    def _queue_readback(self, fetch_trace: bool) -> bool:
+        """Queue the read-back of the control block (with ``fetch_trace`` and a short trace: of the whole
+        read-back block) behind the launch on the engine's stream, through readback.hip's path; True if
+        the traces come along."""
         nt = self.trace.numel()
         fetch = bool(fetch_trace) and nt <= 16384
         if self._rb_host is None:
@@ -210,15 +235,24 @@ class NativeGraphEngine:
         nb = self._rb.numel() * 8 if fetch else 32
         native.check(self.lib.gadmm_readback_d2h(self._rb_host.data_ptr(), self._rb.data_ptr(), nb,
                                                  self.stream.cuda_stream), "readback")
-        self.stream.synchronize()
-        wall_ms = (time.perf_counter() - t0) * 1e3
+        return fetch
+
+    def finish(self, wall_ms: float, fetch: bool, what: str) -> EngineRun:
+        """The ``EngineRun`` of a launch whose read-back (``_queue_readback``) has completed. A hand-off
+        timeout (done == 4) raises."""
         self._tr_valid = fetch
         c = self._ctl_host.tolist()
         done, conv, nxt = c[1], c[2], c[0]
         self.last_placed = c[6]
         if done == 4:
-            raise HandoffTimeout("persistent graph kernel timed out (hand-off never completed)")
+            raise HandoffTimeout("%s timed out (hand-off never completed)" % what)
         return EngineRun(conv, done, nxt - 1, 1, wall_ms, 0, 0, 0, 0)
+
+    def adopt_stream(self, stream: torch.cuda.Stream):
+        """Move the engine onto ``stream`` (ordered behind everything queued on its old one): its resets
+        and launches then share that stream with the other members of a sweep."""
+        stream.wait_stream(self.stream)
+        self.stream = stream
 
     def _class_bound(self) -> int:
         k, g = self.kernel_class(), self.graph.max_degree

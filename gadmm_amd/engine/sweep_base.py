@@ -1,6 +1,8 @@
-"""What the three sweep engines share: up to eight ``NativeChainEngine`` members on one stream, run side
+"""What the sweep engines share: up to eight ``NativeChainEngine`` members on one stream, run side
 by side in one kernel launch, one solve per XCD (chain_sweep.py: static chains at several rho;
-quant_sweep.py: Q/CQ-GADMM configs; dyn_sweep.py: D-GADMM coherences, in rounds of launches).
+quant_sweep.py: Q/CQ-GADMM configs; dyn_sweep.py: D-GADMM coherences, in rounds of launches;
+graph_sweep.py: GGADMM / Q-GGADMM over graphs, whose members are ``NativeGraphEngine``, which offers the
+same surface: ``model``, ``nranks``, ``n_local`` / ``n_total``, ``adopt_stream``, ``_queue_readback``).
 
 ``SweepEngineBase`` owns the member validation, the stream, the launcher's staging pair, the shared
 Gram and table of inverses of a sweep over the same shards (``_shared``, ``refresh``), the launch call

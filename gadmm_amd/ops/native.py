@@ -280,6 +280,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_graph_persistent_q_class": (c_int, [ctypes.POINTER(GraphQArgs)]),
         "gadmm_graph_persistent_q_capacity": (c_long, [ctypes.POINTER(GraphQArgs)]),
         "gadmm_graph_persistent_q_launch": (c_int, [ctypes.POINTER(GraphQArgs), c_void_p]),
+        "gadmm_graph_persistent_sweep_capacity": (c_int, []),
+        "gadmm_graph_persistent_sweep_launch": (c_int, [ctypes.POINTER(GraphArgs), c_int, c_void_p, c_void_p, c_void_p]),
+        "gadmm_graph_persistent_q_sweep_capacity": (c_int, []),
+        "gadmm_graph_persistent_q_sweep_launch": (c_int, [ctypes.POINTER(GraphQArgs), c_int, c_void_p, c_void_p,
+                                                          c_void_p]),
         "gadmm_sym_pack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "gadmm_sym_packed_doubles": (c_long, [c_int]),
         "gadmm_ipc_box_bytes": (c_long, [c_int, c_int, c_int, c_int]),
