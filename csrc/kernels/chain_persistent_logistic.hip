@@ -31,6 +31,7 @@
 #include "chain_worker.h"
 #include "gadmm_logi.h"
 #include "fast_sigm.h"
+#include "logi_layout.h"
 #include <cstddef>
 #include <stdlib.h>
 
@@ -200,17 +201,8 @@ __global__ void __launch_bounds__(64) chain_persistent_logistic_kernel(PersistAr
 // from z_0 = X x_0 exactly (no drift across solves). The iterate update, break rule, objective and
 // hand-offs are the one-wave kernel's; only s_k differs in rounding (z from the recursion), so traces
 // match the other engines to ~1e-13 instead of bit for bit.
-constexpr int ZR_NT = 128;
-constexpr int ZR_SLOTS = 64;  // s ring depth; the margins wave checks it every ZR_CHK steps
-// (same-box A/B, E3 bench: 8/4 5.34, 16/4 5.34, 16/8 5.17, 32/8 5.11, 64/8 4.93 ms; 128/8 with an early-end
-// check every 8 steps 5.41, 32/16 with one every step 5.43: profiles/r06_logistic)
-constexpr int ZR_CHK = 8;
-
-// s = y / (1 + e^{y z}) on the margins wave's critical path: inv1pexp_fast (fast_sigm.h). Measured 5.64 ->
-// 5.21 ms on E3, one box (profiles/r05_j/r5jf); the default (GADMM_LOGISTIC_FASTSIGM=0: libm exp and
-// the IEEE quotient). The traces stay within 1e-12 of torch.
-__device__ __forceinline__ double zr_sigm(double yv, double z) { return yv * inv1pexp_fast(yv * z); }
-
+// (ZR_NT threads, the ZR_SLOTS-deep s ring checked every ZR_CHK steps, zr_sigm: logi_layout.h, shared with the
+// sweep unit's copy of this loop, logi_body.h)
 template <int T, bool SYS>
 __global__ void __launch_bounds__(ZR_NT) chain_persistent_logistic_zrec_kernel(PersistArgs a, LogiArgs g) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -484,12 +476,7 @@ static const void* logi_variant(const PersistArgs& a, const LogiArgs& g) {
 
 static int logi_threads() { return logi_zrec() ? ZR_NT : 64; }
 
-static size_t logi_shm(const PersistArgs& a) {
-  const size_t mon = (size_t)a.n * 8;
-  const size_t wk = logi_zrec() ? (size_t)(2 * QSTAGE + 128 + ZR_SLOTS * 4 * QX + 64 * 64) * 8 + 32
-                                 : (size_t)QSTAGE * 8;
-  return mon > wk ? mon : wk;
-}
+static size_t logi_shm(const PersistArgs& a) { return logi_lds_bytes(logi_zrec(), a.n); }
 
 extern "C" {
 

@@ -1138,4 +1138,4 @@ def static_group_admm(model, rho, obj0, acc, max_iter, coherence, cost_static_ma
 # The sweeps lived here and callers name them here: algorithms/sweeps.py, which builds on the solves
 # above, so it is imported once they exist.
 from .sweeps import (_sweep_member, chain_admm_sweep, dynamic_group_admm_sweep,  # noqa: E402,F401
-                     quantized_group_admm_sweep, run_in_groups, sweep_groups)
+                     logistic_admm_sweep, quantized_group_admm_sweep, run_in_groups, sweep_groups)

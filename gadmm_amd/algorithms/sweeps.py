@@ -5,6 +5,7 @@ XCD (engine/sweep_base.py and the three engines on it); anywhere else the loop o
   ``quantized_group_admm_sweep``  Q-GADMM / CQ-GADMM under several (rho, bits, seed[, tau0, xi]) (engine/quant_sweep.py)
   ``dynamic_group_admm_sweep``    D-GADMM at several coherences (engine/dyn_sweep.py)
   ``graph_admm_sweep``            GGADMM / Q-GGADMM over several (graph, rho[, bits, seed]) (engine/graph_sweep.py)
+  ``logistic_admm_sweep``         logistic inner-GD GADMM under several rho / (rho, max_inner, inner_tol) (engine/logistic_sweep.py)
 
 They are one driver (``_run_sweep``: the gates that send a call to the loop, the groups of one
 launch, the fall-back when a launch is refused) around what each sweep knows: its gates and their
@@ -190,6 +191,82 @@ def chain_admm_sweep(model, local_ids: Sequence[int], n_total: int, rhos: Sequen
              (getenv("GADMM_CHECK_EXCHANGE", "0") == "1", "exchange checker")]
     return _run_sweep(list(zip(rhos, tols)), sequential_one, gates, capacity, run_group,
                       "%s sweep native N=%d K=%d" % (name, n_total, len(rhos)))
+
+
+def _logistic_member(mem, max_inner: int, inner_tol: float) -> tuple:
+    """A logistic sweep member ``rho`` or ``(rho, max_inner, inner_tol)`` as ``(rho, max_inner, inner_tol)``."""
+    if isinstance(mem, (int, float)):
+        return float(mem), int(max_inner), float(inner_tol)
+    mem = tuple(mem)
+    if len(mem) != 3:
+        raise ValueError("a logistic sweep member is rho or (rho, max_inner, inner_tol), got %r" % (mem,))
+    rho, mi, it = float(mem[0]), int(mem[1]), float(mem[2])
+    if mi < 1 or mi != mem[1] or it < 0.0:
+        raise ValueError("a logistic sweep member needs an integer max_inner >= 1 and inner_tol >= 0, got %r" % (mem,))
+    return rho, mi, it
+
+
+def logistic_admm_sweep(model, local_ids: Sequence[int], n_total: int, members: Sequence, obj0: float, tol: float,
+                        max_iter: int, *, tols: Optional[Sequence[float]] = None,
+                        placement: Optional[Placement] = None, backend: str = "auto", name: str = "GADMM-logistic",
+                        engine_opts: Optional[dict] = None, comm: Optional[Comm] = None, step: float = 1.0,
+                        max_inner: int = 100, inner_tol: float = 1e-4) -> List[RunResult]:
+    """The static-chain logistic GADMM solve with the inexact inner-GD local solver under every member of
+    ``members`` -- ``rho``, or ``(rho, max_inner, inner_tol)`` -- one ``RunResult`` per member, in the order
+    given, equal to ``[chain_admm(model, ..., rho, ..., local_solver="gd", step=step, max_inner=..,
+    inner_tol=..) ...]`` in iterations, objective trace and ``converged``. ``step``, and ``max_inner`` /
+    ``inner_tol`` of a member given as ``rho`` alone, are ``chain_admm``'s arguments with its defaults;
+    ``lam`` is the model's, as in the single solve. On one HIP device the solves run side by side, up to
+    eight per kernel launch, one per XCD (engine/logistic_sweep.py; more members run in groups), each to
+    its own stop: ``tols`` gives one tolerance per member (default ``tol`` for all). Each result then
+    carries ``extra['sweep'] = {width, slot, kernel, placed, wall_ms_launch}``, and its ``wall_s`` is that
+    solve's OWN time (as ``chain_admm_sweep``). ``extra['state']`` is not produced. Anywhere else -- CPU
+    tensors, ``backend='torch'``, several ranks, the exchange checker, no native library, not a logistic
+    model, not every worker local, max(d, m) > 64, or a launcher that refuses the group (``ResidencyError``:
+    the device cannot hold its workgroups; a shape it does not take) -- it IS that loop, and every result
+    records ``extra['sweep_fallback'] = reason``. A hand-off timeout propagates. ``engine_opts``:
+    ``cache``, ``xcd``, ``residual`` as in ``chain_admm``."""
+    parsed = [_logistic_member(m, max_inner, inner_tol) for m in members]
+    opts = dict(engine_opts or {})
+    local_ids = [int(w) for w in local_ids]
+    tols = [float(tol)] * len(parsed) if tols is None else [float(t) for t in tols]
+    if len(tols) != len(parsed):
+        raise ValueError("tols: one per member")
+    xcd = int(opts.get("xcd", 2))
+    residual = bool(opts.get("residual", True))
+    lam = float(getattr(model, "lam", 0.0))
+
+    def sequential_one(mem):
+        (rho, mi, it), t = mem
+        return chain_admm(model, local_ids, n_total, rho, obj0, t, max_iter, comm=comm, placement=placement,
+                          local_solver="gd", step=step, max_inner=mi, inner_tol=it, backend=backend, name=name,
+                          engine_opts=engine_opts)
+
+    def run_group(group, idx):
+        from ..engine.logistic_sweep import LogisticSweepEngine
+        t_begin = time.perf_counter()
+        g_mems, g_tols = [g[0] for g in group], [g[1] for g in group]
+        key = ("logistic-sweep", n_total, tuple(local_ids), tuple(g_mems), float(step), lam, int(max_iter), xcd, residual)
+        sw = _group_engine(model, key, opts, lambda: LogisticSweepEngine.build(
+            model.X, model.y, local_ids, n_total, [(rho, step, mi, it) for rho, mi, it in g_mems], obj0=obj0,
+            tols=g_tols, max_iters=max_iter, lam=lam, placement=placement, xcd=xcd, residual=residual), (obj0, g_tols))
+        out = _one_launch_results(name, sw, t_begin, obj0, n_total, primal=residual)
+        for res in out:
+            res.extra.update(solver="gd", kernel=sw.last_kernel, placed=res.extra["sweep"]["placed"])
+        return out
+
+    def capacity():
+        from ..engine.logistic_sweep import logistic_sweep_capacity
+        return logistic_sweep_capacity()
+
+    gates = [(model.device.type != "cuda", "cpu tensors"), (backend == "torch", "torch backend"),
+             (comm is not None and comm.nranks > 1, "several ranks"),
+             (getenv("GADMM_CHECK_EXCHANGE", "0") == "1", "exchange checker"),
+             (getattr(model, "kind", None) != "logistic", "not a logistic model with the inner-GD solver"),
+             (sorted(local_ids) != list(range(n_total)), "not every worker local"),
+             (max(model.d, getattr(model, "m", 0)) > 64, "max(d, m) > 64")]
+    return _run_sweep(list(zip(parsed, tols)), sequential_one, gates, capacity, run_group,
+                      "%s sweep native-logistic N=%d K=%d" % (name, n_total, len(parsed)))
 
 
 def _sweep_member(cfg):

@@ -36,11 +36,18 @@ class SweepEngineBase:
     _CLASSES = "d <= 32 and 33..52"
     _SOLVES = "closed-form solves"  # what a member is, in the refusal of one that is not
     _WHAT = "blocked sweep kernel"  # prefix of a hand-off timeout's text
+    _MODEL = "linear"  # the members' model
+    _ARGS = native.PersistArgs  # a slot's argument struct: the staging pair holds capacity() of them
 
     @staticmethod
     def capacity() -> int:
         """Solves one launch takes."""
         raise NotImplementedError
+
+    @staticmethod
+    def _size(m) -> int:
+        """What the kernel's register class is picked by (``_SPLIT``)."""
+        return m.d
 
     def _member_defect(self, m: NativeChainEngine) -> Optional[str]:
         """What else keeps ``m`` out of this sweep (the text after ``member j``), or None."""
@@ -60,11 +67,11 @@ class SweepEngineBase:
             raise ValueError("the members of a sweep live on one device")
         for j, m in enumerate(members):
             defect = self._member_defect(m)
-            if defect is None and (m.model != "linear" or m.nranks != 1 or m.n_local != m.n_total):
-                defect = ": one-GPU linear %s only" % self._SOLVES
+            if defect is None and (m.model != self._MODEL or m.nranks != 1 or m.n_local != m.n_total):
+                defect = ": one-GPU %s %s only" % (self._MODEL, self._SOLVES)
             if defect is not None:
                 raise ValueError("member %d%s" % (j, defect))
-        if len({m.d <= self._SPLIT for m in members}) != 1:
+        if len({self._size(m) <= self._SPLIT for m in members}) != 1:
             raise ValueError("members of different register classes (%s) cannot share a launch" % self._CLASSES)
         self.lib = native.require()
         self.device = dev
@@ -73,8 +80,8 @@ class SweepEngineBase:
         for m in members:  # one stream: every member's resets, table copies and zero-fills precede the launch
             if m.stream is not self.stream:
                 m.adopt_stream(self.stream)
-        nbytes = cap * ctypes.sizeof(native.PersistArgs)
-        # the launcher's staging pair: the slots' PersistArgs go up in one async copy ahead of the kernel
+        nbytes = cap * ctypes.sizeof(self._ARGS)
+        # the launcher's staging pair: the slots' arguments go up in one async copy ahead of the kernel
         self._stage_host = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
         self._stage_dev = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         self._shared = None

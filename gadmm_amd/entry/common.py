@@ -313,6 +313,7 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
     a checkpoint. With the preset field ``sweep='concurrent'`` the linear closed-form rho list runs
     side by side in one kernel launch (``chain_admm_sweep``) on a one-GPU session, unless the backend
     is torch or a run must keep its state; each run's summary then names the sweep kernel and its slot.
+    A logistic preset's inner-GD rho list goes the same way through ``logistic_admm_sweep``.
     With ``quant_bits`` set, the same switch sends the Q-GADMM ``quant_bits x rhos`` list through
     ``quantized_group_admm_sweep`` (same run keys and names; where that call is the sequential loop,
     the summaries carry ``sweep_fallback``). With ``censor`` (and ``quant_bits``) every Q run gets a
@@ -333,6 +334,21 @@ def gadmm_sweep(prob: Problem, sess: Session, backend: str = "auto", state_rho: 
             r.algorithm = "GADMM(rho=%g)" % rho
             r.extra.pop("engine_obj", None)  # (the summary carries sweep_kernel / sweep_slot of each run)
             out["GADMM_rho%g" % rho] = attach_modelled_clock(r, prob.model, rho, sess)
+    # a logistic preset (its local solver is the inexact inner GD): the rho list side by side through logistic_admm_sweep
+    logi_concurrent = (cfg.sweep == "concurrent" and cfg.model == "logistic" and sess.world == 1
+                       and sess.device.type == "cuda" and backend != "torch" and state_rho is None and len(cfg.rhos) > 0)
+    if logi_concurrent:
+        from ..algorithms import logistic_admm_sweep
+
+        with roctx_range("gadmm_sweep logistic concurrent"):
+            rs = logistic_admm_sweep(prob.model, prob.local_ids, prob.n_total, list(cfg.rhos), prob.obj0, cfg.acc,
+                                     cfg.gadmm_iters, placement=prob.placement, backend=backend, comm=sess.comm,
+                                     step=cfg.gd_step, max_inner=cfg.max_inner)
+        for rho, r in zip(cfg.rhos, rs):
+            r.algorithm = "GADMM(rho=%g)" % rho
+            r.extra.pop("engine_obj", None)
+            out["GADMM_rho%g" % rho] = attach_modelled_clock(r, prob.model, rho, sess)
+        concurrent = True
     for rho in ([] if concurrent else cfg.rhos):
         with roctx_range("gadmm_sweep rho=%g" % rho):
             r = gadmm_solve(prob, sess, rho, cfg.acc, cfg.gadmm_iters, backend, name="GADMM(rho=%g)" % rho,

@@ -127,6 +127,26 @@ class LogiArgs(ctypes.Structure):
                 ("scratch", c_void_p)]
 
 
+class LogiSweepArgs(ctypes.Structure):
+    """Mirror of LogiSweepArgs in csrc/include/gadmm_logi.h: one slot of the inner-GD logistic sweep launch."""
+    _fields_ = [("p", PersistArgs), ("g", LogiArgs)]
+
+
+def logi_sweep_abi_expected() -> list:
+    """What ``gadmm_logi_sweep_abi_layout`` must report for the ``LogiSweepArgs`` mirror above."""
+    S = LogiSweepArgs
+    return [ctypes.sizeof(S), S.p.offset, S.g.offset, ctypes.sizeof(PersistArgs), ctypes.sizeof(LogiArgs)]
+
+
+def check_logi_sweep_abi(lib) -> None:
+    """ABI self-check of ``LogiSweepArgs`` against the built library (raises on a mismatch: a stale build)."""
+    buf = (c_longlong * 8)()
+    k = lib.gadmm_logi_sweep_abi_layout(buf, 8)
+    if list(buf[:k]) != logi_sweep_abi_expected():
+        raise RuntimeError("LogiSweepArgs layout mismatch between gadmm_amd/ops/native.py and the native library: "
+                           "%s vs %s" % (list(buf[:k]), logi_sweep_abi_expected()))
+
+
 class StarArgs(ctypes.Structure):
     """Mirror of csrc/include/gadmm_star.h (persistent star ADMM)."""
     _fields_ = [
@@ -260,6 +280,10 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_chain_persistent_logistic_launch": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs),
                                                            c_void_p]),
         "gadmm_logi_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_logi_sweep_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_chain_persistent_logistic_sweep_capacity": (c_int, []),
+        "gadmm_chain_persistent_logistic_sweep_launch": (c_int, [ctypes.POINTER(LogiSweepArgs), c_int, c_void_p,
+                                                                 c_void_p, c_void_p]),
         "gadmm_chain_persistent_newton_capacity": (c_long, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
         "gadmm_chain_persistent_newton_kernel": (c_int, [ctypes.POINTER(PersistArgs), ctypes.POINTER(LogiArgs)]),
         "gadmm_newton_rec_scratch_doubles": (c_long, []),
