@@ -92,23 +92,51 @@ def run_bytes(comm, snap) -> int:
     return int(d["bytes_sent"] + d["coll_bytes"])
 
 
+def control_reduce(comm, values, op: str = "sum") -> list:
+    """``values`` all-reduced (``op``: sum or max) as one small float64 CPU tensor over the ranks' control
+    group, back as Python floats."""
+    import torch
+    import torch.distributed as dist
+
+    t = torch.tensor([float(v) for v in values], dtype=torch.float64)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM,
+                    group=getattr(comm, "control_group", None))
+    return t.tolist()
+
+
 def total_bytes(comm, snap=None) -> int:
     """Algorithm bytes summed over all ranks (one scalar all-reduce, outside any timed loop)."""
-    import torch
-
     b = run_bytes(comm, snap) if snap is not None else int(comm.stats.bytes_sent) + int(comm.stats.coll_bytes)
     if comm.nranks <= 1:
         return b
-    t = torch.tensor([float(b)], dtype=torch.float64)
     if getattr(comm, "backend", "").startswith("torch"):
+        import torch
         import torch.distributed as dist
 
+        t = torch.tensor([float(b)], dtype=torch.float64)
         dist.all_reduce(t, group=comm.group)
-    else:
-        import torch.distributed as dist
+        return int(t.item())
+    return int(control_reduce(comm, [b])[0])
 
-        dist.all_reduce(t, group=getattr(comm, "control_group", None))
-    return int(t.item())
+
+def cached_engine(model, key: tuple, build, targets: tuple, cache: bool = True, hit=None):
+    """``(engine, fresh)``: the engine cached under ``key`` in ``model._chain_engines`` -- after
+    ``hit(engine)``, if given, with new ``set_targets(*targets)`` -- or ``build()``, cached unless ``cache``
+    is off. One engine per (model, configuration): repeated solves (rho sweeps, benchmarks, D-GADMM
+    re-runs) reuse its device buffers, cached inverses and captured graph."""
+    engines = getattr(model, "_chain_engines", None)
+    eng = engines.get(key) if engines is not None else None
+    if eng is not None:
+        if hit is not None:
+            hit(eng)
+        eng.set_targets(*targets)
+        return eng, False
+    eng = build()
+    if cache:
+        if engines is None:
+            engines = model._chain_engines = {}
+        engines[key] = eng
+    return eng, True
 
 
 def global_objective_and_residual(comm, f_local, r_local, local_ids, n_total: int):

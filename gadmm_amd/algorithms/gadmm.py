@@ -24,14 +24,16 @@ Many solves side by side in one launch (``chain_admm_sweep`` and its kin): algor
 from __future__ import annotations
 
 import time
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from ..parallel.comm import Comm, LocalComm
-from ..parallel.topology import rechain_iterations, PathSchedule, Placement, chain_plan
-from .base import global_objective_and_residual, RunResult, Stopper, total_bytes, global_objective, run_bytes
+from ..engine.epoch_chunks import MAX_EPOCHS, EpochCursor, rechains as _rechains
+from ..parallel.topology import PathSchedule, Placement, chain_plan
+from .base import (global_objective_and_residual, RunResult, Stopper, cached_engine, control_reduce, total_bytes,
+                   run_bytes)
 from ..utils import timing as _timing
 from ..utils.timing import roctx_range
 from ..utils.env import getenv
@@ -405,19 +407,10 @@ def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter
     block = int(opts.get("block", 32))
     key = ("quant", n_total, tuple(map(int, local_ids)), float(rho), int(max_iter), block, bits, seed,
            int(opts.get("xcd", 2)), censor)
-    cache = getattr(model, "_chain_engines", None)
-    eng = cache.get(key) if cache is not None else None
-    if eng is None:
-        eng = NativeChainEngine(model.X, model.y, local_ids, n_total, "linear", rho=rho, obj0=obj0, tol=tol,
-                                max_iter=max_iter, block=block, precomputed=(model.A, model.b, model.yy),
-                                xcd=int(opts.get("xcd", 2)), quant=(bits, seed), censor=censor)
-        if opts.get("cache", True):
-            if cache is None:
-                cache = {}
-                model._chain_engines = cache
-            cache[key] = eng
-    else:
-        eng.set_targets(obj0, tol)
+    eng, _ = cached_engine(model, key, lambda: NativeChainEngine(
+        model.X, model.y, local_ids, n_total, "linear", rho=rho, obj0=obj0, tol=tol, max_iter=max_iter, block=block,
+        precomputed=(model.A, model.b, model.yy), xcd=int(opts.get("xcd", 2)), quant=(bits, seed), censor=censor),
+        (obj0, tol), opts.get("cache", True))
     eng.set_path(schedule.path, placement, 0)
     eng.reset()
     torch.cuda.synchronize(model.device)
@@ -458,21 +451,6 @@ def _chain_admm_native_quant(model, local_ids, n_total, rho, obj0, tol, max_iter
     return res
 
 
-_RECHAINS: dict = {}
-
-
-def _rechains(max_iter: int, coherence) -> np.ndarray:
-    """``rechain_iterations`` memoised per (max_iter, coherence) (read-only array)."""
-    key = (int(max_iter), float(coherence))
-    r = _RECHAINS.get(key)
-    if r is None:
-        r = rechain_iterations(max_iter, coherence)
-        r.setflags(write=False)
-        if len(_RECHAINS) < 64:
-            _RECHAINS[key] = r
-    return r
-
-
 def _max_epochs(eng) -> int:
     """gadmm_chain_blocked_max_epochs (a constant of the build), asked once per engine."""
     v = eng.__dict__.get("_max_epochs")
@@ -481,31 +459,34 @@ def _max_epochs(eng) -> int:
     return v
 
 
-def _dyn_early_draw(eng, schedule, max_iter, fabric, n_total):
-    """``(saved schedule state, epochs drawn, join)`` for the first D-GADMM launch's chains started
-    asynchronously (PathSchedule.prefetch_async), with the chunk / look-ahead rule of the launch loop in
-    ``_chain_admm_native``; None when the dynamic persistent path or the native builder does not
-    apply."""
-    if not eng.dynamic_eligible(fabric):
+def _dyn_cursor(eng, schedule, max_iter, fabric, n_total, epoch_chunk=None, early=False) -> EpochCursor:
+    """The epoch-chunk cursor of a D-GADMM solve of ``schedule`` on ``eng``. ``early``: the first launch's
+    chains start drawing now, on the native host worker (PathSchedule.prefetch_async)."""
+    # the blocked kernel's dynamic mode stages a launch's epoch tables in LDS: at most
+    # gadmm_chain_blocked_max_epochs rows per launch (this chunk + the look-ahead epoch)
+    cap = _max_epochs(eng) - 1 if eng.dynamic_uses_blocked(fabric, schedule.coherence) else 1 << 30
+    return EpochCursor(schedule, max_iter, n_total, eng.__dict__.setdefault("_dyn_epoch_hint", {}), epoch_chunk, cap,
+                       schedule.prefetch_async if early else None)
+
+
+def _dyn_persistent(eng, schedule, max_iter, fabric, opts) -> bool:
+    """Whether a D-GADMM solve runs in persistent launches of epoch chunks (else epoch by epoch)."""
+    return opts.get("persistent", "auto") in (True, "auto") and eng.dynamic_eligible(fabric) \
+        and len(_rechains(max_iter, schedule.coherence)) < MAX_EPOCHS
+
+
+def _dyn_early_draw(model, key, schedule, max_iter, fabric, n_total, opts, state):
+    """D-GADMM on a cached engine: the solve's cursor with the first launch's chains drawing already
+    (geometries from the schedule's RNG here, greedy walks on the native host worker; joined where the
+    launch's tables are built, so the walks overlap the refresh / set_path / reset), or None where that
+    does not apply. The cursor sizes the draw by its own first window, so the window consumes it."""
+    eng = (getattr(model, "_chain_engines", None) or {}).get(key)
+    if eng is None or state is not None or _static_schedule(schedule, max_iter) or "epoch_chunk" in opts \
+            or getenv("GADMM_DGADMM_EARLY", "1") == "0" or not _dyn_persistent(eng, schedule, max_iter, fabric, opts):
         return None
-    rechains = _rechains(max_iter, schedule.coherence)
-    if len(rechains) >= (1 << 20):
-        return None
-    hints = eng.__dict__.get("_dyn_epoch_hint", {})
-    hk = (float(schedule.coherence), schedule.kind, int(max_iter), int(n_total))
-    chunk = max(16, int(hints[hk]) + 8) if hk in hints else 128
-    if eng.dynamic_uses_blocked(fabric, schedule.coherence):
-        chunk = min(chunk, _max_epochs(eng) - 1)
-    E_total = 1 + len(rechains)
-    e1 = min(chunk, E_total)
-    look = e1 if e1 < E_total else e1 - 1
-    if look <= 0:
-        return None
-    saved = schedule.save()
-    join = schedule.prefetch_async(look)
-    if join is None:
-        return None
-    return saved, look, join
+    cur = _dyn_cursor(eng, schedule, max_iter, fabric, n_total, early=True)
+    _timing.host_stamp("native:early_draw")
+    return cur
 
 
 def _static_schedule(schedule, max_iter) -> bool:
@@ -513,355 +494,219 @@ def _static_schedule(schedule, max_iter) -> bool:
         or schedule.coherence >= max_iter + 1
 
 
-def _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule, local_solver,
-                       step, max_inner, inner_tol, cost_quirk, name, opts, state=None):
-    """``opts``: ``block`` (iterations per graph replay), ``persistent`` (auto/True/False), ``graph``,
-    ``cache``, ``state``, ``refresh`` (recompute Gram + inverses from the raw shards first), ``fabric`` (an ``XgmiFabric``: the device-initiated multi-GPU persistent
-    kernels; with ``table_slots >= lag + 4`` it also runs multi-rank D-GADMM in one launch),
-    ``stop_iter`` (static chains: run no iteration past it, on the graph engine - the persistent
-    kernels stop only at the decision).
-    ``state``: ``(theta_table (n_total, d), mu (n_local, d), start_iter)`` - resume a static chain
-    from a checkpoint (one rank): the engine's tables are loaded and the kernels start at
-    ``start_iter`` with no pending head duals (a saved state has them applied); the result covers
-    iterations ``start_iter..iters`` like the torch path's."""
-    from ..engine.chain_engine import NativeChainEngine, ResidencyError, HandoffTimeout
+class _Solved(NamedTuple):
+    """What a solve strategy hands to the result assembly."""
+    engine_kind: str
+    iters: int
+    done: int
+    com_cost: Sequence[float]
+    p2p: int = 0
+    mon: int = 0
+    wire: int = 0
 
-    _timing.host_stamp("native:start")
-    rank = comm.rank
-    rcomm = comm if comm.nranks > 1 else None
-    fabric = opts.get("fabric")
-    kind = "linear" if local_solver == "closed" else "logistic"
-    # iterations per replayed graph: a logistic phase is ~37 us, so the replays left over after the stop
-    # decision cost more than the extra host round trips of short blocks (tools/logistic_block_sweep.py:
-    # 6.78 / 6.81 / 6.88 / 7.11 ms for 8 / 16 / 32 / 64)
-    block = int(opts.get("block", 16 if comm.nranks > 1 else (8 if kind == "logistic" else 32)))
-    pre = (model.A, model.b, model.yy) if kind == "linear" else None
-    # one engine per (model, configuration) on a single rank: repeated solves (rho sweeps, benchmarks,
-    # D-GADMM re-runs) reuse its device buffers, cached inverses and captured graph
-    key = (kind, local_solver, n_total, tuple(map(int, local_ids)), float(rho), int(max_iter), block,
-           float(step), int(max_inner), float(inner_tol), float(getattr(model, "lam", 0.0)),
-           opts.get("chord"), bool(opts.get("residual", True)))
-    cache = getattr(model, "_chain_engines", None) if rcomm is None else None
-    eng = cache.get(key) if cache is not None else None
-    fresh = eng is None
-    # ``refresh``: the solve starts from the raw shards -- the Gram (K1) and the cached inverses (K2) are
-    # recomputed (benchmarks time the same set-up in every config: bench.py's headline does this too)
+
+def _acquire_engine(model, key, local_ids, n_total, kind, rho, obj0, tol, max_iter, rcomm, block, local_solver, step,
+                    max_inner, inner_tol, opts):
+    """``(engine, fresh)``: on a single rank the engine cached on the model under ``key`` (base.py:
+    cached_engine), else a new one. ``opts['refresh']``: the solve starts from the raw shards -- the Gram
+    (K1) and the cached inverses (K2) are recomputed (benchmarks time the same set-up in every config:
+    bench.py's headline does this too)."""
+    from ..engine.chain_engine import NativeChainEngine
     refresh = bool(opts.get("refresh", False)) and kind == "linear"
-    if eng is None and refresh:
-        from ..ops.linalg import gram
-        gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
-    # D-GADMM on a cached engine: the first launch's chains start drawing now (geometries from the
-    # schedule's RNG here, greedy walks on the native host worker) and are joined where the launch's
-    # tables are built, so the walks overlap the refresh / set_path / reset below
-    early = None
-    if eng is not None and state is None and not _static_schedule(schedule, max_iter) \
-            and opts.get("persistent", "auto") in (True, "auto") and "epoch_chunk" not in opts \
-            and getenv("GADMM_DGADMM_EARLY", "1") != "0":
-        early = _dyn_early_draw(eng, schedule, max_iter, fabric, n_total)
-        _timing.host_stamp("native:early_draw")
-    try:
-        if eng is not None and refresh:
+
+    def build():
+        if refresh:
+            from ..ops.linalg import gram
+            gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
+        return NativeChainEngine(model.X, model.y, local_ids, n_total, kind, rho=rho, obj0=obj0, tol=tol,
+                                 max_iter=max_iter, lam=getattr(model, "lam", 0.0), step=step, max_inner=max_inner,
+                                 inner_tol=inner_tol, comm=rcomm, block=block,
+                                 precomputed=(model.A, model.b, model.yy) if kind == "linear" else None,
+                                 local_solver="newton" if local_solver == "newton" else "gd",
+                                 chord=None if opts.get("chord") is None else float(opts["chord"]),
+                                 residual=bool(opts.get("residual", True)), obj_mode=str(opts.get("obj_mode", "auto")))
+
+    def refresh_cached(eng):
+        if refresh:
             # in place on the engine's stream (Gram, then inverses), while the native worker walks the
             # early-drawn chains (launching the refresh before the draw exposed the walks at the join:
             # profiles/r06_dgadmm)
             eng.refresh(model.X, model.y)
             _timing.host_stamp("native:refresh")
-        if eng is None:
-            eng = NativeChainEngine(model.X, model.y, local_ids, n_total, kind, rho=rho, obj0=obj0, tol=tol,
-                                    max_iter=max_iter, lam=getattr(model, "lam", 0.0), step=step, max_inner=max_inner,
-                                    inner_tol=inner_tol, comm=rcomm, block=block, precomputed=pre,
-                                    local_solver="newton" if local_solver == "newton" else "gd",
-                                    chord=None if opts.get("chord") is None else float(opts["chord"]),
-                                    residual=bool(opts.get("residual", True)),
-                                    obj_mode=str(opts.get("obj_mode", "auto")))
-            if rcomm is None and opts.get("cache", True):
-                if cache is None:
-                    cache = {}
-                    model._chain_engines = cache
-                cache[key] = eng
-        else:
-            eng.set_targets(obj0, tol)
-        _timing.host_stamp("native:engine")
-        eng.set_path(schedule.path, placement, rank)
-        _timing.host_stamp("native:set_path")
-        start = 1 if state is None else int(state[2])
-        static = _static_schedule(schedule, max_iter)
-        if state is not None and not (static and comm.nranks == 1):
-            raise ValueError("native resume: one rank, static chain")
 
-        def load_state():  # fresh solve state, or the checkpoint's tables at start_iter (no pending duals)
-            eng.reset(start_iter=start)
-            if state is not None:
-                eng.stream.wait_stream(torch.cuda.current_stream(model.device))  # the state's producers
-                with torch.cuda.stream(eng.stream):
-                    eng.theta.copy_(state[0].to(eng.theta.device, torch.float64).reshape(eng.theta.shape))
-                    eng.mu.copy_(state[1].to(eng.mu.device, torch.float64).reshape(eng.mu.shape))
+    if rcomm is not None:
+        return build(), True
+    return cached_engine(model, key, build, (obj0, tol), opts.get("cache", True), hit=refresh_cached)
 
-        load_state()
-        _timing.host_stamp("native:reset")
-        stop_iter = int(opts.get("stop_iter", 0))
-        if fresh or state is not None:
-            # inputs made on other streams (a new engine's set-up, a loaded state) are complete before the
-            # solve; a cached engine's inputs are, and its own stream orders the reset before the kernel
-            torch.cuda.synchronize(model.device)
-    except BaseException:
-        # the early draw moved the schedule's RNG ahead of its chains: join the worker and rewind, so a
-        # re-run of this schedule draws the same chain sequence (seeded D-GADMM reproducibility)
-        if early is not None:
-            early[2]()
-            schedule.restore(early[0])
-        raise
-    if fabric is not None and comm.nranks > 1:
-        # the device-initiated kernels need every rank's launch: their eligibility is agreed, and a rank
-        # that cannot run them sends every rank to the graph engine over the session's data plane
-        import torch.distributed as dist
-        elig = opts.get("persistent", "auto") in (True, "auto") and (
-            eng.persistent_eligible(fabric) if static else eng.dynamic_eligible(fabric))
-        t = torch.tensor([0.0 if elig else 1.0], dtype=torch.float64)
-        dist.all_reduce(t, group=getattr(comm, "control_group", None))
-        if float(t.item()) != 0.0:
-            eng.close()
-            fb = opts.get("fallback_comm")
-            if fb is None:
-                raise RuntimeError("%s: the xGMI kernel is not eligible on some rank and no data-plane "
-                                   "fallback was given" % name)
-            o2 = {k: v for k, v in opts.items() if k not in ("fabric", "fallback_comm")}
-            res = _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, fb, placement, schedule,
-                                     local_solver, step, max_inner, inner_tol, cost_quirk, name, o2, state=state)
-            res.extra["fabric_fallback"] = "xgmi kernel not eligible on some rank: %s" % getattr(fb, "backend", "")
-            return res
-    t0 = time.perf_counter()
+
+def _load_state(eng, model, state, start):
+    """Fresh solve state, or the checkpoint's tables at ``start`` (no pending duals)."""
+    eng.reset(start_iter=start)
+    if state is not None:
+        eng.stream.wait_stream(torch.cuda.current_stream(model.device))  # the state's producers
+        with torch.cuda.stream(eng.stream):
+            eng.theta.copy_(state[0].to(eng.theta.device, torch.float64).reshape(eng.theta.shape))
+            eng.mu.copy_(state[1].to(eng.mu.device, torch.float64).reshape(eng.mu.shape))
+
+
+def _prepare(eng, fresh, model, schedule, placement, comm, state, start, static):
+    """Install the initial chain and the solve state on ``eng``."""
+    _timing.host_stamp("native:engine")
+    eng.set_path(schedule.path, placement, comm.rank)
+    _timing.host_stamp("native:set_path")
+    if state is not None and not (static and comm.nranks == 1):
+        raise ValueError("native resume: one rank, static chain")
+    _load_state(eng, model, state, start)
+    _timing.host_stamp("native:reset")
+    if fresh or state is not None:
+        # inputs made on other streams (a new engine's set-up, a loaded state) are complete before the
+        # solve; a cached engine's inputs are, and its own stream orders the reset before the kernel
+        torch.cuda.synchronize(model.device)
+
+
+def _fabric_fallback(eng, comm, fabric, static, name, opts, rerun) -> Optional[RunResult]:
+    """The device-initiated kernels need every rank's launch: their eligibility is agreed, and a rank that
+    cannot run them sends every rank to the graph engine over the session's data plane (its result;
+    None: every rank is eligible)."""
+    elig = opts.get("persistent", "auto") in (True, "auto") and (
+        eng.persistent_eligible(fabric) if static else eng.dynamic_eligible(fabric))
+    if control_reduce(comm, [0.0 if elig else 1.0])[0] == 0.0:
+        return None
+    eng.close()
+    fb = opts.get("fallback_comm")
+    if fb is None:
+        raise RuntimeError("%s: the xGMI kernel is not eligible on some rank and no data-plane "
+                           "fallback was given" % name)
+    res = rerun(fb, {k: v for k, v in opts.items() if k not in ("fabric", "fallback_comm")})
+    res.extra["fabric_fallback"] = "xgmi kernel not eligible on some rank: %s" % getattr(fb, "backend", "")
+    return res
+
+
+def _solve_static(eng, model, comm, fabric, schedule, scale, local_solver, opts, state, start, rerun):
+    """A static chain: the persistent kernel, else (not wanted, not eligible, ``stop_iter``, or a launch that
+    could not run) the graph engine. A ``_Solved``, or the ``RunResult`` of the chord-Newton exact re-run."""
+    from ..engine.chain_engine import ResidencyError, HandoffTimeout
+    stop_iter = int(opts.get("stop_iter", 0))
+    r = None
+    engine_kind = None
+    if opts.get("persistent", "auto") in (True, "auto") and stop_iter <= 0 and eng.persistent_eligible(fabric):
+        try:
+            r = eng.run_persistent(fabric=fabric, start_iter=start, fetch_trace=True)
+            engine_kind = "persistent"
+        except (ResidencyError, HandoffTimeout) as e:
+            # the device could not hold every workgroup, or a hand-off stalled: the graph engine
+            # runs the same schedule without co-residency (single rank; several ranks must agree,
+            # see bench.py, so they raise)
+            if comm.nranks > 1:
+                raise
+            _load_state(eng, model, state, start)
+            engine_kind = "graph(fallback: %s)" % type(e).__name__
+    if r is None:
+        r = eng.run(stop_iter=stop_iter, use_graph=opts.get("graph", True))
+        if engine_kind is None:
+            engine_kind = "graph" if eng.graph_ok() else "eager"
+    if local_solver == "newton" and not opts.get("_exact_retry"):
+        # chord-Newton safety net: a local solve that reached the 50-step cap unconverged (a stale
+        # inverse can send the first chord steps far off: the derm-shaped E4 problem at rho = 0.02) means
+        # the iterates are not the exact prox the spec asks for (group_ADMM_logistic.m:26-49) -- the
+        # whole solve is re-run with exact Newton steps (every step refreshes its inverse), as torch does
+        fails = int(eng.ctl[7].item())
+        chord_used = eng.chord_persistent if engine_kind == "persistent" else eng.chord
+        if comm.nranks > 1:
+            fails = int(control_reduce(comm, [fails])[0])
+        if fails > 0 and chord_used > 0.0:
+            res2 = rerun(comm, dict(opts, chord=0.0, cache=False, _exact_retry=fails))
+            res2.extra["chord_fallback"] = "%d unconverged chord-Newton local solves: re-run exact" % fails
+            return res2
+    per = float(np.sum(schedule.cost)) * scale
+    return _Solved(engine_kind, r.iters, r.done, np.arange(1, r.iters - start + 2) * per, r.p2p_bytes,
+                   r.monitor_bytes, r.wire_bytes)
+
+
+def _solve_dynamic(eng, cur, comm, fabric, schedule, placement, scale, opts) -> _Solved:
+    """D-GADMM in persistent launches of epoch chunks (engine/epoch_chunks.py): window -> launch -> the
+    ranks' agreement on the outcome -> advance, until a launch ends in a stop decision."""
+    from ..engine.chain_engine import HandoffTimeout
+    use_blk = eng.dynamic_uses_blocked(fabric, schedule.coherence)
+    p2p = mon = wire = 0
+    more = True
+    while more:
+        _timing.host_stamp("dyn:chunk_setup")
+        starts, chains, start_iter, pending_in, hard_stop, cont = cur.window()
+        _timing.host_stamp("dyn:draws")
+        timed_out = r = None
+        try:
+            # the cumulative cost needs no outcome: it is summed while the launch executes
+            r = eng.run_persistent(epochs=(starts, chains), fabric=fabric, start_iter=start_iter,
+                                   pending_in=pending_in, hard_stop=hard_stop, cont=cont, fetch_trace=True,
+                                   blocked_dyn=use_blk, on_enqueued=lambda: cur.com_cost(scale))
+        except HandoffTimeout as e:
+            if comm.nranks == 1:
+                raise
+            timed_out = e  # agree with the other ranks first: they may be waiting on this chunk's outcome
+        done, iters = (int(r.done), int(r.iters)) if r is not None else (4, 0)
+        if comm.nranks > 1:
+            # every chunk ends in ONE collective on every rank: the monitor rank holds the outcome
+            # (the workers may stop at the hard stop before the decision of its last lag iterations
+            # reaches them), and a timeout on ANY rank is agreed in the same all-reduce, so all ranks
+            # raise together instead of the others waiting in a broadcast until the group's timeout.
+            # MAX over [rank 0's (done, iters) | -1 elsewhere, failed flag].
+            mine = comm.rank == 0
+            done, iters, failed = (int(v) for v in control_reduce(
+                comm, [done if mine else -1, iters if mine else -1, timed_out is not None], "max"))
+            if failed > 0:
+                raise HandoffTimeout("D-GADMM chunk: a persistent hand-off timed out on some rank"
+                                     + (" (here: %s)" % timed_out if timed_out is not None else ""))
+        p2p, mon, wire = p2p + r.p2p_bytes, mon + r.monitor_bytes, wire + r.wire_bytes
+        more = cur.advance(done, iters, start_iter - 1 + int(r.iterations_launched))
+    _timing.host_stamp("dyn:launches_done")
+    cur.finish()
+    com_cost = cur.com_cost(scale)[:cur.iters]  # already summed while the last launch ran
+    # leave the schedule (and the engine's plan) where the epoch-by-epoch run would have left them --
+    # unless nobody can look: a schedule private to this call (dynamic_group_admm builds one per solve)
+    # with no state to flush (~6 us of host time per D-GADMM solve, profiles/r06_dgadmm)
+    if not getattr(schedule, "private", False) or opts.get("state", True):
+        cur.skip_schedule()
+        eng.set_path(cur.paths[cur.reached - 1], placement, comm.rank)
+    return _Solved("persistent-dynamic", cur.iters, cur.done, com_cost, p2p, mon, wire)
+
+
+def _solve_epochs(eng, comm, schedule, placement, max_iter, scale) -> _Solved:
+    """D-GADMM epoch by epoch: at a re-chain iteration flush the heads' pending duals with the old chain,
+    install the new chain, continue. Every rank draws the same chain sequence."""
     cc = 0.0
     com_cost = []
-    n_heads = (n_total + 1) // 2
-    p2p = 0
-    mon = 0
-    wire = 0
-    want_persistent = opts.get("persistent", "auto") in (True, "auto")
-    if static:
-        r = None
-        engine_kind = None
-        if want_persistent and stop_iter <= 0 and eng.persistent_eligible(fabric):
-            try:
-                r = eng.run_persistent(fabric=fabric, start_iter=start, fetch_trace=True)
-                engine_kind = "persistent"
-            except (ResidencyError, HandoffTimeout) as e:
-                # the device could not hold every workgroup, or a hand-off stalled: the graph engine
-                # runs the same schedule without co-residency (single rank; several ranks must agree,
-                # see bench.py, so they raise)
-                if comm.nranks > 1:
-                    raise
-                load_state()
-                engine_kind = "graph(fallback: %s)" % type(e).__name__
-        if r is None:
-            r = eng.run(stop_iter=stop_iter, use_graph=opts.get("graph", True))
-            if engine_kind is None:
-                engine_kind = "graph" if eng.graph_ok() else "eager"
-        iters, done = r.iters, r.done
-        p2p, mon, wire = r.p2p_bytes, r.monitor_bytes, r.wire_bytes
-        per = float(np.sum(schedule.cost)) * (n_heads if cost_quirk else 1)
-        com_cost = np.arange(1, iters - start + 2) * per
-        if local_solver == "newton" and not opts.get("_exact_retry"):
-            # chord-Newton safety net: a local solve that reached the 50-step cap unconverged (a stale
-            # inverse can send the first chord steps far off: the derm-shaped E4 problem at rho = 0.02) means
-            # the iterates are not the exact prox the spec asks for (group_ADMM_logistic.m:26-49) -- the
-            # whole solve is re-run with exact Newton steps (every step refreshes its inverse), as torch does
-            fails = int(eng.ctl[7].item())
-            chord_used = eng.chord_persistent if engine_kind == "persistent" else eng.chord
-            if comm.nranks > 1:
-                import torch.distributed as dist
-                t = torch.tensor([float(fails)], dtype=torch.float64)
-                dist.all_reduce(t, group=getattr(comm, "control_group", None))
-                fails = int(t.item())
-            if fails > 0 and chord_used > 0.0:
-                res2 = _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement,
-                                          schedule, local_solver, step, max_inner, inner_tol, cost_quirk, name,
-                                          dict(opts, chord=0.0, cache=False, _exact_retry=fails), state=state)
-                res2.extra["chord_fallback"] = "%d unconverged chord-Newton local solves: re-run exact" % fails
-                return res2
-    elif want_persistent and eng.dynamic_eligible(fabric) \
-            and len(_rechains(max_iter, schedule.coherence)) < (1 << 20):
-        # D-GADMM in persistent launches of up to `epoch_chunk` epochs each: the seeded chain sequence
-        # is drawn a chunk ahead (batched, the identical RNG stream), every worker switches neighbours /
-        # role at each epoch on the device. A chunk ends at a hard stop just before its last+1 epoch
-        # (whose neighbours already receive theta); unless the monitor decided a stop, the next launch
-        # continues with the same tag salt from there. Only the chains a solve reaches are drawn.
-        engine_kind = "persistent-dynamic"
-        rechains = _rechains(max_iter, schedule.coherence)
-        # first launch: `epoch_chunk` epochs, each continuation twice the previous. Drawing a chain
-        # costs ~0.75 us on the host, a launch + read-back ~0.25 ms: 128 keeps coherence-10 solves
-        # (~51 epochs) to one launch with few spare chains, coherence-1 solves (~250) to two
-        # Without an explicit chunk, a repeat of a schedule of the same shape (coherence, kind, max_iter,
-        # N) on this engine sizes its first launch from the epochs the previous solve reached (+ margin):
-        # chains beyond them would be drawn for nothing. Only the launch size follows the hint; the
-        # chains and iterates do not (a shortfall costs a continuation launch).
-        hint_key = (float(schedule.coherence), schedule.kind, int(max_iter), int(n_total))
-        hints = eng.__dict__.setdefault("_dyn_epoch_hint", {})
-        if "epoch_chunk" in opts:
-            chunk = max(1, int(opts["epoch_chunk"]))
-        elif hint_key in hints:
-            chunk = max(16, int(hints[hint_key]) + 8)
-        else:
-            chunk = 128
-        # the blocked kernel's dynamic mode stages a launch's epoch tables in LDS: at most
-        # gadmm_chain_blocked_max_epochs rows per launch (this chunk + the look-ahead epoch)
-        use_blk = eng.dynamic_uses_blocked(fabric, schedule.coherence)
-        cap = _max_epochs(eng) - 1 if use_blk else 1 << 30
-        chunk = min(chunk, cap)
-        saved = early[0] if early is not None else schedule.save()
-        E_total = 1 + len(rechains)
-        # epoch e's chain is row e of one (E_total, N) table, filled as chains are drawn (epoch 0: the
-        # initial chain); epoch e starts at iteration ep_start[e]
-        Pall = np.empty((E_total, n_total), dtype=np.int64)
-        Pall[0] = saved[1]
-        ep_start = np.concatenate([np.ones(1, dtype=np.int64), rechains])
-        drawn_C = []
-        n_drawn = [1]
+    p2p = mon = wire = 0
+    it = 1
+    done = iters = 0
+    while it <= max_iter and not done:
+        nxt = it + 1
+        while nxt <= max_iter and not _is_rechain(nxt, schedule.coherence):
+            nxt += 1
+        per = float(np.sum(schedule.cost)) * scale
+        r = eng.run(stop_iter=nxt - 1, use_graph=False)
+        p2p += r.p2p_bytes
+        mon += r.monitor_bytes
+        wire += r.wire_bytes
+        for _ in range(it, r.iters + 1):
+            cc += per
+            com_cost.append(cc)
+        done = r.done
+        iters = r.iters
+        if done or nxt > max_iter:
+            break
+        eng.flush_duals()
+        schedule.step(nxt)
+        eng.set_path(schedule.path, placement, comm.rank)
+        if comm.nranks > 1:
+            eng.exchange("tail")  # refresh ghost rows of the new cross-rank neighbours
+        it = nxt
+    return _Solved("epochs", iters, done, com_cost, p2p, mon, wire)
 
-        pend = [early]
 
-        def ensure(upto):  # epochs 0..upto drawn
-            need = upto + 1 - n_drawn[0]
-            if pend[0] is not None:  # the early draw covers epochs 1..early[1]
-                e_ = pend[0]
-                pend[0] = None
-                if n_drawn[0] == 1 and need >= e_[1]:
-                    Pn_, Cn_ = e_[2]()
-                    Pall[1:1 + e_[1]] = Pn_
-                    n_drawn[0] += e_[1]
-                    drawn_C.append(Cn_)
-                    need -= e_[1]
-                else:  # not this shape (cannot happen: same chunk rule); the schedule restarts from it
-                    e_[2]()
-                    schedule.restore(e_[0])
-            if need > 0:
-                Pn_, Cn_ = schedule.prefetch_arrays(need)
-                Pall[n_drawn[0]:n_drawn[0] + need] = Pn_
-                n_drawn[0] += need
-                drawn_C.append(Cn_)
-
-        e0, start_iter, pending_in, cont = 0, 1, 0, False
-        done = iters = 0
-        last_launched = 0
-        pre = {}
-        ep_all = ep_start  # every epoch's first iteration (ep_start is truncated after the launches)
-
-        def cost_arrays():
-            """Per-epoch chain costs of every epoch drawn so far and the cumulative com_cost of each
-            iteration they cover: needs no outcome, so it runs while the launch executes
-            (run_persistent's on_enqueued) instead of after it."""
-            nd = n_drawn[0]
-            if pre.get("nd") == nd:
-                return
-            if drawn_C and any(c.dtype == object for c in drawn_C):
-                Cn_ = np.empty(sum(len(c) for c in drawn_C), dtype=object)
-                Cn_[:] = [c for cc in drawn_C for c in cc]
-            else:
-                Cn_ = np.concatenate(drawn_C) if drawn_C else np.zeros((0, max(n_total - 1, 0)))
-            # per-epoch cost; the initial cost vector may be ragged (the v0 column-slice quirk)
-            csum = Cn_.sum(axis=1) if (len(Cn_) and Cn_.dtype != object) else np.asarray([float(np.sum(c)) for c in Cn_])
-            per_it_ = np.concatenate([[float(np.sum(saved[2]))], csum]) * (n_heads if cost_quirk else 1)
-            span = int(ep_all[nd] - 1) if nd < E_total else int(max_iter)  # iterations the drawn epochs cover
-            which_ = np.searchsorted(ep_all[:nd], np.arange(1, span + 1), side="right") - 1
-            pre.update(nd=nd, Cn=Cn_, com=np.cumsum(per_it_[which_]))
-        while True:
-            e1 = min(e0 + chunk, E_total)  # this launch executes epochs e0 .. e1 - 1
-            look = e1 if e1 < E_total else e1 - 1  # + the next epoch's chain (push targets of theta^hard_stop)
-            _timing.host_stamp("dyn:chunk_setup")
-            ensure(look)
-            _timing.host_stamp("dyn:draws")
-            hard_stop = ep_start[e1] - 1 if e1 < E_total else 0
-            st_arr = ep_start[e0:look + 1]
-            P_arr = Pall[e0:look + 1]
-            timed_out = None
-            try:
-                r = eng.run_persistent(epochs=(st_arr, P_arr), fabric=fabric, start_iter=start_iter,
-                                       pending_in=pending_in, hard_stop=hard_stop, cont=cont, fetch_trace=True,
-                                       blocked_dyn=use_blk, on_enqueued=cost_arrays)
-            except HandoffTimeout as e:
-                if comm.nranks == 1:
-                    raise
-                timed_out = e  # agree with the other ranks first: they may be waiting on this chunk's outcome
-                r = None
-            done, iters = (int(r.done), int(r.iters)) if r is not None else (4, 0)
-            if comm.nranks > 1:
-                # every chunk ends in ONE collective on every rank: the monitor rank holds the outcome
-                # (the workers may stop at the hard stop before the decision of its last lag iterations
-                # reaches them), and a timeout on ANY rank is agreed in the same all-reduce, so all ranks
-                # raise together instead of the others waiting in a broadcast until the group's timeout.
-                # MAX over [rank 0's (done, iters) | -1 elsewhere, failed flag].
-                import torch.distributed as dist
-                mine = comm.rank == 0
-                t = torch.tensor([float(done) if mine else -1.0, float(iters) if mine else -1.0,
-                                  1.0 if timed_out is not None else 0.0], dtype=torch.float64)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=getattr(comm, "control_group", None))
-                if float(t[2].item()) > 0:
-                    raise HandoffTimeout("D-GADMM chunk: a persistent hand-off timed out on some rank"
-                                         + (" (here: %s)" % timed_out if timed_out is not None else ""))
-                done, iters = int(t[0].item()), int(t[1].item())
-            p2p, mon, wire = p2p + r.p2p_bytes, mon + r.monitor_bytes, wire + r.wire_bytes
-            last_launched = hard_stop if done == 5 else start_iter - 1 + int(r.iterations_launched)
-            if done != 5:
-                if done == 0:
-                    raise RuntimeError("D-GADMM chunk ended without an outcome (hard stop %d)" % hard_stop)
-                break
-            start_iter, pending_in, cont = hard_stop + 1, 1, True
-            e0 = e1 - 1  # epoch 0 of the next launch: this chunk's last (the flush of pending duals)
-            chunk = min(2 * chunk, cap)
-        _timing.host_stamp("dyn:launches_done")
-        if done == 5:
-            done = 2
-        ep_start = ep_start[:n_drawn[0]]
-        hints[hint_key] = int(np.searchsorted(ep_start, max(last_launched, 1), side="right"))
-        Pn = Pall[1:n_drawn[0]]
-        cost_arrays()  # already done while the last launch ran, unless it drew more epochs since
-        Cn = pre["Cn"]
-        starts = ep_start
-        P = Pall[:n_drawn[0]]
-        com_cost = pre["com"][:iters]
-        # leave the schedule (and the engine's plan) where the epoch-by-epoch run would have left them --
-        # unless nobody can look: a schedule private to this call (dynamic_group_admm builds one per solve)
-        # with no state to flush (~6 us of host time per D-GADMM solve, profiles/r06_dgadmm)
-        if not getattr(schedule, "private", False) or opts.get("state", True):
-            schedule.skip(saved, Pn, Cn, int(np.searchsorted(rechains, iters, side="right")))  # rechains ascend
-            eng.set_path(P[int(np.searchsorted(starts, max(last_launched, 1), side="right") - 1)], placement, rank)
-    else:
-        # D-GADMM: run epoch by epoch; at a re-chain iteration flush the heads' pending duals with the
-        # old chain, install the new chain, continue. Every rank draws the same chain sequence.
-        if early is not None:  # (not reached with an early draw: it requires the dynamic path) undo it
-            early[2]()
-            schedule.restore(early[0])
-        engine_kind = "epochs"
-        it = 1
-        done = 0
-        iters = 0
-        while it <= max_iter and not done:
-            nxt = it + 1
-            while nxt <= max_iter and not _is_rechain(nxt, schedule.coherence):
-                nxt += 1
-            per = float(np.sum(schedule.cost)) * (n_heads if cost_quirk else 1)
-            r = eng.run(stop_iter=nxt - 1, use_graph=False)
-            p2p += r.p2p_bytes
-            mon += r.monitor_bytes
-            wire += r.wire_bytes
-            ran_to = r.iters
-            for _ in range(it, ran_to + 1):
-                cc += per
-                com_cost.append(cc)
-            done = r.done
-            iters = ran_to
-            if done or nxt > max_iter:
-                break
-            eng.flush_duals()
-            schedule.step(nxt)
-            eng.set_path(schedule.path, placement, rank)
-            if comm.nranks > 1:
-                eng.exchange("tail")  # refresh ghost rows of the new cross-rank neighbours
-            it = nxt
-    _timing.host_stamp("native:solved")
-    if engine_kind not in ("persistent", "persistent-dynamic"):  # those synchronised after their launch
-        eng.stream.synchronize()
-    wall = time.perf_counter() - t0
+def _native_result(eng, s: _Solved, wall, comm, fabric, name, n_total, obj0, start, local_solver) -> RunResult:
+    """The ``RunResult`` of a native solve, the same on every rank."""
+    iters = s.iters
     tr, tt = eng.traces(iters)
     if start > 1:  # a resumed solve reports iterations start..iters (as the torch path does)
         tr, tt = tr[start - 1:], tt[start - 1:]
@@ -872,59 +717,118 @@ def _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, comm
         buf = torch.from_numpy(np.stack([tr, tt]).astype(np.float64))
         dist.broadcast(buf, src=0, group=getattr(comm, "control_group", None))
         tr, tt = buf[0].numpy().copy(), buf[1].numpy().copy()
-    loss = np.abs(tr - obj0)
     pres = eng.primal_residual(iters)  # K4, emitted by the kernels' tails (this rank's edges)
     if pres is not None and start > 1:
         pres = pres[start - 1:]
-    if pres is not None and comm.nranks > 1:
-        import torch.distributed as dist
-
-        buf = torch.from_numpy(pres.astype(np.float64))
-        dist.all_reduce(buf, group=getattr(comm, "control_group", None))
-        pres = buf.numpy()
-    bytes_tot = p2p
+    bytes_tot = s.p2p
     if comm.nranks > 1:
-        import torch.distributed as dist
-
-        t = torch.tensor([float(p2p)], dtype=torch.float64)
-        dist.all_reduce(t, group=getattr(comm, "control_group", None))
-        bytes_tot = int(t.item())
-    res = RunResult(algorithm=name, obj=tr, loss=loss, iters=iters, converged=(done == 1), wall_s=wall,
+        if pres is not None:
+            pres = np.asarray(control_reduce(comm, pres))
+        bytes_tot = int(control_reduce(comm, [s.p2p])[0])
+    res = RunResult(algorithm=name, obj=tr, loss=np.abs(tr - obj0), iters=iters, converged=(s.done == 1), wall_s=wall,
                     time_trace=tt,  # measured on the device: decision time of each iteration
                     comm_units=np.arange(start, iters + 1, dtype=np.float64) * n_total,
-                    com_cost=np.asarray(com_cost[:iters - start + 1]), bytes_sent=int(p2p), bytes_total=bytes_tot,
+                    com_cost=np.asarray(s.com_cost[:iters - start + 1]), bytes_sent=int(s.p2p), bytes_total=bytes_tot,
                     primal_res=pres,
-                    extra={"backend": "native", "engine": engine_kind, "rank": rank, "nranks": comm.nranks,
-                           "solver": local_solver, "monitor_bytes": int(mon), "wire_bytes": int(wire),
+                    extra={"backend": "native", "engine": s.engine_kind, "rank": comm.rank, "nranks": comm.nranks,
+                           "solver": local_solver, "monitor_bytes": int(s.mon), "wire_bytes": int(s.wire),
                            "transport": getattr(comm, "backend", "local") if fabric is None else "xgmi",
                            # effective settings (engine-dependent defaults): the objective
                            # evaluation of the phase kernels and, for Newton, the chord threshold used
                            "obj_mode": eng.obj_mode_name})
     if local_solver == "newton":
-        res.extra["chord"] = eng.chord_persistent if str(engine_kind).startswith("persistent") else eng.chord
+        res.extra["chord"] = eng.chord_persistent if str(s.engine_kind).startswith("persistent") else eng.chord
     res.extra["engine_obj"] = eng
+    return res
+
+
+def _resumable_state(res, eng, model, s: _Solved, comm, static, state, start, opts) -> None:
+    """``extra['state']`` / ``extra['state_from']`` for checkpoints: (theta, mu) after the STOPPING
+    iteration, whatever engine ran. A persistent kernel learns the monitor's decision `lag` iterations late
+    and leaves its tables there; the same schedule is then replayed on the graph engine with no iteration
+    past the stop (bit-identical to the persistent kernels on the linear chains, tests/test_gpu.py), so
+    every engine hands back the state -- and next iteration -- of the graph engine
+    (group_ADMM_closedForm.m:105-108)."""
+    state_from = s.engine_kind
+    if s.engine_kind == "persistent" and comm.nranks == 1 and static and s.done in (1, 2) \
+            and int(eng.ctl_state()["iter"]) != s.iters + 1:
+        _load_state(eng, model, state, start)
+        r2 = eng.run(stop_iter=s.iters, use_graph=opts.get("graph", True))
+        state_from = "graph replay to iteration %d" % s.iters
+        if int(r2.iters) != s.iters:
+            state_from += " (replay stopped at %d)" % int(r2.iters)
+    res.extra["state_from"] = state_from
+    # apply the heads' pending (lazy) duals with the current chain, so (theta, mu) is the reference
+    # state after iteration next-1
+    eng.flush_duals()
+    eng.stream.synchronize()  # the flush runs on the engine's stream; the copies below do not
+    res.extra["state"] = (eng.theta.clone(), eng.mu.clone(), int(eng.ctl_state()["iter"]))
+
+
+def _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, comm, placement, schedule, local_solver,
+                       step, max_inner, inner_tol, cost_quirk, name, opts, state=None):
+    """``opts``: ``block`` (iterations per graph replay), ``persistent`` (auto/True/False), ``graph``,
+    ``cache``, ``state``, ``refresh`` (recompute Gram + inverses from the raw shards first), ``fabric`` (an ``XgmiFabric``: the device-initiated multi-GPU persistent
+    kernels; with ``table_slots >= lag + 4`` it also runs multi-rank D-GADMM in one launch),
+    ``stop_iter`` (static chains: run no iteration past it, on the graph engine - the persistent
+    kernels stop only at the decision), ``epoch_chunk`` (D-GADMM: epochs of the first persistent launch).
+    ``state``: ``(theta_table (n_total, d), mu (n_local, d), start_iter)`` - resume a static chain
+    from a checkpoint (one rank): the engine's tables are loaded and the kernels start at
+    ``start_iter`` with no pending head duals (a saved state has them applied); the result covers
+    iterations ``start_iter..iters`` like the torch path's."""
+    _timing.host_stamp("native:start")
+    rcomm = comm if comm.nranks > 1 else None
+    fabric = opts.get("fabric")
+    kind = "linear" if local_solver == "closed" else "logistic"
+    static = _static_schedule(schedule, max_iter)
+    start = 1 if state is None else int(state[2])
+    scale = (n_total + 1) // 2 if cost_quirk else 1  # the reference accumulates sum(pathCost) per head worker
+    # iterations per replayed graph: a logistic phase is ~37 us, so the replays left over after the stop
+    # decision cost more than the extra host round trips of short blocks (tools/logistic_block_sweep.py:
+    # 6.78 / 6.81 / 6.88 / 7.11 ms for 8 / 16 / 32 / 64)
+    block = int(opts.get("block", 16 if comm.nranks > 1 else (8 if kind == "logistic" else 32)))
+    key = (kind, local_solver, n_total, tuple(map(int, local_ids)), float(rho), int(max_iter), block,
+           float(step), int(max_inner), float(inner_tol), float(getattr(model, "lam", 0.0)),
+           opts.get("chord"), bool(opts.get("residual", True)))
+
+    def rerun(comm2, opts2):
+        return _chain_admm_native(model, local_ids, n_total, rho, obj0, tol, max_iter, comm2, placement, schedule,
+                                  local_solver, step, max_inner, inner_tol, cost_quirk, name, opts2, state=state)
+
+    cur = _dyn_early_draw(model, key, schedule, max_iter, fabric, n_total, opts, state) if rcomm is None else None
+    try:
+        eng, fresh = _acquire_engine(model, key, local_ids, n_total, kind, rho, obj0, tol, max_iter, rcomm, block,
+                                     local_solver, step, max_inner, inner_tol, opts)
+        _prepare(eng, fresh, model, schedule, placement, comm, state, start, static)
+    except BaseException:
+        if cur is not None:
+            cur.abandon()
+        raise
+    if fabric is not None and comm.nranks > 1:
+        res = _fabric_fallback(eng, comm, fabric, static, name, opts, rerun)
+        if res is not None:
+            return res
+    t0 = time.perf_counter()
+    if static:
+        solved = _solve_static(eng, model, comm, fabric, schedule, scale, local_solver, opts, state, start, rerun)
+        if isinstance(solved, RunResult):
+            return solved
+    elif _dyn_persistent(eng, schedule, max_iter, fabric, opts):
+        if cur is None:
+            cur = _dyn_cursor(eng, schedule, max_iter, fabric, n_total, opts.get("epoch_chunk"))
+        solved = _solve_dynamic(eng, cur, comm, fabric, schedule, placement, scale, opts)
+    else:
+        if cur is not None:  # (an early draw is only made for the persistent path: not reached) undo it
+            cur.abandon()
+        solved = _solve_epochs(eng, comm, schedule, placement, max_iter, scale)
+    _timing.host_stamp("native:solved")
+    if solved.engine_kind not in ("persistent", "persistent-dynamic"):  # those synchronised after their launch
+        eng.stream.synchronize()
+    wall = time.perf_counter() - t0
+    res = _native_result(eng, solved, wall, comm, fabric, name, n_total, obj0, start, local_solver)
     _timing.host_stamp("native:result")
     if opts.get("state", True):
-        # resumable state for checkpoints: (theta, mu) after the STOPPING iteration, whatever engine ran.
-        # A persistent kernel learns the monitor's decision `lag` iterations late and leaves its tables
-        # there; the same schedule is then replayed on the graph engine with no iteration past the stop
-        # (bit-identical to the persistent kernels on the linear chains, tests/test_gpu.py), so every engine
-        # hands back the state -- and next iteration -- of the graph engine (group_ADMM_closedForm.m:105-108)
-        state_from = engine_kind
-        if engine_kind == "persistent" and comm.nranks == 1 and static and done in (1, 2) \
-                and int(eng.ctl_state()["iter"]) != iters + 1:
-            load_state()
-            r2 = eng.run(stop_iter=iters, use_graph=opts.get("graph", True))
-            state_from = "graph replay to iteration %d" % iters
-            if int(r2.iters) != iters:
-                state_from += " (replay stopped at %d)" % int(r2.iters)
-        res.extra["state_from"] = state_from
-        # apply the heads' pending (lazy) duals with the current chain, so (theta, mu) is the reference
-        # state after iteration next-1
-        eng.flush_duals()
-        eng.stream.synchronize()  # the flush runs on the engine's stream; the copies below do not
-        nxt = int(eng.ctl_state()["iter"])
-        res.extra["state"] = (eng.theta.clone(), eng.mu.clone(), nxt)
+        _resumable_state(res, eng, model, solved, comm, static, state, start, opts)
     return res
 
 

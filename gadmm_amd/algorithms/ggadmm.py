@@ -51,7 +51,7 @@ import torch
 from ..parallel.comm import LocalComm
 from ..parallel.topology import BipartiteGraph
 from ..utils.timing import roctx_range
-from .base import RunResult, Stopper, global_objective_and_residual
+from .base import RunResult, Stopper, cached_engine, global_objective_and_residual
 
 
 def _check_case(model, graph, comm) -> None:
@@ -228,19 +228,9 @@ def _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, opts, quant
     xcd = int(opts.get("xcd", 2))
     residual = bool(opts.get("residual", True))
     key = ("graph", graph.key(), float(rho), int(max_iter), xcd, residual) + (() if quant is None else quant)
-    cache = getattr(model, "_chain_engines", None)
-    eng = cache.get(key) if cache is not None else None
-    fresh = eng is None
-    if eng is None:
-        eng = NativeGraphEngine(model.X, model.y, graph, rho, obj0, tol, max_iter,
-                                precomputed=(model.A, model.b, model.yy), xcd=xcd, residual=residual, quant=quant)
-        if opts.get("cache", True):
-            if cache is None:
-                cache = {}
-                model._chain_engines = cache
-            cache[key] = eng
-    else:
-        eng.set_targets(obj0, tol)
+    eng, fresh = cached_engine(model, key, lambda: NativeGraphEngine(
+        model.X, model.y, graph, rho, obj0, tol, max_iter, precomputed=(model.A, model.b, model.yy), xcd=xcd,
+        residual=residual, quant=quant), (obj0, tol), opts.get("cache", True))
     why = eng.refusal()
     if why is not None:
         return None, why

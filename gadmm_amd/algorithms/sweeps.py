@@ -25,7 +25,7 @@ from ..parallel.topology import PathSchedule, Placement
 from ..utils import timing as _timing
 from ..utils.env import getenv
 from ..utils.timing import roctx_range
-from .base import RunResult
+from .base import RunResult, cached_engine
 from .gadmm import _quant_accounting, _static_schedule, chain_admm, dynamic_group_admm
 
 
@@ -86,23 +86,17 @@ def _group_engine(model, key: tuple, opts: dict, build: Callable, targets: tuple
     """The sweep engine of a group: the one cached under ``key`` in ``model._chain_engines`` with new
     ``set_targets(*targets)``, or ``build()``, its set-up complete, cached unless ``opts['cache']`` is
     off. ``refresh``: the Gram and the inverses are recomputed from the raw shards first."""
-    cache = getattr(model, "_chain_engines", None)
-    sw = cache.get(key) if cache is not None else None
-    if sw is not None:
-        sw.set_targets(*targets)
+    def build_fresh():
         if refresh:
-            sw.refresh(model.X, model.y)
-        return sw
-    if refresh:
-        from ..ops.linalg import gram
-        gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
-    sw = build()
-    torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
-    if opts.get("cache", True):
-        if cache is None:
-            cache = {}
-            model._chain_engines = cache
-        cache[key] = sw
+            from ..ops.linalg import gram
+            gram(model.X, model.y, out=(model.A, model.b, model.yy))  # the new engine inverts the fresh Gram
+        return build()
+
+    sw, fresh = cached_engine(model, key, build_fresh, targets, opts.get("cache", True))
+    if fresh:
+        torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
+    elif refresh:
+        sw.refresh(model.X, model.y)
     return sw
 
 
@@ -482,7 +476,7 @@ def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, c
             if _static_schedule(scheds[j], cap):  # chain_admm's static-chain accounting
                 com = np.arange(1, iters + 1) * (float(np.sum(r.cost0)) * scale)
             else:
-                com = _dyn_com_cost(r, n_total, scale)[:iters]
+                com = r.cursor.com_cost(scale)[:iters]
             res = _member_result("D-GADMM(coh=%s)" % coh, sw, j, len(group), iters, r.done, obj0, n_total,
                                  sum(sw.last_round_ms[:r.rounds]) * 1e-3, r.tail_ticks, r.placed,
                                  engine="persistent-dynamic", com_cost=np.asarray(com[:iters]))
@@ -505,17 +499,3 @@ def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, c
     return _run_sweep(list(zip(coherences, seeds, caps)), sequential_one, gates, capacity, run_group,
                       "D-GADMM sweep native N=%d K=%d" % (n_total, len(coherences)))
 
-
-def _dyn_com_cost(r, n_total: int, scale: int) -> np.ndarray:
-    """Cumulative ``com_cost`` of the iterations covered by the epochs a sweep member drew, with the
-    arithmetic of ``_chain_admm_native``'s ``cost_arrays`` (per-epoch hop-cost sums, scaled, one cumsum)."""
-    drawn_C, nd = r.costs, len(r.starts)
-    if drawn_C and any(c.dtype == object for c in drawn_C):
-        Cn = np.empty(sum(len(c) for c in drawn_C), dtype=object)
-        Cn[:] = [c for cc in drawn_C for c in cc]
-    else:
-        Cn = np.concatenate(drawn_C) if drawn_C else np.zeros((0, max(n_total - 1, 0)))
-    csum = Cn.sum(axis=1) if (len(Cn) and Cn.dtype != object) else np.asarray([float(np.sum(c)) for c in Cn])
-    per_it = np.concatenate([[float(np.sum(r.cost0))], csum]) * scale
-    which = np.searchsorted(r.starts[:nd], np.arange(1, int(r.span) + 1), side="right") - 1
-    return np.cumsum(per_it[which])

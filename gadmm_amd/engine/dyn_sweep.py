@@ -5,8 +5,8 @@ A D-GADMM solve is not one launch: it runs in epoch chunks (a chunk ends at a ha
 its last + 1 epoch; the next launch continues with the same tag salt), and an LDS-staged launch takes
 at most ``gadmm_chain_blocked_max_epochs`` epochs. The members of a sweep therefore finish in different
 launches. ``DynSweepEngine.run`` works in ROUNDS: each round draws and stages the next chunk of every
-unfinished member (the member's own chunk rule, as ``_chain_admm_native``: first ``epoch_chunk``
-epochs, default 128, then doubling, capped at the LDS rows, plus the look-ahead epoch), launches them
+unfinished member (the member's own ``EpochCursor``, epoch_chunks.py: first ``epoch_chunk`` epochs,
+default 128, then doubling, capped at the LDS rows, plus the look-ahead epoch), launches them
 all in one call, reads every control block back and decodes it. A member that ran to its hard stop
 (done == 5) continues in the next round; one that reached a stop decision drops out. Slot ``j`` of a
 round's launch is the j-th member still running, so a member may change slot, and XCD, between its
@@ -23,17 +23,17 @@ What a sweep engine is apart from its kernel and its members' preparation: sweep
 from __future__ import annotations
 
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import List, Sequence
 
 import numpy as np
 import torch
 
 from ..ops import native
-from ..parallel.topology import rechain_iterations
 from ..utils import timing as _timing
 from .chain_engine import NativeChainEngine
 from .chain_sweep import sweep_capacity
+from .epoch_chunks import EpochCursor
 from .sweep_base import SweepEngineBase, per_member
 
 
@@ -42,7 +42,8 @@ class DynSweepRun:
     """Outcome of one member. ``rounds``: launches it took part in (rounds 0 .. rounds - 1);
     ``tail_ticks``: device time (s_memrealtime, 100 MHz) between its stop decision and the end of its
     last round; ``starts`` / ``paths`` / ``costs``: first iterations, chains and hop costs of the
-    epochs drawn (epoch 0 = the initial chain, whose cost is ``cost0``); ``span``: the iterations they cover."""
+    epochs drawn (epoch 0 = the initial chain, whose cost is ``cost0``); ``span``: the iterations they cover;
+    ``cursor``: the member's ``EpochCursor`` (its ``com_cost``)."""
     iters: int
     done: int
     rounds: int
@@ -55,6 +56,7 @@ class DynSweepRun:
     costs: list
     cost0: np.ndarray
     span: int
+    cursor: EpochCursor
 
     @property
     def converged(self) -> bool:
@@ -63,40 +65,14 @@ class DynSweepRun:
 
 @dataclass
 class _Member:
-    """A member's chunk cursor between rounds."""
+    """A member between rounds: its engine, its chunk cursor, and where its last round put it."""
     eng: NativeChainEngine
-    schedule: object
-    saved: tuple
-    ep_start: np.ndarray
-    Pall: np.ndarray
-    E_total: int
-    chunk: int
-    cap: int
-    hint_key: tuple
-    n_drawn: int = 1
-    costs: list = field(default_factory=list)
-    e0: int = 0
-    e1: int = 0
-    start_iter: int = 1
-    pending_in: int = 0
-    cont: bool = False
-    hard_stop: int = 0
+    cur: EpochCursor
     rounds: int = 0
-    done: int = 0
-    iters: int = 0
     placed: int = 0
     slot: int = -1
-    last_launched: int = 0
     stop_tick: int = 0
     fetch: bool = False
-
-    def ensure(self, upto: int):  # epochs 0..upto drawn (only the chains a member reaches)
-        need = upto + 1 - self.n_drawn
-        if need > 0:
-            Pn, Cn = self.schedule.prefetch_arrays(need)
-            self.Pall[self.n_drawn:self.n_drawn + need] = Pn
-            self.n_drawn += need
-            self.costs.append(Cn)
 
 
 class DynSweepEngine(SweepEngineBase):
@@ -134,29 +110,6 @@ class DynSweepEngine(SweepEngineBase):
         for m in self.members[1:]:
             m._minv_pad, m._minv_pad_version = m0._minv_pad, m._minv_version
 
-    # ---------------------------------------------------------------------------------------------
-    def _begin(self, m: NativeChainEngine, schedule, epoch_chunk) -> _Member:
-        max_iter = m.max_iter
-        rechains = rechain_iterations(max_iter, schedule.coherence)
-        if len(rechains) >= (1 << 20):
-            raise ValueError("too many epochs for one tag range")
-        cap = int(self.lib.gadmm_chain_blocked_max_epochs()) - 1
-        hint_key = (float(schedule.coherence), schedule.kind, int(max_iter), int(m.n_total))
-        hints = m.__dict__.setdefault("_dyn_epoch_hint", {})
-        if epoch_chunk is not None:
-            chunk = max(1, int(epoch_chunk))
-        elif hint_key in hints:  # a repeat sizes its first launch from the epochs the last solve reached
-            chunk = max(16, int(hints[hint_key]) + 8)
-        else:
-            chunk = 128
-        saved = schedule.save()
-        E_total = 1 + len(rechains)
-        Pall = np.empty((E_total, m.n_total), dtype=np.int64)
-        Pall[0] = saved[1]
-        ep_start = np.concatenate([np.ones(1, dtype=np.int64), np.asarray(rechains, dtype=np.int64)])
-        return _Member(eng=m, schedule=schedule, saved=saved, ep_start=ep_start, Pall=Pall, E_total=E_total,
-                       chunk=min(chunk, cap), cap=cap, hint_key=hint_key)
-
     def run(self, schedules: Sequence, epoch_chunk=None, lag: int = 4, timeout_s: float = 20.0) -> List[DynSweepRun]:
         """Reset every member and run member j over ``schedules[j]`` (a ``PathSchedule`` at its initial
         chain, already installed with ``set_path``) to its own stop; one ``DynSweepRun`` per member.
@@ -169,7 +122,9 @@ class DynSweepEngine(SweepEngineBase):
             raise ValueError("one schedule per member")
         for m in self.members:
             m.reset()
-        state = [self._begin(m, s, epoch_chunk) for m, s in zip(self.members, schedules)]
+        cap = int(self.lib.gadmm_chain_blocked_max_epochs()) - 1  # a launch's epoch tables are staged in LDS
+        state = [_Member(m, EpochCursor(s, m.max_iter, m.n_total, m.__dict__.setdefault("_dyn_epoch_hint", {}),
+                                        epoch_chunk, cap)) for m, s in zip(self.members, schedules)]
         live = list(range(len(state)))
         self.last_round_ms = []
         round_end = []
@@ -182,19 +137,15 @@ class DynSweepEngine(SweepEngineBase):
             plans = []
             for slot, i in enumerate(live):
                 s = state[i]
-                s.e1 = min(s.e0 + s.chunk, s.E_total)  # this launch executes epochs e0 .. e1 - 1
-                look = s.e1 if s.e1 < s.E_total else s.e1 - 1  # + the next epoch's chain
                 # drawn member after member on this thread: the draws are most of the host time ahead of a
                 # launch (~2 us per chain at N = 50), but handing them to host threads did not shorten it
                 # (the schedule's batched draw holds the interpreter lock: profiles/dyn_sweep)
-                s.ensure(look)
+                starts, chains, start_iter, pending_in, hard_stop, cont = s.cur.window()
                 _timing.host_stamp("dsw:drawn")
-                s.hard_stop = int(s.ep_start[s.e1] - 1) if s.e1 < s.E_total else 0
                 try:
                     pa, plan = s.eng.prepare_blocked_dyn(
-                        np.ascontiguousarray(s.ep_start[s.e0:look + 1]), np.ascontiguousarray(s.Pall[s.e0:look + 1]),
-                        lag=lag, timeout_s=timeout_s, start_iter=s.start_iter, pending_in=s.pending_in,
-                        hard_stop=s.hard_stop, cont=s.cont)
+                        np.ascontiguousarray(starts), np.ascontiguousarray(chains), lag=lag, timeout_s=timeout_s,
+                        start_iter=start_iter, pending_in=pending_in, hard_stop=hard_stop, cont=cont)
                 except ValueError as e:
                     raise ValueError("sweep member %d: %s" % (i, e))
                 batch[slot] = pa
@@ -222,8 +173,7 @@ class DynSweepEngine(SweepEngineBase):
                 s = state[i]
                 done, conv, nxt = c[1], c[2], c[0]
                 s.rounds += 1
-                s.done = done
-                last_it = conv if done in (1, 2, 3) else s.hard_stop  # the last iteration decided in this round
+                last_it = conv if done in (1, 2, 3) else s.cur.hard_stop  # the last iteration decided in this round
                 if not 1 <= last_it <= s.eng.trace.numel():
                     s.stop_tick = 0
                 elif s.fetch:
@@ -231,31 +181,19 @@ class DynSweepEngine(SweepEngineBase):
                 else:  # a trace too long for the one-copy read-back: this stamp alone (a blocking 8-byte copy)
                     s.stop_tick = int(s.eng.tstamp[last_it - 1:last_it].cpu().item())
                 ticks.append(s.stop_tick)
-                if done == 5:  # ran to its hard stop: the next round continues it with the same tag salt
-                    s.last_launched = s.hard_stop
-                    s.start_iter, s.pending_in, s.cont = s.hard_stop + 1, 1, True
-                    s.e0 = s.e1 - 1  # epoch 0 of the next launch: this chunk's last (the pending duals' flush)
-                    s.chunk = min(2 * s.chunk, s.cap)
-                    nxt_live.append(i)
-                elif done in (1, 2, 3):
-                    s.iters = conv
-                    s.last_launched = nxt - 1
-                else:
-                    raise RuntimeError("D-GADMM chunk of member %d ended without an outcome (hard stop %d)"
-                                       % (i, s.hard_stop))
+                if s.cur.advance(done, conv, nxt - 1, " of member %d" % i):
+                    nxt_live.append(i)  # ran to its hard stop: the next round continues it with the same tag salt
             round_end.append(max(ticks))
             self.last_round_ms.append((time.perf_counter() - t0) * 1e3)
             live = nxt_live
         self.last_wall_ms = float(sum(self.last_round_ms))
         out = []
         for s in state:
-            hints = s.eng.__dict__.setdefault("_dyn_epoch_hint", {})
-            starts = s.ep_start[:s.n_drawn]
-            hints[s.hint_key] = int(np.searchsorted(starts, max(s.last_launched, 1), side="right"))
+            c = s.cur
+            c.finish()
             end = round_end[s.rounds - 1]
-            out.append(DynSweepRun(iters=s.iters, done=s.done, rounds=s.rounds, slot=s.slot, placed=s.placed,
-                                   last_launched=s.last_launched,
+            out.append(DynSweepRun(iters=c.iters, done=c.done, rounds=s.rounds, slot=s.slot, placed=s.placed,
+                                   last_launched=c.last_launched,
                                    tail_ticks=max(end - s.stop_tick, 0) if s.stop_tick > 0 else 0,
-                                   starts=starts, paths=s.Pall[:s.n_drawn], costs=s.costs,
-                                   cost0=np.asarray(s.saved[2]), span=int(s.ep_start[s.n_drawn] - 1) if s.n_drawn < s.E_total else int(s.eng.max_iter)))
+                                   starts=c.starts, paths=c.paths, costs=c.costs, cost0=c.cost0, span=c.span, cursor=c))
         return out

@@ -319,6 +319,42 @@ def test_epoch_chunks_per_worker(n, m, d, coh, monkeypatch):
     _report("D-GADMM per-worker epoch_chunk=2 (%d launches) %s coh %d" % (launches, (n, m, d), coh), out)
 
 
+def test_cached_engine_early_draw_and_hint(lin24, lin_obj0, monkeypatch):
+    """Repeats on the model's cached engine: the second solve draws its first launch's chains early and
+    sizes that launch from the epochs the first one reached, the third draws them synchronously
+    (GADMM_DGADMM_EARLY=0). All three == the epoch-by-epoch engine, bit for bit."""
+    from gadmm_amd.algorithms import dynamic_group_admm
+    from gadmm_amd.models import LinearRegression
+    from gadmm_amd.parallel import topology as T
+    m = LinearRegression(lin24.X.to("cuda"), lin24.y.to("cuda"))
+    p0, c0, _ = T.find_path(24, np.random.default_rng(5))
+    run = lambda **o: dynamic_group_admm(m, 1.0, lin_obj0, 1e-4, 3000, p0, c0, 10, seed=99, engine_opts=o)  # noqa: E731
+    ref = run(persistent=False, cache=False)
+    assert ref.extra["engine"] == "epochs" and ref.converged and getattr(m, "_chain_engines", None) is None
+    early = []
+    inner = T.PathSchedule.prefetch_async
+    monkeypatch.setattr(T.PathSchedule, "prefetch_async", lambda self, count: early.append(count) or inner(self, count))
+    calls = _count_launches(monkeypatch)
+    first = run()
+    assert early == [] and len(m._chain_engines) == 1  # a new engine: nothing to overlap the draw with
+    eng = first.extra["engine_obj"]
+    reached = dict(eng._dyn_epoch_hint)
+    (epochs,) = reached.values()
+    assert calls == [1279] and 16 <= epochs + 8 < 128, (calls, reached)  # 128 epochs: the hard stop before iteration 1280
+    second = run()
+    # one launch of the epochs the first solve reached + 8 (epoch e starts at iteration 10 e), drawn early
+    assert calls == [1279, 10 * (epochs + 8) - 1] and early == [epochs + 8], (calls, early, reached)
+    monkeypatch.setenv("GADMM_DGADMM_EARLY", "0")
+    third = run()
+    assert len(early) == 1 and eng._dyn_epoch_hint == reached
+    for r in (first, second, third):
+        assert r.extra["engine"] == "persistent-dynamic" and r.extra["engine_obj"] is eng
+        assert r.iters == ref.iters and r.converged
+        assert np.array_equal(r.obj, ref.obj) and np.array_equal(r.com_cost, ref.com_cost)
+    assert len(m._chain_engines) == 1
+    eng.close()
+
+
 # ------------------------------------------------------------------------------------------------
 # Epoch by epoch (engine_opts["persistent"] = False): the phase kernels up to the iteration before a
 # re-chain, flush_duals with the old chain, set_path, on. gadmm_chain_phase (chain_small.hip) takes
