@@ -7,6 +7,7 @@ margins make the comparison meaningful, and the mixed sweep.
 How far the counts of a censored run are determined by the specification is in the docstring of
 tests/test_cqgadmm_cpu.py: the decisions of the first 80 iterations on the shipped data are (every
 rounding of the local solve agrees on them), the iteration of the stop is not.
+The independent long-double reference of whole censored runs is in tests/test_gpu_cqgadmm_classes.py.
 
 Run with: pytest -m gpu tests/test_gpu_cqgadmm.py
 """

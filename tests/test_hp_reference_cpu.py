@@ -980,6 +980,211 @@ def test_qgadmm_bound_rejects_a_missing_clamp(n, m, d, bits, path):
 
 
 # ------------------------------------------------------------------------------------------------
+# CQ-GADMM (tests/test_gpu_cqgadmm_classes.py). A censored run is comparable only while neither a code
+# nor a censoring decision can flip, and it tests censoring only if censoring happens: the conditions on
+# the reference alone for every case, the zero table against the Q recurrence, the decisions against the
+# specification, and the power of the GPU comparison against six wrong variants of the censored part.
+CQGADMM_CASES = H.cqgadmm_cases()
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", CQGADMM_CASES)
+def test_cqgadmm_case_qualifies(n, m, d, bits, path):
+    """Conditions (a)-(d) of ``cqgadmm_condition`` hold for the case's ``(seed, tau0, xi)`` over the
+    longest run a GPU test asks for; ``tau0`` is the derived one (``cq_tau0``); every combination earlier
+    in ``cq_search_order`` fails them; a shorter run is a prefix."""
+    seed, tau0, xi = H.cqgadmm_censor(n, m, d, bits, path)
+    run = H.qgadmm_run_length(d)
+    assert H.QGADMM_FIRST_SEED <= seed <= H.QGADMM_LAST_SEED and xi in H.CQGADMM_XI
+    assert tau0 == H.cq_tau0(n, m, d, bits, seed, xi, path) and len(("%r" % tau0).replace(".", "").strip("0")) <= 2
+    c = H.cqgadmm_condition(n, m, d, bits, path, seed, tau0, xi)
+    ref = H.cqgadmm_case(n, m, d, bits, run, path)[3]
+    print("CQ-GADMM %s b=%d chain %s (seed %d, tau0 %g, xi %g), %d iterations: agree %s, flip margin %.3g b_theta, "
+          "censor margin %.3g = %.3g b_s, %d of %d sent" % ((n, m, d), bits, path, seed, tau0, xi, run, c["agree"], c["flip"],
+                                                           ref.cmargin, c["censor"], ref.sent.sum(), ref.sent.size))
+    assert c["agree"] and ref.codes_agree and ref.sent_agree                       # (a)
+    assert ref.margin >= H.QGADMM_MARGIN * ref.b_theta                            # (b)
+    assert ref.cmargin >= H.QGADMM_MARGIN * ref.b_s                               # (c)
+    for upto in (H.QGADMM_PERSISTENT_K, H.K_ITERS):                               # (d)
+        pat = H.cq_pattern(ref.sent, path, upto)
+        assert set(pat) == {"censored-head", "sent-head", "censored-tail", "sent-tail", "mixed", "stale"}
+        assert all(pat.values()), (upto, pat)
+    assert c["ok"] and ref.sent.shape == (run, n) and ref.s.dtype == H.LD and ref.censor == (tau0, xi)
+    assert np.array_equal(ref.codes[~ref.sent], np.full(((~ref.sent).sum(), d), -1)) and (ref.codes[ref.sent] >= 0).all()
+    for earlier in H.cq_search_order(n, m, d, bits, path):
+        if earlier == (seed, tau0, xi):
+            break
+        e = H.cqgadmm_condition(n, m, d, bits, path, *earlier)
+        print("   earlier %r: agree %s flip %.3g censor %.3g missing %s" % (earlier, e["agree"], e["flip"], e["censor"], e["missing"]))
+        assert not e["ok"]
+    short = H.cqgadmm_case(n, m, d, bits, H.QGADMM_PERSISTENT_K, path)[3]
+    assert np.array_equal(short.sent, ref.sent[:H.QGADMM_PERSISTENT_K]) and short.cmargin >= ref.cmargin
+    assert np.array_equal(short.last_sent, H.cq_last_sent(ref.sent)[H.QGADMM_PERSISTENT_K - 1])
+
+
+def test_cqgadmm_cases_and_dropped_pairs():
+    """Every case of the Q module has its entry, but for at most two dropped (shape, bits) pairs, none at
+    d in {16, 17, 52, 53, 64, 65, 128, 129, 256}, each with truly no combination that qualifies (none is
+    dropped). (e): a graph case has, in iteration K_ITERS, a censored worker next to a sent one: the
+    message-table check of the GPU tests sees both kinds."""
+    dropped = H.CQGADMM_DROPPED
+    assert len(dropped) <= 2
+    for (n, m, d), bits in dropped:
+        assert d not in (16, 17, 52, 53, 64, 65, 128, 129, 256)
+        assert not any(H.cqgadmm_condition(n, m, d, bits, None, *c)["ok"] for c in H.cq_search_order(n, m, d, bits))
+    assert set(H.CQGADMM_CASES) == {c for c in H.qgadmm_cases() if (c[:3], c[3]) not in dropped}
+    both = 0
+    for n, m, d in H.QGADMM_GRAPH_SHAPES:
+        for bits in H.QGADMM_BITS:
+            if ((n, m, d), bits) not in dropped:
+                last = H.cqgadmm_case(n, m, d, bits, K)[3].sent[-1]
+                both += bool(last.any() and not last.all())
+    print("CQ-GADMM: %d graph cases with a censored and a sent worker in iteration %d" % (both, K))
+    assert both >= 1
+
+
+def test_cq_pattern_on_hand_made_traces():
+    s = np.array([[1, 1, 1], [1, 0, 0], [0, 1, 1], [1, 1, 0]], dtype=bool)
+    assert all(H.cq_pattern(s, None, 4).values())
+    assert H.cq_pattern(s, None, 2) == {"censored-head": True, "sent-head": True, "censored-tail": True, "sent-tail": True,
+                                        "mixed": True, "stale": False}   # iteration 2: the tail's heads differ
+    assert not H.cq_pattern(s, None, 1)["mixed"] and not H.cq_pattern(s, None, 1)["censored-tail"]
+    assert H.cq_pattern(s, None, 3)["stale"]
+    assert not H.cq_pattern(s[:, :2], None, 2)["stale"] and H.cq_pattern(s[:, :2], None, 2)["mixed"]   # N = 2
+    # roles follow the chain position: worker 0 is a tail of (1, 0, 2), between the heads 1 and 2
+    t = np.array([[1, 0, 1], [1, 1, 1]], dtype=bool)
+    assert not H.cq_pattern(t, None, 2)["mixed"] and H.cq_pattern(t, (1, 0, 2), 2)["mixed"]
+    assert H.cq_pattern(t, None, 2)["censored-tail"] and not H.cq_pattern(t, (1, 0, 2), 2)["censored-tail"]
+    # an interior head solves iteration k + 1 on the tails' decisions of iteration k
+    h = np.array([[1, 1, 1, 1], [1, 1, 1, 0], [1, 1, 1, 1]], dtype=bool)
+    assert not H.cq_pattern(h, None, 2)["mixed"] and H.cq_pattern(h, None, 3)["mixed"]
+    assert np.array_equal(H.cq_last_sent(s), [[1, 1, 1], [2, 1, 1], [2, 3, 3], [4, 4, 3]])
+    assert np.array_equal(H.cq_last_sent(np.zeros((3, 2), dtype=bool)), np.zeros((3, 2)))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, H.LD])
+@pytest.mark.parametrize("n,m,d,bits,path", [(3, 7, 3, 8, None), (3, 20, 9, 16, None), (4, 30, 16, 8, (3, 2, 1, 0)),
+                                             (3, 80, 65, 4, None)])
+def test_cqgadmm_zero_table_is_qgadmm(n, m, d, bits, path, dtype):
+    """tau0 = 0: everybody always sends and every output of the censored recurrence equals
+    ``qgadmm_linear`` exactly, in either dtype; without ``censor`` the function returns what it did."""
+    X, y, rho = H.make_linear(n, m, d, H.seed_of(n, m, d))
+    seed = H.qgadmm_seed(n, m, d, bits, path)[0]
+    q = H.qgadmm_linear(X, y, rho, K, bits, seed, path, dtype)
+    c = H.qgadmm_linear(X, y, rho, K, bits, seed, path, dtype, censor=(0.0, 0.9))
+    assert len(q) == 8 and len(c) == 11
+    for a, b in zip(q, c[:8]):
+        assert np.array_equal(a, b) and np.asarray(a).dtype == np.asarray(b).dtype
+    assert c[8].all() and c[8].shape == (K, n) and c[9].dtype == dtype and (c[9] > 0).all() and c[10] == np.inf
+    if dtype is H.LD:   # the cached Q case is the same run
+        ref = H.qgadmm_case(n, m, d, bits, K, path)[3]
+        assert np.array_equal(ref.theta, c[0]) and np.array_equal(ref.codes, c[4]) and np.array_equal(ref.obj, c[3])
+
+
+def _cq_rows(n, m, d, bits, path, run):
+    """The float64 run of a case as rows: ``(theta, th_hat before the worker's step, candidate)``, each
+    (run, N, d) -- the candidate recomputed with ``q_line`` -- and ``(thr, thr2, sent, s)``."""
+    seed, tau0, xi = H.cqgadmm_censor(n, m, d, bits, path)
+    h = H._cqgadmm_history(n, m, d, bits, seed, path, H.qgadmm_run_length(d), np.float64, (tau0, xi))
+    theta, hats, sent, s = h[3][:run], h[4][:run], h[11][:run], h[12][:run]
+    prev = np.concatenate([np.zeros_like(hats[:1]), hats[:-1]])
+    cand = np.zeros_like(theta)
+    for k in range(run):
+        for w in range(n):
+            cand[k, w] = H.q_line(theta[k, w], prev[k, w], H.q_uniforms(seed, k + 1, n, w, d), bits, np.float64)[2]
+    thr, thr2 = H.cq_thresholds(tau0, xi, run)
+    return theta, prev, cand, thr, thr2, sent, s
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", [(2, 3, 1, 8, None), (3, 20, 5, 16, None), (4, 40, 64, 4, None),
+                                             (3, 80, 65, 8, None), (3, 280, 256, 16, None),
+                                             (5, 40, 33, 8, (2, 0, 4, 1, 3))])
+def test_cqgadmm_decisions_are_the_specification(n, m, d, bits, path):
+    """Two restatements, one specification: on the (K, N) candidate rows of the float64 run
+    ``quantize.censor_rows`` takes the reference's decisions, against the same table bit for bit
+    (``censor_thresholds``); its ``s`` (the kernels' summation order) sits within the censor margin's
+    noise of the reference's; a sent row moved to the candidate, a censored one stayed."""
+    from gadmm_amd.algorithms import quantize as Q
+    seed, tau0, xi = H.cqgadmm_censor(n, m, d, bits, path)
+    theta, prev, cand, thr, thr2, sent, s = _cq_rows(n, m, d, bits, path, K)
+    ref = H.cqgadmm_case(n, m, d, bits, K, path)[3]
+    assert np.array_equal(thr2.view(np.uint64), Q.censor_thresholds(tau0, xi, K).view(np.uint64))
+    assert np.array_equal(thr2, ref.thr2) and thr2.dtype == np.float64 and thr2[0] == tau0 * tau0
+    for k in range(K):
+        send, s_spec, margin = Q.censor_rows(cand[k], prev[k], thr2[k + 1])
+        assert np.array_equal(send, sent[k]) and np.array_equal(send, ref.sent[k]), k
+        assert np.max(np.abs(s_spec - s[k]) / thr2[k + 1]) <= ref.b_s and margin >= H.QGADMM_MARGIN * ref.b_s
+    after = np.asarray(H._cqgadmm_history(n, m, d, bits, seed, path, H.qgadmm_run_length(d), np.float64, (tau0, xi))[4][:K])
+    assert np.array_equal(after[sent], cand[sent]) and np.array_equal(after[~sent], prev[~sent])
+
+
+def _cq_comparison(ref, run, upto, residual=False):
+    """What tests/test_gpu_cqgadmm_classes.py holds a kernel to, applied to ``run`` (the outputs of a
+    censored ``_qgadmm_run``) after ``upto`` iterations: the sent trace, the last message of every worker
+    sent in iteration ``upto`` (codes exactly, R under its bound), the objective trace, true theta, th_hat
+    and the duals (and the K4 residual trace) under theirs. ``(fails, largest err / bound, decisions that
+    differ)``; ``ref`` is the case's reference at ``upto`` iterations."""
+    th, hats, mus, obj, codes, Rs, res, _, sent = run[:9]
+    flips = int(np.sum(sent[:upto] != ref.sent))
+    now = ref.sent[-1]
+    codes_ok = np.array_equal(codes[upto - 1][now], ref.codes[-1][now])
+    ratios = {"objective": ref.err_obj(obj[:upto]) / ref.b_obj, "theta_true": ref.err_theta(th[upto - 1]) / ref.b_theta,
+              "th_hat": ref.err_hat(hats[upto - 1]) / ref.b_hat, "dual": ref.err_dual(mus[upto - 1]) / ref.b_dual}
+    if now.any():
+        ratios["R"] = H.noise_level(ref.R[-1][now], Rs[upto - 1][now], ref.scale_theta) / ref.b_R
+    if residual:
+        ratios["residual"] = ref.err_res(res[:upto]) / ref.b_res
+    worst = max(ratios.values())
+    return bool(flips or not codes_ok or not worst <= 1.0), worst, flips
+
+
+def _cq_can_act(mutant, n, m, d, bits, path, upto):
+    """Can the mutation change anything within ``upto`` iterations of the case? A condition on the
+    reference's float64 run alone. The three that change the DECISION act when their rule, on the rows of
+    the reference, decides otherwise somewhere; the others need a censored worker (a censored tail)."""
+    theta, prev, cand, thr, thr2, sent, s = _cq_rows(n, m, d, bits, path, upto)
+    tails = (list(range(n)) if path is None else list(path))[1::2]
+    if mutant in ("censored-moves", "residual-candidate"):
+        return bool(((~sent) & (cand != prev).any(axis=2)).any())
+    if mutant == "dual-candidate":
+        return bool(((~sent[:, tails]) & (cand != prev).any(axis=2)[:, tails]).any())
+    if mutant == "s-true":
+        step = theta - prev
+        other = np.array([[np.sum(step[k, w] * step[k, w]) for w in range(n)] for k in range(upto)]) >= thr2[1:, None]
+    elif mutant == "thr-index":
+        other = s >= thr2[:-1, None]
+    else:
+        assert mutant == "thr-unsquared"
+        other = s >= thr[1:, None]
+    return bool((other != sent).any())
+
+
+@pytest.mark.parametrize("n,m,d,bits,path", CQGADMM_CASES)
+def test_cqgadmm_comparison_rejects_a_wrong_variant(n, m, d, bits, path):
+    """Power of the GPU tests, on the reference alone: the float64 run of each of the six wrong variants
+    of the censored part goes through the comparison the GPU tests apply (``_cq_comparison``) after
+    QGADMM_PERSISTENT_K and after K_ITERS iterations -- the two lengths the GPU tests stop at (the K4
+    residual is held at four of the cases there; here every case carries it) -- and fails it wherever
+    the mutation can act at all (``_cq_can_act``); the float64 run of the recurrence itself passes. No
+    number is asserted beyond "fails": the smallest excess of every variant is printed, and recorded in
+    profiles/cqgadmm_classes/README.md."""
+    seed, tau0, xi = H.cqgadmm_censor(n, m, d, bits, path)
+    run = H.qgadmm_run_length(d)
+    for upto in (H.QGADMM_PERSISTENT_K, K):
+        ref = H.cqgadmm_case(n, m, d, bits, upto, path)[3]
+        own = H._cqgadmm_history(n, m, d, bits, seed, path, run, np.float64, (tau0, xi))[3:]
+        fails, worst, flips = _cq_comparison(ref, own, upto, residual=True)
+        assert not fails and worst <= 1.0 / 8 and flips == 0
+        for mutant in H.CQGADMM_MUTANTS:
+            acts = _cq_can_act(mutant, n, m, d, bits, path, upto)
+            out = H._cqgadmm_history(n, m, d, bits, seed, path, run, np.float64, (tau0, xi), mutant)[3:]
+            fails, worst, flips = _cq_comparison(ref, out, upto, residual=mutant == "residual-candidate")
+            print("CQ-GADMM %s b=%d chain %s %2d iterations mutant %-18s: acts %-5s fails %-5s decisions that differ %3d, "
+                  "largest err/bound %.2e" % ((n, m, d), bits, path, upto, mutant, acts, fails, flips, worst))
+            assert fails or not acts, (mutant, upto, worst, flips)
+            assert acts or not fails   # where it cannot act it is the recurrence
+
+
+# ------------------------------------------------------------------------------------------------
 # K4 primal residual (the "K4 primal residual" sections of tests/test_gpu_dispatch_classes.py and
 # tests/test_gpu_newton_classes.py, and every solve of tests/test_gpu_dgadmm_classes.py): a function of
 # the theta history the references already hold (``chain_residual``). The condition that entitles the
