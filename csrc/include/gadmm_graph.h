@@ -3,6 +3,7 @@
 // worker local. The specification is gadmm_amd/algorithms/ggadmm.py.
 #pragma once
 #include "gadmm_chain.h"
+#include "gadmm_logi.h"
 
 // Arguments of one launch (passed by value; every pointer is a device address). Per-worker arrays are
 // indexed by worker id; the launch order (workgroup b runs worker wid[b]) is the heads in ascending
@@ -45,4 +46,14 @@ struct GraphQArgs {
   int q_bits, q_pad;               // 4, 8 or 16
   unsigned long long q_seed;
   double* q_true;                  // optional [n][d] out: the TRUE iterates (theta receives the public models)
+};
+
+// Logistic GGADMM with inner-GD local solves (csrc/kernels/graph_persistent_logistic.hip): the same launch
+// with the shards instead of the Gram form. GraphArgs comes first, unchanged; Minv, A, b and yy are not
+// read and may be null. LogiArgs as in the chain's logistic kernels, its per-worker arrays by worker id:
+// X [n][m][d], Y [n][m], inner_iters [n] (each worker's step count of its last local solve); scratch is
+// not read.
+struct GraphLogiArgs {
+  GraphArgs g;
+  LogiArgs l;
 };

@@ -39,6 +39,28 @@ Two executions: ``backend='torch'``, a batched loop in the style of the chain's 
 that path on a chain graph), and the native persistent kernel on one HIP device
 (engine/graph_engine.py, csrc/kernels/graph_persistent.hip; quantized: csrc/kernels/graph_quant.hip). The linear model with closed-form solves,
 one process, every worker local; anything else raises ``NotImplementedError``.
+
+Logistic GGADMM, ``graph_admm_logistic``: the logistic model (``models.LogisticRegression``, worker n holds
+shard ``X_n``, ``y_n``) with the reference's inexact local solver, at most ``max_inner`` gradient steps of
+size ``step`` on the local loss plus a proximal shift ``s`` frozen at the pre-update iterate. Each line one
+rounded float64 operation per coordinate, in this order:
+
+    heads, all at once:  x0 = theta_n^{it-1};  s = mu_n;  for k in N(n): s = s + rho (x0 - theta_k)
+                         (the tails' theta^{it-1}; s stays frozen during the local solve)
+                         x = x0; at most max_inner times:
+                             z = X_n x;  v = y / (1 + exp(y z));  g = -X_n^T v + lam x + s;  xn = x - step g
+                             x = xn; stop after the first step in which every |xn - x_old| < inner_tol (strict)
+                         theta_n = x
+    tails, all at once:  the same with the heads' theta^{it}
+    every worker:        for k in N(n): mu_n = mu_n + rho (theta_n - theta_k)
+    objective            sum_n [lam/2 |theta_n|^2 + sum_i softplus(-y_i x_i^T theta_n)] in worker order
+    stop rule            |objective - obj0| < tol
+    primal residual      sum over edges |theta_h - theta_t|^2 (each edge once; its tail owns it)
+
+On a chain graph this is ``chain_admm(local_solver="gd")``'s torch path bit for bit (``m - rho (tl - th)`` and
+``m + rho (th - tl)`` are the same float64 value). Accounting as GGADMM's. Two executions likewise: the
+batched torch loop and the native persistent kernel for ``max(d, m) <= 64`` (engine/graph_logistic_engine.py,
+csrc/kernels/graph_persistent_logistic.hip). ``graph_admm`` itself keeps refusing a logistic model.
 """
 from __future__ import annotations
 
@@ -126,6 +148,59 @@ def graph_admm(model, graph: BipartiteGraph, rho: float, obj0: float, tol: float
 generalized_group_admm = graph_admm
 
 
+def graph_admm_logistic(model, graph: BipartiteGraph, rho: float, obj0: float, tol: float, max_iter: int, step: float,
+                        max_inner: int = 100, inner_tol: float = 1e-4, backend: str = "auto",
+                        name: str = "GGADMM-logistic", engine_opts: Optional[dict] = None, record_theta: bool = False,
+                        comm=None) -> RunResult:
+    """One logistic GGADMM solve (module docstring) of ``model``, a ``LogisticRegression`` whose shard n
+    belongs to worker n, over ``graph``: inner-GD local solves of at most ``max_inner`` steps of size ``step``,
+    stopped after the first step in which every coordinate moved less than ``inner_tol``.
+
+    ``backend`` / ``engine_opts`` / ``record_theta`` / ``comm``: as ``graph_admm``; the native kernel takes
+    ``max(d, m) <= 64``, and the torch path's reason in ``extra['graph_fallback']`` is one of ``max(d, m) > 64``,
+    the LDS staging, residency, a hand-off timeout, ``cpu tensors`` or ``native library unavailable``. The torch
+    path returns ``extra['state'] = (theta, mu, next_iter)`` and ``extra['inner_steps_mean']``."""
+    if not isinstance(graph, BipartiteGraph):
+        raise TypeError("graph_admm_logistic: graph must be a BipartiteGraph (parallel.topology)")
+    if getattr(model, "kind", None) != "logistic":
+        raise NotImplementedError("graph_admm_logistic: the logistic model (models.LogisticRegression) only "
+                                  "(got model kind %r)" % getattr(model, "kind", None))
+    if comm is not None and getattr(comm, "nranks", 1) != 1:
+        raise NotImplementedError("graph_admm_logistic: one process, every worker local (got %d ranks)" % comm.nranks)
+    if int(model.n_local) != graph.n:
+        raise NotImplementedError("graph_admm_logistic: every worker local -- the model holds %d shards, the graph "
+                                  "has %d workers" % (int(model.n_local), graph.n))
+    if backend not in ("auto", "torch", "native"):
+        raise ValueError("unknown backend %r" % backend)
+    gd = (float(step), int(max_inner), float(inner_tol))
+    why = None
+    if backend == "torch":
+        why = "torch backend"
+    elif model.device.type != "cuda":
+        why = "cpu tensors"
+    elif max(model.d, model.m) > 64:
+        why = "max(d, m) > 64"
+    else:
+        from ..ops import native
+        if not native.available():
+            why = "native library unavailable"
+    if why is None:
+        res, why = _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, dict(engine_opts or {}), gd=gd)
+        if res is not None:
+            if record_theta:
+                res.theta = res.extra["engine_obj"].theta.cpu().numpy()
+            return res
+    if backend == "native":
+        raise RuntimeError("graph_admm_logistic: the native backend does not cover this case (%s)" % why)
+    res = _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta, gd=gd)
+    if backend != "torch":
+        res.extra["graph_fallback"] = why
+    return res
+
+
+generalized_group_admm_logistic_gd = graph_admm_logistic
+
+
 def quantized_graph_admm(model, graph: BipartiteGraph, rho: float, obj0: float, tol: float, max_iter: int, bits: int,
                          seed: int = 1234, **kw) -> RunResult:
     """Q-GGADMM: ``graph_admm(..., quantize=(bits, seed))`` under its own name."""
@@ -146,7 +221,9 @@ def _padded_neighbours(graph: BipartiteGraph, workers, dev):
     return out
 
 
-def _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta, quant=None) -> RunResult:
+def _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta, quant=None, gd=None) -> RunResult:
+    """The batched loop of both specifications. ``gd``: ``(step, max_inner, inner_tol)`` -- the logistic
+    model's inexact local solve instead of the closed form."""
     n, d, dev = graph.n, model.d, model.device
     theta = torch.zeros((n, d), dtype=torch.float64, device=dev)  # quantized: the table of PUBLIC models
     mu = torch.zeros((n, d), dtype=torch.float64, device=dev)
@@ -164,12 +241,21 @@ def _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta
     eh = torch.tensor([e[0] for e in graph.edges], dtype=torch.long, device=dev)
     et = torch.tensor([e[1] for e in graph.edges], dtype=torch.long, device=dev)
     ids = list(range(n))
+    inner_used = []
     comm = LocalComm()
     stop = Stopper(obj0, tol, max_iter)
     primal = []
     iters, converged = max_iter, False
     for it in range(1, max_iter + 1):
         for li, deg, nbs in groups:  # heads (the tails' theta of the last iteration), then tails
+            if gd is not None:
+                x0 = theta.index_select(0, li)
+                shift = mu.index_select(0, li)
+                for idx, mask in nbs:
+                    shift = shift + rho * (x0 - theta.index_select(0, idx)) * mask
+                theta[li], used = model.inexact_gd(li, x0, shift, gd[0], gd[1], gd[2])
+                inner_used.append(float(used.double().mean()))
+                continue
             rhs = model.b.index_select(0, li) - mu.index_select(0, li)
             for idx, mask in nbs:
                 rhs = rhs + rho * (theta.index_select(0, idx) * mask)
@@ -206,9 +292,11 @@ def _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta
                     comm_units=np.arange(1, n_it + 1, dtype=np.float64) * n, com_cost=np.zeros(n_it),
                     bytes_sent=0, bytes_total=0, primal_res=np.asarray(primal),
                     extra={"backend": "torch", "engine": "torch", "kernel": "torch", "rank": 0, "nranks": 1,
-                           "solver": "closed", "monitor_bytes": 0, "transport": "local",
+                           "solver": "closed" if gd is None else "gd", "monitor_bytes": 0, "transport": "local",
                            "graph": graph.describe(), "deliveries": done_it * 2 * len(graph.edges)})
     res.extra["state"] = (theta, mu, done_it + 1)
+    if gd is not None:
+        res.extra["inner_steps_mean"] = float(np.mean(inner_used)) if inner_used else 0.0
     if quant is not None:
         from .gadmm import _quant_accounting
         _quant_accounting(res, quant[0], quant[1], n, d)
@@ -219,18 +307,26 @@ def _graph_admm_torch(model, graph, rho, obj0, tol, max_iter, name, record_theta
     return res
 
 
-def _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, opts, quant=None):
+def _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, opts, quant=None, gd=None):
     """``(RunResult, None)`` from the persistent kernel, or ``(None, reason)`` when the engine refuses
-    the shape, the launcher the residency, or a hand-off timed out."""
+    the shape, the launcher the residency, or a hand-off timed out. ``gd``: ``(step, max_inner, inner_tol)``
+    -- the logistic kernel (engine/graph_logistic_engine.py)."""
     from ..engine.chain_engine import HandoffTimeout, ResidencyError
-    from ..engine.graph_engine import NativeGraphEngine
 
     xcd = int(opts.get("xcd", 2))
     residual = bool(opts.get("residual", True))
-    key = ("graph", graph.key(), float(rho), int(max_iter), xcd, residual) + (() if quant is None else quant)
-    eng, fresh = cached_engine(model, key, lambda: NativeGraphEngine(
-        model.X, model.y, graph, rho, obj0, tol, max_iter, precomputed=(model.A, model.b, model.yy), xcd=xcd,
-        residual=residual, quant=quant), (obj0, tol), opts.get("cache", True))
+    if gd is not None:
+        from ..engine.graph_logistic_engine import NativeGraphLogisticEngine
+        key = ("graph-logistic", graph.key(), float(rho)) + tuple(gd) + (int(max_iter), xcd, residual)
+        eng, fresh = cached_engine(model, key, lambda: NativeGraphLogisticEngine(
+            model.X, model.y, graph, rho, obj0, tol, max_iter, model.lam, gd[0], gd[1], gd[2], xcd=xcd,
+            residual=residual), (obj0, tol), opts.get("cache", True))
+    else:
+        from ..engine.graph_engine import NativeGraphEngine
+        key = ("graph", graph.key(), float(rho), int(max_iter), xcd, residual) + (() if quant is None else quant)
+        eng, fresh = cached_engine(model, key, lambda: NativeGraphEngine(
+            model.X, model.y, graph, rho, obj0, tol, max_iter, precomputed=(model.A, model.b, model.yy), xcd=xcd,
+            residual=residual, quant=quant), (obj0, tol), opts.get("cache", True))
     why = eng.refusal()
     if why is not None:
         return None, why
@@ -239,8 +335,8 @@ def _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, opts, quant
         torch.cuda.synchronize(model.device)  # a new engine's set-up is complete before the solve
     t0 = time.perf_counter()
     try:
-        with roctx_range("%s native-graph%s N=%d E=%d" % (name, "" if quant is None else "-Q", graph.n,
-                                                          len(graph.edges))):
+        with roctx_range("%s native-graph%s N=%d E=%d" % (
+                name, "-logistic" if gd is not None else "" if quant is None else "-Q", graph.n, len(graph.edges))):
             r = eng.run(fetch_trace=True, timeout_s=float(opts.get("timeout_s", 20.0)))
     except ResidencyError as e:
         return None, "ResidencyError: %s" % e
@@ -253,7 +349,7 @@ def _graph_admm_native(model, graph, rho, obj0, tol, max_iter, name, opts, quant
                     time_trace=tt, comm_units=np.arange(1, iters + 1, dtype=np.float64) * graph.n,
                     com_cost=np.zeros(iters), bytes_sent=0, bytes_total=0, primal_res=eng.primal_residual(iters),
                     extra={"backend": "native", "engine": "persistent", "kernel": eng.last_kernel, "rank": 0,
-                           "nranks": 1, "solver": "closed", "monitor_bytes": 0, "wire_bytes": 0,
+                           "nranks": 1, "solver": "closed" if gd is None else "gd", "monitor_bytes": 0, "wire_bytes": 0,
                            "transport": "local", "placed": int(eng.last_placed), "engine_obj": eng,
                            "graph": graph.describe(), "deliveries": iters * 2 * len(graph.edges)})
     if quant is not None:

@@ -55,7 +55,7 @@ class ExperimentConfig:
     # CQ-GADMM (censoring on top of Q-GADMM): ``censor=tau0,xi`` with ``quant_bits`` adds one
     # ``CQ-GADMM_b{bits}_rho{rho}`` run next to every Q run; empty = none
     censor: List[float] = field(default_factory=list)
-    # GGADMM (entry LinearRegression_Topologies): the bipartite graphs to solve on, as
+    # GGADMM (entries LinearRegression_Topologies, LogisticRegression_Topologies): the bipartite graphs to solve on, as
     # ``parallel.topology.parse_graph`` names them ("chain", "ring", "grid:RxC", "star[:hub]", "kbip")
     graphs: List[str] = field(default_factory=list)
 
@@ -109,6 +109,12 @@ PRESETS = {
         gadmm_iters=3000, rhos=[3.0], acc=1e-4, graphs=["chain", "ring", "grid:4x6", "star:0", "kbip"],
         run_baselines=False, run_dualavg=False,
         reference="beyond the reference: GGADMM (arXiv:2009.06459) on the data of LinearRegression_Synthetic.m"),
+    "LogisticRegression_Topologies": ExperimentConfig(
+        name="LogisticRegression_Topologies", model="logistic", data="logistic_synthetic", num_workers=24,
+        gadmm_iters=400, rhos=[2e-4], acc=1e-4, lam=1e-5, gd_step=2.2,
+        graphs=["chain", "ring", "grid:4x6", "star:0", "kbip"], run_baselines=False, run_dualavg=False,
+        reference="beyond the reference: GGADMM (arXiv:2009.06459) with the local solver of logReg_GD.m on the "
+                  "data of LogisticRegression_Synthetic.m"),
 }
 
 

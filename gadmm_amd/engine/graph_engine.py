@@ -34,6 +34,7 @@ class NativeGraphEngine:
     model = "linear"         # what a sweep (engine/sweep_base.py) asks of a member: a one-GPU linear solve
     nranks = 1
     obj_mode_name = "exact"  # the objective the monitor sums is the true one
+    Minv = A = b = yy = None  # the closed-form launch's inputs: a subclass with another local solve leaves them unset
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, graph, rho: float, obj0: float, tol: float, max_iter: int,
                  precomputed=None, xcd: int = 2, residual: bool = True, quant=None, stream=None, inverses=None):
@@ -56,19 +57,8 @@ class NativeGraphEngine:
             from ..algorithms.quantize import check_bits, granules_per_row
             native.check_graph_q_abi(self.lib)
             self.quant = (check_bits(quant[0]), int(quant[1]))
-        self.graph = graph
-        self.device = X.device
-        self.n, self.d = int(X.shape[0]), int(X.shape[2])
-        if self.n != graph.n:
-            raise ValueError("the graph has %d workers, the data %d shards" % (graph.n, self.n))
-        self.rho, self.obj0, self.tol, self.max_iter = float(rho), float(obj0), float(tol), int(max_iter)
-        self.xcd = int(xcd)
-        self.n_local = self.n_total = self.n
-        self.ring = self.LAG + 4
-        self.stream = stream if stream is not None else torch.cuda.Stream(self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        dev, f64, n, d, mi = self.device, torch.float64, self.n, self.d, self.max_iter
-        ptr, idx = graph.csr()
+        self._setup(graph, X, rho, obj0, tol, max_iter, xcd, stream)
+        dev, f64, n, d = self.device, torch.float64, self.n, self.d
         with torch.cuda.stream(self.stream):
             if precomputed is not None:
                 self.A, self.b, self.yy = precomputed
@@ -82,32 +72,57 @@ class NativeGraphEngine:
             else:
                 self._shifts = torch.tensor([[self.rho * g] for g in graph.degree], dtype=f64, device=dev)
                 self.Minv = spd_inverse(self.A, self._shifts)
-            self.theta = torch.zeros((n, d), dtype=f64, device=dev)
-            self.mu = torch.zeros((n, d), dtype=f64, device=dev)
-            # read-back block, as NativeChainEngine: [ctl (8 x i32) | t0stamp | pad x 3 | trace | tstamp]
-            self._rb = torch.zeros((8 + 2 * mi,), dtype=f64, device=dev)
-            self.ctl = self._rb[0:4].view(torch.int32)
-            self.t0stamp = self._rb[4:5].view(torch.int64)
-            self.trace = self._rb[8:8 + mi]
-            self.trace.fill_(float("nan"))
-            self.tstamp = self._rb[8 + mi:8 + 2 * mi].view(torch.int64)
-            self._rres = torch.zeros((mi * n,), dtype=f64, device=dev) if residual else None
-            self._nb_ptr = torch.from_numpy(ptr).to(dev)
-            self._nb_idx = torch.from_numpy(idx).to(dev)
-            self._wid = torch.tensor(graph.order, dtype=torch.int32, device=dev)
-            self._is_head = torch.tensor([1 if graph.is_head[w] else 0 for w in graph.order], dtype=torch.int32,
-                                         device=dev)
-            # granule tables: zeroed once, tags are salted per launch (never re-zeroed)
-            self._thg = torch.zeros((n * d * 4,), dtype=torch.int32, device=dev)
-            self._objg = torch.zeros((self.ring * n * 4,), dtype=torch.int32, device=dev)
-            self._decg = torch.zeros((self.ring,), dtype=torch.int64, device=dev)
-            self._dec_push = torch.tensor([self._decg.data_ptr()], dtype=torch.int64, device=dev)
-            self._xchk = torch.zeros((256 * 4,), dtype=torch.int32, device=dev)
+            self._alloc(residual)
             if self.quant is not None:
                 # the message table, zeroed once like thg (tags are salted per launch), and the true iterates
                 self.q_granules = granules_per_row(d, self.quant[0])
                 self._qg = torch.zeros((n * self.q_granules * 4,), dtype=torch.int32, device=dev)
                 self.theta_true = torch.zeros((n, d), dtype=f64, device=dev)
+        self._start()
+
+    def _setup(self, graph, X, rho, obj0, tol, max_iter, xcd, stream):
+        """The shape, the targets and the stream of the engine (ordered behind the caller's current stream)."""
+        self.graph = graph
+        self.device = X.device
+        self.n, self.d = int(X.shape[0]), int(X.shape[2])
+        if self.n != graph.n:
+            raise ValueError("the graph has %d workers, the data %d shards" % (graph.n, self.n))
+        self.rho, self.obj0, self.tol, self.max_iter = float(rho), float(obj0), float(tol), int(max_iter)
+        self.xcd = int(xcd)
+        self.n_local = self.n_total = self.n
+        self.ring = self.LAG + 4
+        self.stream = stream if stream is not None else torch.cuda.Stream(self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def _alloc(self, residual: bool):
+        """State, read-back block, CSR arrays and granule tables (called under the engine's stream)."""
+        dev, f64, n, d, mi = self.device, torch.float64, self.n, self.d, self.max_iter
+        graph = self.graph
+        ptr, idx = graph.csr()
+        self.theta = torch.zeros((n, d), dtype=f64, device=dev)
+        self.mu = torch.zeros((n, d), dtype=f64, device=dev)
+        # read-back block, as NativeChainEngine: [ctl (8 x i32) | t0stamp | pad x 3 | trace | tstamp]
+        self._rb = torch.zeros((8 + 2 * mi,), dtype=f64, device=dev)
+        self.ctl = self._rb[0:4].view(torch.int32)
+        self.t0stamp = self._rb[4:5].view(torch.int64)
+        self.trace = self._rb[8:8 + mi]
+        self.trace.fill_(float("nan"))
+        self.tstamp = self._rb[8 + mi:8 + 2 * mi].view(torch.int64)
+        self._rres = torch.zeros((mi * n,), dtype=f64, device=dev) if residual else None
+        self._nb_ptr = torch.from_numpy(ptr).to(dev)
+        self._nb_idx = torch.from_numpy(idx).to(dev)
+        self._wid = torch.tensor(graph.order, dtype=torch.int32, device=dev)
+        self._is_head = torch.tensor([1 if graph.is_head[w] else 0 for w in graph.order], dtype=torch.int32,
+                                     device=dev)
+        # granule tables: zeroed once, tags are salted per launch (never re-zeroed)
+        self._thg = torch.zeros((n * d * 4,), dtype=torch.int32, device=dev)
+        self._objg = torch.zeros((self.ring * n * 4,), dtype=torch.int32, device=dev)
+        self._decg = torch.zeros((self.ring,), dtype=torch.int64, device=dev)
+        self._dec_push = torch.tensor([self._decg.data_ptr()], dtype=torch.int64, device=dev)
+        self._xchk = torch.zeros((256 * 4,), dtype=torch.int32, device=dev)
+
+    def _start(self):
+        """End of construction: the set-up is complete on the stream, the state is reset."""
         self.stream.synchronize()
         self._epoch = 0
         self._rb_host = None
@@ -126,7 +141,7 @@ class NativeGraphEngine:
         a.timeout_ticks = int(timeout_s * 1e8)
         a.nb_ptr, a.nb_idx = self._nb_ptr.data_ptr(), self._nb_idx.data_ptr()
         a.wid, a.is_head = self._wid.data_ptr(), self._is_head.data_ptr()
-        a.Minv, a.A, a.b, a.yy = self.Minv.data_ptr(), self.A.data_ptr(), self.b.data_ptr(), self.yy.data_ptr()
+        a.Minv, a.A, a.b, a.yy = (native.ptr(t) for t in (self.Minv, self.A, self.b, self.yy))
         a.theta, a.mu = self.theta.data_ptr(), self.mu.data_ptr()
         a.thg, a.objg, a.decg = self._thg.data_ptr(), self._objg.data_ptr(), self._decg.data_ptr()
         a.dec_push = self._dec_push.data_ptr()

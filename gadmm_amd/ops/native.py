@@ -218,6 +218,27 @@ def check_graph_q_abi(lib) -> None:
                            "%s vs %s" % (list(buf[:k]), graph_q_abi_expected()))
 
 
+class GraphLogiArgs(ctypes.Structure):
+    """Mirror of ``GraphLogiArgs`` of csrc/include/gadmm_graph.h (persistent logistic GGADMM, inner GD):
+    ``GraphArgs`` first, then ``LogiArgs`` with its per-worker arrays by worker id."""
+    _fields_ = [("g", GraphArgs), ("l", LogiArgs)]
+
+
+def graph_logistic_abi_expected() -> list:
+    """What ``gadmm_graph_logistic_abi_layout`` must report for the ``GraphLogiArgs`` mirror above."""
+    S = GraphLogiArgs
+    return [ctypes.sizeof(S), S.g.offset, S.l.offset, ctypes.sizeof(GraphArgs), ctypes.sizeof(LogiArgs)]
+
+
+def check_graph_logistic_abi(lib) -> None:
+    """ABI self-check of ``GraphLogiArgs`` against the built library (raises on a mismatch: a stale build)."""
+    buf = (c_longlong * 8)()
+    k = lib.gadmm_graph_logistic_abi_layout(buf, 8)
+    if list(buf[:k]) != graph_logistic_abi_expected():
+        raise RuntimeError("GraphLogiArgs layout mismatch between gadmm_amd/ops/native.py and the native library: "
+                           "%s vs %s" % (list(buf[:k]), graph_logistic_abi_expected()))
+
+
 MODEL_LINEAR, MODEL_LOGISTIC = 0, 1
 
 
@@ -309,6 +330,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_graph_persistent_q_sweep_capacity": (c_int, []),
         "gadmm_graph_persistent_q_sweep_launch": (c_int, [ctypes.POINTER(GraphQArgs), c_int, c_void_p, c_void_p,
                                                           c_void_p]),
+        "gadmm_graph_logistic_abi_layout": (c_int, [ctypes.POINTER(c_longlong), c_int]),
+        "gadmm_graph_logistic_lds": (c_long, [c_int, c_int]),
+        "gadmm_graph_logistic_class": (c_int, [ctypes.POINTER(GraphLogiArgs)]),
+        "gadmm_graph_logistic_capacity": (c_long, [ctypes.POINTER(GraphLogiArgs)]),
+        "gadmm_graph_logistic_launch": (c_int, [ctypes.POINTER(GraphLogiArgs), c_void_p]),
         "gadmm_sym_pack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "gadmm_sym_packed_doubles": (c_long, [c_int]),
         "gadmm_ipc_box_bytes": (c_long, [c_int, c_int, c_int, c_int]),
