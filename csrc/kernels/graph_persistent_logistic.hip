@@ -44,18 +44,33 @@ using chain_dev::softplus;
 
 constexpr int GL_MAX_DK = 8;  // the widest poll group (profiles/glogistic/resource_usage.txt: no scratch at 8)
 
-template <int QT, int DK>
-__global__ void __launch_bounds__(64) graph_logistic_kernel(GraphLogiArgs ga) {
+// A sweep slot's GraphLogiArgs (graph_logistic_sweep_kernel below): written by the host before the launch
+// and never by a kernel, so it is read like kernel arguments, through the constant address space
+// (wave-uniform scalar loads), as GraphSweepArgs of graph_persistent.hip.
+typedef __attribute__((address_space(4))) GraphLogiArgs GraphLogiSweepArgs;
+
+// The persistent logistic GGADMM solve (described above) as a body shared by the single-solve and the
+// sweep kernel, as graph_body of graph_persistent.hip.
+// SWEEP: the body runs as one slot of graph_logistic_sweep_kernel: always 8-strided, this slot's blocks
+// are blockIdx.x >> 3, and a block past the slot's own n + 1 leaves before the placement check, any
+// barrier and any LDS flag (place_block_sweep). Everything the body reads or writes is named by the
+// slot's own arguments, and the LDS layout is the slot's own (its n and max_degree) inside a dynamic
+// allocation sized for the launch's largest.
+// GA: GraphLogiArgs (the kernel's own argument) or GraphLogiSweepArgs (a slot's entry).
+template <int QT, int DK, bool SWEEP, class GA>
+__device__ __forceinline__ void graph_logistic_body(const GA& ga) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const GraphArgs& a = ga.g;
-  const LogiArgs& g = ga.l;
+  const auto& a = ga.g;
+  const auto& g = ga.l;
   int* xflag = reinterpret_cast<int*>(lds);  // the placement verdict (xcd_verdict's LDS word)
   const int d = a.d, n = a.n, m = g.m;
   const int lane = threadIdx.x, qi = lane & 15, qc = lane >> 4;
   const __amdgpu_buffer_rsrc_t rth = rsrc_of(a.thg);
   const __amdgpu_buffer_rsrc_t rob = rsrc_of(a.objg);
   const unsigned long long deadline = now_ticks() + (unsigned long long)a.timeout_ticks;
-  const Placement pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  Placement pl;
+  if constexpr (SWEEP) pl = place_block_sweep(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
+  else pl = place_block<false>(a.xcd, a.xchk, (unsigned)a.xtag, n + 1, deadline, xflag, a.ctl);
   if (pl.spacer) return;
   const int bid = pl.bid;
   const bool local = pl.local;
@@ -200,6 +215,39 @@ __global__ void __launch_bounds__(64) graph_logistic_kernel(GraphLogiArgs ga) {
   }
 }
 
+template <int QT, int DK>
+__global__ void __launch_bounds__(64) graph_logistic_kernel(GraphLogiArgs ga) {
+  graph_logistic_body<QT, DK, false>(ga);
+}
+
+// Up to 8 independent logistic GGADMM solves in one launch, one per XCD: slot j = blockIdx.x & 7 runs
+// solve j on the blocks b % 8 == j, i.e. on the blocks that the single-solve launch leaves as exiting
+// spacers. batch[j] is solve j's own GraphLogiArgs: its own graph (CSR arrays, launch order), n, d, m, rho,
+// lam, step, max_inner, inner_tol, stop rule, theta / mu, granule table, objective and decision rings, ctl,
+// trace, tstamp, rres, inner_iters, xchk, tag salt and deadline; only the shards X, Y and the read-only CSR
+// arrays may be shared. Slots may differ in n, d and m (within the QT class), graph and degree class:
+// `classes` holds log2 of slot j's own DK (what pick_variant gives its single launch) in bits 4 j ..
+// 4 j + 3, and the wave-uniform switch below sends the slot into the body of that class, so every slot
+// executes the poll code of its own single solve (a chain member never runs a star's 8-wide poll group).
+// The three bodies hold the shard in the same 16 QT VGPRs each; the kernel's registers are those of its
+// widest body (profiles/glogistic_sweep/resource_usage.txt: no scratch). Nothing assumes WHICH XCD a
+// slot gets (place_block_sweep): a slot publishes with plain stores only after its own blocks reported one
+// XCC_ID under its own xtag, else with sc1 stores.
+template <int QT>
+__global__ void __launch_bounds__(64) graph_logistic_sweep_kernel(const GraphLogiArgs* __restrict__ batch, int nb,
+                                                                  unsigned classes) {
+  const int j = (int)(blockIdx.x & 7u);
+  if (j >= nb) return;
+  const GraphLogiSweepArgs& ga = *(const GraphLogiSweepArgs*)(batch + j);
+  switch ((classes >> (4 * j)) & 15u) {
+    case 1: graph_logistic_body<QT, 2, true>(ga); break;
+    case 2: graph_logistic_body<QT, 4, true>(ga); break;
+    default: graph_logistic_body<QT, GL_MAX_DK, true>(ga); break;
+  }
+}
+
+#define GRAPH_LOGISTIC_SWEEP_CAPACITY 8
+
 struct GLVariant {
   const void* fn = nullptr;
   size_t shm = 0;
@@ -228,8 +276,7 @@ GLVariant pick_variant(const GraphLogiArgs& ga) {
 
 // What the launch asks of its arguments, before residency: 0 fine, -1 malformed, -2 the staging does not
 // fit in LDS. No HIP call.
-int entry_check(const GraphLogiArgs& ga, const GLVariant& v) {
-  const char* who = "persistent graph logistic kernel";
+int entry_check(const GraphLogiArgs& ga, const GLVariant& v, const char* who = "persistent graph logistic kernel") {
   const GraphArgs& a = ga.g;
   const LogiArgs& g = ga.l;
   if (!v.fn) {
@@ -262,6 +309,13 @@ int entry_check(const GraphLogiArgs& ga, const GLVariant& v) {
 }
 
 }  // namespace
+
+template <>
+struct SweepSlot<GraphLogiArgs> {
+  static int& xcd(GraphLogiArgs& a) { return a.g.xcd; }
+  static int& xtag(GraphLogiArgs& a) { return a.g.xtag; }
+  static void set_dbg(GraphLogiArgs&, int) {}
+};
 
 extern "C" {
 
@@ -305,6 +359,57 @@ int gadmm_graph_logistic_launch(const GraphLogiArgs* args, hipStream_t st) {
   GADMM_CHECK(hipLaunchKernel(v.fn, dim3(ka.g.xcd > 0 ? 8 * blocks : blocks), dim3(64), kargs, v.shm, st));
   GADMM_CHECK(hipGetLastError());
   return 0;
+}
+
+// Solves one launch of graph_logistic_sweep_kernel can run side by side (one per XCD).
+int gadmm_graph_logistic_sweep_capacity() { return GRAPH_LOGISTIC_SWEEP_CAPACITY; }
+
+// nb <= 8 independent logistic GGADMM solves (one register class: max(d, m) <= 52 or 53..64; any graphs,
+// each slot on the degree class of its own single launch) in ONE launch, solve j on the blocks b % 8 == j.
+// Every entry passes the single launch's checks and names its own written buffers (gadmm_graph_sweep_shares
+// on the GraphArgs parts, plus inner_iters) and a placement-check buffer. Dynamic LDS: the largest entry's.
+// Staging buffers and the residency refusal (-2: the sum of the workgroups, or one solve's n + 1 past the
+// CUs of an XCD): gadmm_sweep_launch_as. -1: refused before any HIP call.
+int gadmm_graph_logistic_sweep_launch(const GraphLogiArgs* batch, int nb, GraphLogiArgs* host_stage,
+                                      GraphLogiArgs* dev_stage, hipStream_t st) {
+  const char* name = "persistent graph logistic sweep";
+  if (!gadmm_sweep_batch_ok(name, batch, nb, GRAPH_LOGISTIC_SWEEP_CAPACITY, host_stage, dev_stage)) return -1;
+  int blocks[GRAPH_LOGISTIC_SWEEP_CAPACITY], dk[GRAPH_LOGISTIC_SWEEP_CAPACITY];
+  size_t shm = 0;
+  const auto small = [](const GraphLogiArgs& s) { return (s.g.d > s.l.m ? s.g.d : s.l.m) <= 52; };
+  for (int j = 0; j < nb; ++j) {
+    const GraphArgs& a = batch[j].g;
+    char who[56];
+    snprintf(who, sizeof(who), "%s: solve %d", name, j);
+    if (small(batch[j]) != small(batch[0])) {
+      gadmm_set_error("%s: solves of different register classes (max(d, m) <= 52 or 53..64)", name);
+      return -1;
+    }
+    const GLVariant v = pick_variant(batch[j]);
+    if (const int rc = entry_check(batch[j], v, who)) return rc;
+    if (!a.xchk) {
+      gadmm_set_error("%s has no placement-check buffer (xchk)", who);
+      return -1;
+    }
+    blocks[j] = a.n + 1;
+    if (blocks[j] > XCHK) {
+      gadmm_set_error("%s has %d workgroups, the placement check holds %d", who, blocks[j], XCHK);
+      return -1;
+    }
+    for (int i = 0; i < j; ++i)
+      if (gadmm_graph_sweep_shares(a, batch[i].g) ||
+          (batch[j].l.inner_iters && batch[i].l.inner_iters == batch[j].l.inner_iters)) {
+        gadmm_set_error("%s: solves %d and %d share a buffer that both write", name, i, j);
+        return -1;
+      }
+    dk[j] = v.dk;
+    if (v.shm > shm) shm = v.shm;
+  }
+  unsigned classes = gadmm_graph_sweep_classes(dk, nb);
+  const void* fn = small(batch[0]) ? (const void*)graph_logistic_sweep_kernel<13>
+                                   : (const void*)graph_logistic_sweep_kernel<16>;
+  return gadmm_sweep_launch_as<GraphLogiArgs>({fn, 64, shm, name, false}, batch, nb, blocks, host_stage, dev_stage, st,
+                                              &classes);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ XCD (engine/sweep_base.py and the three engines on it); anywhere else the loop o
   ``dynamic_group_admm_sweep``    D-GADMM at several coherences (engine/dyn_sweep.py)
   ``graph_admm_sweep``            GGADMM / Q-GGADMM over several (graph, rho[, bits, seed]) (engine/graph_sweep.py)
   ``logistic_admm_sweep``         logistic inner-GD GADMM under several rho / (rho, max_inner, inner_tol) (engine/logistic_sweep.py)
+  ``graph_admm_logistic_sweep``   logistic GGADMM over several (graph, rho[, step, max_inner, inner_tol]) (engine/graph_logistic_sweep.py)
 
 They are one driver (``_run_sweep``: the gates that send a call to the loop, the groups of one
 launch, the fall-back when a launch is refused) around what each sweep knows: its gates and their
@@ -416,6 +417,71 @@ def graph_admm_sweep(model, members: Sequence, obj0: float, tol: float, max_iter
         for i, r in zip(idx, res):
             out[i] = r
     return out
+
+
+def graph_admm_logistic_sweep(model, members: Sequence, obj0: float, tol: float, max_iter: int, step: float, *,
+                              max_inner: int = 100, inner_tol: float = 1e-4, tols: Optional[Sequence[float]] = None,
+                              backend: str = "auto", name: str = "GGADMM-logistic", engine_opts: Optional[dict] = None,
+                              comm: Optional[Comm] = None) -> List[RunResult]:
+    """Logistic GGADMM of ``model`` (inner-GD local solves) under every member of ``members`` -- ``(graph,
+    rho)`` or ``(graph, rho, step, max_inner, inner_tol)`` -- one ``RunResult`` per member, in the order given,
+    equal to ``[graph_admm_logistic(model, graph, rho, ..., step, max_inner=.., inner_tol=..) ...]`` in
+    iterations, objective trace, ``comm_units``, primal residual, ``converged``, ``extra['graph']`` and
+    ``extra['deliveries']``. ``step`` / ``max_inner`` / ``inner_tol`` are those of a member given as ``(graph,
+    rho)``; ``lam`` is the model's. On one HIP device the solves run side by side, up to eight per kernel
+    launch, one per XCD (engine/graph_logistic_sweep.py; more members run in groups), each to its own stop:
+    ``tols`` gives one tolerance per member (default ``tol`` for all). Each result then carries the single
+    native solve's fields plus ``extra['sweep'] = {width, slot, kernel, placed, wall_ms_launch}`` and
+    ``extra['kernel']`` (the sweep's), and its ``wall_s`` is that solve's OWN time (as ``chain_admm_sweep``).
+    ``extra['state']`` is not produced. Anywhere else -- ``backend='torch'``, CPU tensors, several ranks, not
+    a logistic model, max(d, m) > 64, a member graph whose ``n`` is not the model's, no native library, or a
+    launcher that refuses the group (``ResidencyError``: a graph of more than 31 workers does not fit one
+    XCD's slot; a shape it does not take) -- it IS that loop, and every result records
+    ``extra['sweep_fallback'] = reason``. A hand-off timeout propagates. ``engine_opts``: ``cache``, ``xcd``,
+    ``residual``, ``timeout_s`` as in ``graph_admm_logistic``."""
+    from ..engine.graph_logistic_sweep import parse_member  # (no device code is touched by the import)
+    parsed = [parse_member(m, step, max_inner, inner_tol) for m in members]
+    opts = dict(engine_opts or {})
+    tols = [float(tol)] * len(parsed) if tols is None else [float(t) for t in tols]
+    if len(tols) != len(parsed):
+        raise ValueError("tols: one per member")
+    xcd = int(opts.get("xcd", 2))
+    residual = bool(opts.get("residual", True))
+    n_model = int(model.n_local)
+    lam = float(getattr(model, "lam", 0.0))
+
+    def sequential_one(mem):
+        from .ggadmm import graph_admm_logistic
+        (g, rho, st, mi, it), t = mem
+        return graph_admm_logistic(model, g, rho, obj0, t, max_iter, st, max_inner=mi, inner_tol=it, backend=backend,
+                                   name=name, engine_opts=engine_opts, comm=comm)
+
+    def run_group(group, idx):
+        from ..engine.graph_logistic_sweep import GraphLogisticSweepEngine
+        t_begin = time.perf_counter()
+        g_mems, g_tols = [g[0] for g in group], [g[1] for g in group]
+        key = ("graph-logistic-sweep", tuple((m[0].key(),) + m[1:] for m in g_mems), lam, int(max_iter), xcd, residual)
+        sw = _group_engine(model, key, opts, lambda: GraphLogisticSweepEngine.build(
+            model.X, model.y, g_mems, lam, step, obj0=obj0, tols=g_tols, max_iters=max_iter, xcd=xcd,
+            residual=residual), (obj0, g_tols))
+        out = _one_launch_results(name, sw, t_begin, obj0, n_model, primal=residual,
+                                  timeout_s=float(opts.get("timeout_s", 20.0)))
+        for res, mem in zip(out, g_mems):
+            res.extra.update(solver="gd", kernel=sw.last_kernel, placed=res.extra["sweep"]["placed"],
+                             graph=mem[0].describe(), deliveries=res.iters * 2 * len(mem[0].edges))
+        return out
+
+    def capacity():
+        from ..engine.graph_logistic_sweep import graph_logistic_sweep_capacity
+        return graph_logistic_sweep_capacity()
+
+    gates = [(backend == "torch", "torch backend"), (model.device.type != "cuda", "cpu tensors"),
+             (comm is not None and comm.nranks > 1, "several ranks"),
+             (getattr(model, "kind", None) != "logistic", "not a logistic model"),
+             (max(model.d, getattr(model, "m", 0)) > 64, "max(d, m) > 64"),
+             (any(m[0].n != n_model for m in parsed), "a member graph's n differs from the model's")]
+    return _run_sweep(list(zip(parsed, tols)), sequential_one, gates, capacity, run_group,
+                      "%s sweep native-graph-logistic N=%d K=%d" % (name, n_model, len(parsed)))
 
 
 def dynamic_group_admm_sweep(model, rho, obj0, acc, max_iter, path, path_cost, coherences, seeds, kind="findPath2",

@@ -335,6 +335,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         "gadmm_graph_logistic_class": (c_int, [ctypes.POINTER(GraphLogiArgs)]),
         "gadmm_graph_logistic_capacity": (c_long, [ctypes.POINTER(GraphLogiArgs)]),
         "gadmm_graph_logistic_launch": (c_int, [ctypes.POINTER(GraphLogiArgs), c_void_p]),
+        "gadmm_graph_logistic_sweep_capacity": (c_int, []),
+        "gadmm_graph_logistic_sweep_launch": (c_int, [ctypes.POINTER(GraphLogiArgs), c_int, c_void_p, c_void_p,
+                                                      c_void_p]),
         "gadmm_sym_pack_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
         "gadmm_sym_packed_doubles": (c_long, [c_int]),
         "gadmm_ipc_box_bytes": (c_long, [c_int, c_int, c_int, c_int]),
